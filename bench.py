@@ -2,8 +2,15 @@
 """Headline benchmark: Grid.interp + Grid.diff on a 3600 x 2400 x 75 float64 MITgcm-like C-grid
 (BASELINE.json configs[1]), periodic X / extend Y, through the public `xgcm_amd.Grid` API.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line; everything else this file measures or
+checks (`cpu_baseline` and the parity spot check, the `configs` block with its `box_probe`, the live rocprofv3 PMC passes
+of `roofline.traffic`) runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed (rank 0's
+record) as DIR/<op>_<axis>.npy, float64: the whole output when it has at most DUMP_SAMPLE cells, else a fixed, seeded
+sample of DUMP_SAMPLE cells of it (the same cells in every run of the same shape), so that two builds can be compared
+output for output.
 
 One "step" = one pass of the hot path over one resident record (field T(Z,YC,XC), 648e6 cells):
 interp(T,'X'), diff(T,'X') [contiguous axis, periodic] and interp(T,'Y'), diff(T,'Y') [strided
@@ -14,10 +21,10 @@ data-path collective); RCCL is used for the barriers and
 reduction only => weak scaling, value = cells of all ranks / max-over-ranks time.
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed inside the timed
-region) and `cpu_baseline` (the numpy oracle = the reference's eager call sequence, timed on a
+region) and, with `--full`, `cpu_baseline` (the numpy oracle = the reference's eager call sequence, timed on a
 bounded sample on this box's host cores; N=1 only).
 
-AFTER the headline's timed region (value / ms_per_step are not touched by it) the same process puts
+With `--full`, AFTER the headline's timed region (value / ms_per_step are not touched by it) the same process puts
 one-rank shares of BASELINE configs[2..4] under the same clock and adds them to the line as `configs`
 (`--no-configs` skips it): config 3 `derivative` X / Y / Z with random 2-D / 1-D metrics + `integrate` Z,
 config 4 `cumsum` Z center->left / center->outer over a resident batch of 3 records, config 5 the fused
@@ -45,6 +52,8 @@ BASELINE_SHAPES = ((NZ, NY, NX), CONFIG5_SHAPE)
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 BYTES_PER_CELL = 16.0  # 1 f64 read + 1 f64 write per output cell
 OPS = [("interp", "X"), ("diff", "X"), ("interp", "Y"), ("diff", "Y")]
+DUMP_SAMPLE = 1_500_000  # cells per dumped output: 4 x 12 MB of float64 stays under 64 MB
+DUMP_SEED = 20240601
 
 
 class Mark:
@@ -452,13 +461,34 @@ def check_configs(block, slabs):
                         "against oracle/refimpl.py on the same slab of the input, numpy.array_equal")
 
 
+def dump_outputs(outdir, outs):
+    """`--dump-outputs`: the results of the last timed step (one DataArray per entry of OPS) -> outdir/<op>_<axis>.npy, float64;
+    a result of more than DUMP_SAMPLE cells is reduced to the same seeded, sorted sample of flat indices in every run"""
+    from xgcm_amd import device as D
+
+    os.makedirs(outdir, exist_ok=True)
+    for (fn, ax), res in zip(OPS, outs):
+        flat = res.data.reshape(-1)
+        n = flat.shape[0]
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+            flat = flat[torch.as_tensor(idx, device=flat.device)]
+        np.save(os.path.join(outdir, f"{fn}_{ax}.npy"), np.ascontiguousarray(D.tohost(flat), dtype=np.float64))
+
+
 
 def main():
     global NZ, NY, NX, CONFIG5_SHAPE
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (rank 0) as DIR/<op>_<axis>.npy, float64, "
+                         f"a seeded sample of {DUMP_SAMPLE} cells each where a result is larger")
+    ap.add_argument("--full", action="store_true", help="also run the legs the headline does not need: cpu_baseline + parity spot "
+                    "check, the `configs` block with box_probe, the live PMC passes of roofline.traffic (each still subject to its --no-* "
+                    "switch below)")
     ap.add_argument("--levels", type=int, default=NZ, help="Z levels (default = the full 75; smaller only for debugging)")
     ap.add_argument("--shape", default="", help="Z,Y,X of the record and Z,Y,X of config 5, ';'-separated -- plumbing checks only (the CPU dry run of "
                     "tests/test_bench_dryrun.py): a line from another shape than BASELINE's says so in `config.workload` and is no measurement")
@@ -472,6 +502,10 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic with rocprofv3 --pmc child passes (N = 1 only; "
                     "also XG_BENCH_PMC=0): the committed figure of profiles/pmc_traffic.json is reported instead")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: setup, warmup, the timed steps, the outputs if asked for, the line
+        args.no_cpu_baseline = args.no_configs = args.no_pmc = True
     if args.shape:
         rec, _, c5 = args.shape.partition(";")
         NZ, NY, NX = (int(v) for v in rec.split(","))
@@ -504,11 +538,20 @@ def main():
     field = D.synthetic((nz, NY, NX), 2, offset=rank * cells_per_op)
     grid, T = build_grid(nz, field)
 
+    # --dump-outputs: every step (priming and warmup included, so that the allocator holds all four results before the timed
+    # region) keeps its results until it returns; without it each result is dropped as soon as it is made
+    keep = args.dump_outputs is not None
+
     def step(marks=None):
+        outs = []
         for i, (fn, ax) in enumerate(OPS):
-            getattr(grid, fn)(T, ax)
+            if keep:
+                outs.append(getattr(grid, fn)(T, ax))
+            else:
+                getattr(grid, fn)(T, ax)
             if marks is not None:
                 marks.append(Mark())
+        return outs
 
     barrier = ranks.barrier  # synchronize, barrier over the process group (RCCL), synchronize
 
@@ -540,10 +583,14 @@ def main():
     t0 = time.perf_counter()
     for k in range(K):
         ev[k].append(Mark())
-        step(ev[k])
+        outs = None  # (the previous step's results, if kept, go before this step makes its own)
+        outs = step(ev[k])
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if keep and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
+    del outs
 
     local_cells = K * len(OPS) * cells_per_op
     per_rank_ms_per_step = [round(v / K * 1e3, 4) for v in ranks.gather_floats(elapsed)]

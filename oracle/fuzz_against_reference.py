@@ -16,7 +16,7 @@ of the product, which are compared to 1e-12.
 
     python oracle/fuzz_against_reference.py --cases 200 --seed 1 [--backend oracle-double|host-abi] [-v]
 
-`tests/test_reference_suite_live.py::test_differential_fuzz_against_the_reference` runs a fixed budget of it on every CPU run.
+`tests/test_reference_suite_live.py::test_differential_fuzz_against_the_reference` replays the recorded answers of seeds 101-103.
 What it pins is the reference's LOGIC under the stand-in's container semantics ("pinned modulo the stand-in").
 """
 import argparse

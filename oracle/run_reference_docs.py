@@ -17,7 +17,7 @@ the first and a shim over `xgcm_amd` in the second (same trick as `oracle/run_re
 package where importable, else the stand-in (`oracle/xr_min.py` + `xr_suite.py`); plotting is stubbed.  After each block
 every labelled array in the namespace is snapshotted (dims, name, coordinate names, values) -- the parent compares the two
 runs block by block: same variables, same snapshots (1e-12 for re-associated scans), same exception class where a block
-raises.  `tests/test_reference_suite_live.py::test_documentation_examples` runs it wherever the reference tree is.
+raises.  Run it by hand wherever the reference tree is (the repository does not hold the documentation it executes).
 """
 import argparse
 import json

@@ -17,8 +17,8 @@ GPU box that has the reference, the real library.  pytest then collects `xgcm/te
 What a pass means: the reference's assertion, written by its authors against its own implementation, holds for
 `xgcm_amd` under the stand-in's container semantics ("pinned modulo the stand-in", as DESIGN section 7 says for every
 fixture made this way).  Every outcome is written to a JSON report; `tests/golden/reference_suite_report.json` is the
-committed one and `tests/test_reference_suite_live.py` re-runs the suite wherever /root/reference exists and fails on any
-test that passed in the committed report and no longer does.
+committed one; compare a fresh report with it (`tests/test_reference_suite_live.py` holds what the tests can replay without
+the reference: recorded fuzz answers and the public surface).
 """
 import argparse
 import json

@@ -2,7 +2,7 @@
 "next round" 4): a CPU dry run of exactly those commands with gloo ranks.  Everything on the path is the real thing --
 `sharding.ensure_ranks` (the self-relaunch under torch.distributed.run), `init_ranks`, `bind_to_gpu_numa`, the barriers, the
 gathers, the max-over-ranks clock, the JSON line with its `configs` block -- except the memory the device layer computes in:
-`tests/dryrun_site/usercustomize.py` swaps it for the host build of the C ABI in every process of the run (the ranks' product
+`tests/dryrun_site/sitecustomize.py` swaps it for the host build of the C ABI in every process of the run (the ranks' product
 path imports nothing from `oracle/`; bench.py's own oracle checks of the `configs` slabs run on rank 0 as they do on the GPU)."""
 import json
 import os
@@ -25,7 +25,7 @@ def _env():
 
 
 def _bench(n, extra=(), launcher=False):
-    args = ["bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--shape", SHAPE, "--no-pmc", "--config4-records", "2",
+    args = ["bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--shape", SHAPE, "--full", "--no-pmc", "--config4-records", "2",
             "--config-reps", "2", *extra]
     if launcher:  # as the round-end driver starts N > 1
         from xgcm_amd.sharding import _free_port

@@ -60,12 +60,12 @@ def test_two_ranks_on_the_real_library_equal_one_rank_and_the_oracle():
 
 
 def test_bench_line_measures_its_hbm_traffic_in_the_run():
-    """`roofline.traffic` of the N = 1 line comes from two `rocprofv3 --pmc` child passes of the same command made after the
+    """`roofline.traffic` of the N = 1 `--full` line comes from two `rocprofv3 --pmc` child passes of the same command made after the
     timed region (FETCH_SIZE, WRITE_SIZE, one per pass); the flat stencils move their algorithmic bytes and nothing else.
     Without rocprofv3 the committed figure is reported and flagged."""
     import shutil
 
-    p, lines = _run([BENCH, "--steps", "3", "--warmup", "1", "--levels", "12", "--no-cpu-baseline"], timeout=500)
+    p, lines = _run([BENCH, "--steps", "3", "--warmup", "1", "--levels", "12", "--full", "--no-cpu-baseline"], timeout=500)
     assert p.returncode == 0, p.stderr[-3000:]
     roof = lines[-1]["roofline"]
     if shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3"):
@@ -73,7 +73,7 @@ def test_bench_line_measures_its_hbm_traffic_in_the_run():
         assert 0.98 <= roof["traffic_over_algorithmic"] <= 1.05, roof
     else:
         assert roof["traffic_measured_in_run"] is False
-    p, lines = _run([BENCH, "--steps", "2", "--warmup", "0", "--levels", "4", "--no-cpu-baseline", "--no-pmc"])
+    p, lines = _run([BENCH, "--steps", "2", "--warmup", "0", "--levels", "4", "--full", "--no-cpu-baseline", "--no-pmc"])
     assert p.returncode == 0 and lines[-1]["roofline"]["traffic_measured_in_run"] is False
 
 
@@ -103,7 +103,7 @@ def test_bench_configs_block_on_the_real_library(ranks):
     operators timed with HIP events, every kept slab equal to the oracle bit for bit, the box probe's three launches; with two
     ranks (gloo, sharing the one GPU) the per-rank times of every operator and the job's aggregate."""
     env = {} if ranks == 1 else {"XG_DIST_BACKEND": "gloo", "XG_SHARE_GPU": "1"}
-    p, lines = _run([BENCH, "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--shape", "6,64,256;8,64,128", "--no-pmc",
+    p, lines = _run([BENCH, "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--shape", "6,64,256;8,64,128", "--full", "--no-pmc",
                      "--config4-records", "2", "--config-reps", "3"], env)
     assert p.returncode == 0 and len(lines) == 1, p.stderr[-3000:]
     ln = lines[0]

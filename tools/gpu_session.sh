@@ -8,7 +8,7 @@
 # from where the files worth keeping are copied to profiles/<name>_* by hand.  Steps:
 #     pytest [pytest args]        the GPU suite (default: tests -m gpu -q)            -> pytest_gpu.log
 #     smoke                       __graft_entry__.smoke()                              -> smoke.log
-#     bench [bench.py args]       the driver's bench line                             -> bench_1gpu.json
+#     bench [bench.py args]       bench.py --full: the line with configs, box_probe    -> bench_1gpu.json
 #     bench_rccl                  the same through RCCL with one rank                  -> bench_rccl_ws1.json
 #     configs                     tools/bench_configs.py 2,3 / 4,5 (45 records) / 5x,f1 -> configs_*.jsonl
 #     tables                      tools/microbench.py f64 + f32                        -> microbench_*.jsonl
@@ -48,8 +48,8 @@ while IFS= read -r line || [ -n "$line" ]; do
   case $step in
     pytest) timeout 900 python -m pytest ${@:-tests -m gpu -q} 2>&1 | tail -15 | tee $S/pytest_gpu.log ;;
     smoke) timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $S/smoke.log ;;
-    bench) timeout 400 python bench.py "$@" 2>&1 | tail -1 | tee $S/bench_1gpu.json ;;
-    bench_rccl) XG_BENCH_FORCE_DIST=1 timeout 300 python bench.py --no-cpu-baseline 2>&1 | tail -1 | tee $S/bench_rccl_ws1.json ;;
+    bench) timeout 400 python bench.py --full "$@" 2>&1 | tail -1 | tee $S/bench_1gpu.json ;;
+    bench_rccl) XG_BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --no-cpu-baseline 2>&1 | tail -1 | tee $S/bench_rccl_ws1.json ;;
     configs)
       timeout 300 python tools/bench_configs.py --configs 2,3 2>&1 | grep '^{' | tee $S/configs_2_3.jsonl | cut -c1-220
       timeout 400 python tools/bench_configs.py --gpus 1 --configs 4,5 --records 45 2>&1 | grep '^{' | tee $S/configs_4_5_sharded_1rank.jsonl | cut -c1-260

@@ -65,7 +65,7 @@ def main():
             skipped.append(n)
             continue
         if not a.skip_bench:
-            rc, lines, err = run([sys.executable, "bench.py", "--gpus", str(n), "--steps", str(a.steps), "--warmup", str(a.warmup), "--no-cpu-baseline", "--no-pmc"]
+            rc, lines, err = run([sys.executable, "bench.py", "--gpus", str(n), "--steps", str(a.steps), "--warmup", str(a.warmup), "--full", "--no-cpu-baseline", "--no-pmc"]
                                  + (["--shape", a.bench_shape, "--config4-records", "2", "--config-reps", "2"] if a.bench_shape else []))
             for ln in lines:
                 if "value" in ln:
