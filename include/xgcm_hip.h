@@ -38,6 +38,8 @@
  *   xg_divergence_f64  the chained (diff(u,X) + diff(v,Y)) / area of docs/ufunc_examples.md, fused
  *   xg_vorticity_f64   the chained (diff(v,X) - diff(u,Y)) / area of docs/ufunc_examples.md
  *                      (one fused pass instead of three apply_ufunc passes, grid.py:798-800 TODO)
+ *   xg_flux_divergence_f64 / xg_laplacian_f64  divergence(flux(u, v, T)) (the "Advection" tendency of
+ *                      docs/ufunc_examples.md) and the finite-volume del2, two-step chains in one pass
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -333,6 +335,27 @@ int xg_divergence_halo_f64(const double* u, const double* v, const double* halo_
                            double* out, const int64_t* shape, int ndim, int bc_x, double fill_x,
                            int bc_y, double fill_y, void* stream);
 
+/* ---- fused second-order operators: an intermediate staggered field that never reaches memory ---- */
+/* One pass each, bit-identical to the two-step chains they replace (xg_flux_f64 / xg_gradient_f64,
+ * the metric products of the laplacian, then xg_divergence_f64), on arrays of identical `shape`
+ * (.., Y, X), u at (Y:center, X:left), v at (Y:left, X:center), t / a and out at the centre:
+ *   flux_divergence: Fx = u * (t[j,i-1] + t[j,i]) / 2,  Fy = v * (t[j-1,i] + t[j,i]) / 2
+ *   laplacian:       Fx = (a[j,i] - a[j,i-1]) / dxC * dyG,  Fy = (a[j,i] - a[j-1,i]) / dyC * dxG
+ *                    (all four metrics NULL: the plain differences)
+ *   out[j,i] = ((Fx[j,i+1] - Fx[j,i]) + (Fy[j+1,i] - Fy[j,i])) / area   (area NULL: no division)
+ * The chain pads twice with the same bc / fill per axis: t / a below / left of the first row / column
+ * as in xg_flux_f64, and the intermediate above / right of the last one as in xg_divergence_f64 --
+ * periodic: the intermediate at index 0, extend: at n-1, fill: fill_x / fill_y itself.  Metrics and
+ * area use broadcast strides (0 = broadcast) against `shape`.  XG_BC_HALO is not accepted. */
+int xg_flux_divergence_f64(const double* u, const double* v, const double* t, const double* area,
+                           const int64_t* area_strides, double* out, const int64_t* shape, int ndim,
+                           int bc_x, double fill_x, int bc_y, double fill_y, void* stream);
+int xg_laplacian_f64(const double* a, const double* dxC, const int64_t* dxC_strides, const double* dyC,
+                     const int64_t* dyC_strides, const double* dyG, const int64_t* dyG_strides,
+                     const double* dxG, const int64_t* dxG_strides, const double* area,
+                     const int64_t* area_strides, double* out, const int64_t* shape, int ndim, int bc_x,
+                     double fill_x, int bc_y, double fill_y, void* stream);
+
 /* ---- the same two-point operator along the last TWO axes in one pass -------------------- */
 /* out = OP_second(pad(OP_first(pad(in)))) for (.., Y, X) arrays, order 0: X then Y, 1: Y then X;
  * replaces two sequential apply_as_grid_ufunc passes of Grid.interp/diff/min/max(da, [ax1, ax2])
@@ -427,6 +450,14 @@ int xg_divergence_halo_f32(const float* u, const float* v, const float* halo_x, 
                            const float* area, const int64_t* area_strides, float* out,
                            const int64_t* shape, int ndim, int bc_x, float fill_x, int bc_y,
                            float fill_y, void* stream);
+int xg_flux_divergence_f32(const float* u, const float* v, const float* t, const float* area,
+                           const int64_t* area_strides, float* out, const int64_t* shape, int ndim,
+                           int bc_x, float fill_x, int bc_y, float fill_y, void* stream);
+int xg_laplacian_f32(const float* a, const float* dxC, const int64_t* dxC_strides, const float* dyC,
+                     const int64_t* dyC_strides, const float* dyG, const int64_t* dyG_strides,
+                     const float* dxG, const int64_t* dxG_strides, const float* area,
+                     const int64_t* area_strides, float* out, const int64_t* shape, int ndim, int bc_x,
+                     float fill_x, int bc_y, float fill_y, void* stream);
 int xg_stencil2d_f32(int op, const float* in, float* out, const int64_t* shape, int ndim, int order,
                      int padx_lo, int padx_hi, int bc_x, float fill_x, int pady_lo, int pady_hi,
                      int bc_y, float fill_y, void* stream);

@@ -96,6 +96,8 @@ def main():
         "grad_same": (lambda: D.gradient(T, "periodic", "extend", 0.0, 0.0, dx, dx), 24 + 8 / nz),      # two metric loads per row, ONE plane
         "grad_off": (lambda: D.gradient(T, "periodic", "extend", 0.0, 0.0, dx, dx2_off), 24 + 16 / nz),  # the second plane 2 KiB + 256 B further on
         "flux": (lambda: D.flux(U, V, T, "periodic", "extend"), 40),
+        "advT": (lambda: D.flux_divergence(U, V, T, dx, "periodic", "extend"), 32 + 8 / nz),  # divergence(flux(u, v, T)) in one pass
+        "lapT": (lambda: D.laplacian(T, "periodic", "extend", 0.0, 0.0, dx, dx2, dx2, dx, dx), 16 + 16 / nz),  # del2: its five metrics from two planes
     }
     cases = a.cases.split(",")
     dx2_off = None
@@ -145,7 +147,7 @@ def main():
             R = int(c[5:])
             TR = D.synthetic((R, nz, ny, nx), 4)
             CASES[c] = ((lambda TR=TR: D.cumsum1d(TR, 1, 0, 1, 1, 0, "fill")), 16 * R)
-    if any(c in cases for c in ("vort", "divg", "flux")):
+    if any(c in cases for c in ("vort", "divg", "flux", "advT")):
         U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
     variants = []
     for spec in a.variants.split(";"):
@@ -174,7 +176,7 @@ def main():
                 T2 = D.synthetic((nz, ny, nx), 9, 0, 1000.0, 1000.0)
             if T3k:
                 T3 = D.synthetic((nz, ny, nx), 10, 0, 1000.0, 1000.0)
-            if any(c in cases for c in ("vort", "divg", "flux")):
+            if any(c in cases for c in ("vort", "divg", "flux", "advT")):
                 U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
             for c in cases:
                 CASES[c][0]()

@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian against their chains), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -590,6 +590,32 @@ def main():
         fx, fy = grid_div.flux(U, V, T5)
         okf = bool(torch.equal(fx.data, (U * grid_div.interp(T5, "X")).data) and torch.equal(fy.data, (V * grid_div.interp(T5, "Y")).data))
         print(json.dumps({"config": 5, "check": "fused gradient / flux == operator chains bit for bit at full size", "ok": okg and okf}), flush=True)
+        del fx, fy
+        # the second-order chains in one pass: divergence(flux(u, v, T)) and the finite-volume del2 (five 2-D metric planes)
+        m2 = lambda seed, dims: DataArray(D.synthetic((n5, n5), seed, 0, 1000.0, 1000.0), dims)  # noqa: E731
+        ds2 = Dataset({"dxC": grid._ds["dxC"], "dyC": grid._ds["dyC"], "dyG": m2(35, ("YC", "XG")), "dxG": m2(36, ("YG", "XC")),
+                       "rA": m2(37, ("YC", "XC"))},
+                      {"XC": ("XC", np.arange(n5) + 0.5), "XG": ("XG", np.arange(n5) * 1.0),
+                       "YC": ("YC", np.arange(n5) + 0.5), "YG": ("YG", np.arange(n5) * 1.0), "Z": ("Z", np.arange(nz5) + 0.5)})
+        g2 = Grid(ds2, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"}},
+                  padding={"X": "periodic", "Y": "extend"}, autoparse_metadata=False,
+                  metrics={("X",): ["dxC", "dxG"], ("Y",): ["dyC", "dyG"], ("X", "Y"): ["rA"]})
+
+        def adv_chain():
+            return g2.divergence(*g2.flux(U, V, T5))
+
+        def lap_chain():
+            gx, gy = g2.gradient(T5, metric_weighted=True)
+            return g2.divergence(gx * g2.get_metric(gx, ("Y",)), gy * g2.get_metric(gy, ("X",)))
+
+        rec(5, "flux_divergence fused divergence(flux(u,v,T))/rA, periodic/extend: 3 reads + 1 write", timeit(lambda: g2.flux_divergence(U, V, T5), a.reps), c5, 32 + 8 / nz5)
+        rec(5, "flux_divergence as its chain (flux + divergence), fused-equivalent bytes", timeit(adv_chain, a.reps), c5, 32 + 8 / nz5)
+        oka = bool(torch.equal(g2.flux_divergence(U, V, T5).data, adv_chain().data))
+        print(json.dumps({"config": 5, "check": "fused flux_divergence == chain bit for bit at full size", "ok": oka}), flush=True)
+        rec(5, "laplacian fused (dxC, dyC, dyG, dxG, rA), periodic/extend: 1 read + 1 write", timeit(lambda: g2.laplacian(T5), a.reps), c5, 16 + 40 / nz5)
+        rec(5, "laplacian as its chain (gradient, 2 products, divergence), fused-equivalent bytes", timeit(lap_chain, a.reps), c5, 16 + 40 / nz5)
+        okl = bool(torch.equal(g2.laplacian(T5).data, lap_chain().data))
+        print(json.dumps({"config": 5, "check": "fused laplacian == chain bit for bit at full size", "ok": okl}), flush=True)
     ranks.close()
 
 

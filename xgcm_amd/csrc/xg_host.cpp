@@ -8,8 +8,9 @@
 // layer raises without a GPU; the only users are tests/ (tests/host_abi_device.py) and examples/.  It has its own
 // straightforward loops (one output cell at a time, index arithmetic in the open), written against the header's
 // semantics, not against the kernels or the oracle.  It serves the 1-D operators of SURVEY.md section 8(a):
-// stencil (+ pre-gathered halos), cumsum, reduce, pad, the broadcasting binary op and the synthetic generator; the
-// fused / topology / transform entry points exist and return XG_ERR_UNSUPPORTED.
+// stencil (+ pre-gathered halos), cumsum, reduce, pad, the broadcasting binary op and the synthetic generator, plus the
+// fused divergence / vorticity / flux divergence / laplacian; the other fused / topology / transform entry points exist
+// and return XG_ERR_UNSUPPORTED.
 //
 // Build: g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off  (no FMA contraction: same bit contract as the kernels)
 
@@ -352,6 +353,73 @@ int curl_or_div(bool curl, const R* u, const R* v, const R* area, const int64_t*
 }
 
 
+// fused second-order operators of the header: the two stages of the chain one after the other, plane by plane -- the
+// staggered intermediate Fx / Fy formed with T's halo (center -> left), then the divergence with the intermediate's own halo
+// (left -> center); mode 1: Fx = u * (T[i-1] + T[i]) / 2 (and along Y), mode 0: Fx = (T[i] - T[i-1]) / dxC * dyG,
+// Fy = (T[j] - T[j-1]) / dyC * dxG (met[] = {dxC, dyG, dyC, dxG}, all four or none)
+template <typename R>
+int div2d(int mode, const R* t, const R* u, const R* v, const R* const met[4], const int64_t* const ms[4], const R* area,
+          const int64_t* as, R* out, const int64_t* shape, int ndim, int bc_x, R fill_x, int bc_y, R fill_y) {
+  if (!t || !out || !shape || (mode == 1 && (!u || !v))) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
+  if (area && !as) return fail(XG_ERR_INVALID, "metric without strides");
+  for (int b : {bc_x, bc_y})
+    if (b < XG_BC_PERIODIC || b > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", b);
+  int nmet = 0;
+  for (int k = 0; met && k < 4; ++k) {
+    if (!met[k]) continue;
+    if (!ms[k]) return fail(XG_ERR_INVALID, "metric without strides");
+    ++nmet;
+  }
+  if (nmet != 0 && nmet != 4) return fail(XG_ERR_INVALID, "laplacian: the four metrics dxC, dyC, dyG, dxG, or none");
+  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
+  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
+  auto wrap = [](int64_t q, int64_t n, int bc) { return bc == XG_BC_PERIODIC ? ((q % n + n) % n) : (q < 0 ? 0 : n - 1); };
+  std::vector<R> fx((size_t)(ny * nx)), fy((size_t)(ny * nx));
+  for (int64_t o = 0; o < outer; ++o) {
+    int64_t rem = o, aoff = 0, moff[4] = {0, 0, 0, 0};  // the outer index decomposed for the broadcast strides
+    for (int d = ndim - 3; d >= 0; --d) {
+      const int64_t i = rem % shape[d];
+      rem /= shape[d];
+      if (area) aoff += i * as[d];
+      for (int k = 0; k < 4; ++k)
+        if (nmet) moff[k] += i * ms[k][d];
+    }
+    auto m = [&](int k, int64_t j, int64_t i) { return met[k][moff[k] + j * ms[k][ndim - 2] + i * ms[k][ndim - 1]]; };
+    const R* pt = t + o * ny * nx;
+    for (int64_t j = 0; j < ny; ++j)
+      for (int64_t i = 0; i < nx; ++i) {
+        const R c = pt[j * nx + i];
+        const R l = i > 0 ? pt[j * nx + i - 1] : (bc_x == XG_BC_FILL ? fill_x : pt[j * nx + wrap(-1, nx, bc_x)]);
+        const R b = j > 0 ? pt[(j - 1) * nx + i] : (bc_y == XG_BC_FILL ? fill_y : pt[wrap(-1, ny, bc_y) * nx + i]);
+        const int64_t k = o * ny * nx + j * nx + i;
+        if (mode == 1) {
+          fx[j * nx + i] = u[k] * ((l + c) / R(2));
+          fy[j * nx + i] = v[k] * ((b + c) / R(2));
+        } else if (nmet) {
+          R gx = (c - l) / m(0, j, i), gy = (c - b) / m(2, j, i);
+          fx[j * nx + i] = gx * m(1, j, i);
+          fy[j * nx + i] = gy * m(3, j, i);
+        } else {
+          fx[j * nx + i] = c - l;
+          fy[j * nx + i] = c - b;
+        }
+      }
+    R* po = out + o * ny * nx;
+    for (int64_t j = 0; j < ny; ++j)
+      for (int64_t i = 0; i < nx; ++i) {
+        const R fr = i + 1 < nx ? fx[j * nx + i + 1] : (bc_x == XG_BC_FILL ? fill_x : fx[j * nx + wrap(nx, nx, bc_x)]);
+        const R fu = j + 1 < ny ? fy[(j + 1) * nx + i] : (bc_y == XG_BC_FILL ? fill_y : fy[wrap(ny, ny, bc_y) * nx + i]);
+        const R r = (fr - fx[j * nx + i]) + (fu - fy[j * nx + i]);
+        po[j * nx + i] = area ? r / area[aoff + j * as[ndim - 2] + i * as[ndim - 1]] : r;
+      }
+  }
+  return XG_OK;
+}
+
+
 }  // namespace
 
 extern "C" {
@@ -551,6 +619,17 @@ int xg_event_destroy(void* ev) { free(ev); return XG_OK; }
   int xg_divergence_halo_##SFX(const R*, const R*, const R*, const R*, const R*, const int64_t*, R*, const int64_t*,  \
                                int, int, R, int, R, void*) {                                                          \
     return unsupported("xg_divergence_halo");                                                                         \
+  }                                                                                                                   \
+  int xg_flux_divergence_##SFX(const R* u, const R* v, const R* t, const R* area, const int64_t* as, R* out,            \
+                               const int64_t* shape, int ndim, int bc_x, R fill_x, int bc_y, R fill_y, void*) {         \
+    return div2d<R>(1, t, u, v, nullptr, nullptr, area, as, out, shape, ndim, bc_x, fill_x, bc_y, fill_y);              \
+  }                                                                                                                   \
+  int xg_laplacian_##SFX(const R* a, const R* dxC, const int64_t* dxCs, const R* dyC, const int64_t* dyCs, const R* dyG, \
+                         const int64_t* dyGs, const R* dxG, const int64_t* dxGs, const R* area, const int64_t* as,     \
+                         R* out, const int64_t* shape, int ndim, int bc_x, R fill_x, int bc_y, R fill_y, void*) {       \
+    const R* const met[4] = {dxC, dyG, dyC, dxG};                                                                     \
+    const int64_t* const ms[4] = {dxCs, dyGs, dyCs, dxGs};                                                            \
+    return div2d<R>(0, a, nullptr, nullptr, met, ms, area, as, out, shape, ndim, bc_x, fill_x, bc_y, fill_y);         \
   }                                                                                                                   \
   int xg_stencil2d_##SFX(int, const R*, R*, const int64_t*, int, int, int, int, int, R, int, int, int, R, void*) {    \
     return unsupported("xg_stencil2d");                                                                               \

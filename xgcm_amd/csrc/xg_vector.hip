@@ -154,6 +154,8 @@ __device__ __forceinline__ void load_rows(T (&dst)[SEG], const real* __restrict_
 
 __device__ __forceinline__ real vec_last(dv v) { return v[NV - 1]; }
 __device__ __forceinline__ real vec_last(real v) { return v; }
+__device__ __forceinline__ real vec_first(dv v) { return v[0]; }
+__device__ __forceinline__ real vec_first(real v) { return v; }
 
 template <int V, bool HAS_AREA, bool NTS, int SEG, int ZK = 1>
 __global__ __launch_bounds__(BLOCK) void k_vorticity(
@@ -458,6 +460,185 @@ __global__ __launch_bounds__(BLOCK) void k_pair2d(
         stg<T, NTS>(out_x + base + j * nx + i0, rx);
         stg<T, NTS>(out_y + base + j * nx + i0, ry);
       }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// K7d: the two second-order chains of K7c + K7b in ONE pass, the staggered intermediate kept in registers:
+//   MODE 1 flux divergence: Fx = u * interp(T, X),  Fy = v * interp(T, Y)               (divergence(flux(u, v, T)))
+//   MODE 0 laplacian:       Fx = (delta_x T / dxC) * dyG,  Fy = (delta_y T / dyC) * dxG  (metrics NULL: the differences)
+//   out = ((Fx[i+1] - Fx[i]) + (Fy[j+1] - Fy[j])) [/ area]
+// with K7c's / K7b's own arithmetic helpers in the chain's order (-ffp-contract=off).  The chain pads twice: T below / left
+// of the first row / column (bc of K7c), the INTERMEDIATE above / right of the last one (bc of K7b): periodic -> the
+// intermediate at index 0 (formed from T's own periodic halo), extend -> at n-1, fill -> the fill value itself.
+// Per wave-task (SEG rows): SEG+2 rows of T, SEG rows of u, SEG+1 of v; the T value left of a lane's vector and the Fx
+// right of it come from the neighbouring lanes (DPP); lane 0 / lane 63 / the edge lanes load or form their own.
+// 32 B/cell (flux divergence) and 16 B/cell (laplacian: the five metric planes are 2-D and stay in the L2) instead of
+// 64 / ~100 B/cell for the chains.
+// ------------------------------------------------------------------------------------------
+struct Div2dMet {           // MODE 0 metric planes (all four, or none) at the chain's positions, broadcast strides
+  const real* p[4];         // dxC (Y:c, X:l), dyG (Y:c, X:l), dyC (Y:l, X:c), dxG (Y:l, X:c)
+  AreaIdx ai[4];
+  int64_t sy[4], sx[4];
+};
+
+template <int V, int MODE, bool HAS_AREA, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_div2d(
+    const real* __restrict__ t, const real* __restrict__ u, const real* __restrict__ v, const real* __restrict__ area,
+    real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg,
+    ZBand zb, int bc_x, real fill_x, int bc_y, real fill_y, AreaIdx ai, int64_t a_sy, int64_t a_sx, Div2dMet mt, int ntl) {
+  typedef typename VecT<V>::type T;
+  const u32 pb = (nblk + 7) >> 3;
+  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
+  if (lb >= nblk) return;
+  const u32 w = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
+  const u32 r = fdiv(w, ntile);
+  const u32 tile = w - r * ntile.d;
+  u32 oo, sg;
+  if (zb.on) {  // band-major: the area / metric rows of a band stay in the XCD's L2 for all outer indices
+    if (!zband_map(zb, r, oo, sg)) return;
+  } else {
+    oo = fdiv(r, nseg);
+    if (oo >= nouter) return;
+    sg = r - oo * nseg.d;
+  }
+  const int64_t o = o0 + oo;
+  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
+  if (i0 >= nx) return;
+  const int64_t j0 = (int64_t)sg * SEG;
+  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  const int64_t base = o * ny * nx;
+  const real* pt = t + base;
+  const bool met = MODE == 0 && mt.p[0] != nullptr;
+  // X: T left of the lane (first stage, K7c's rule) and the column whose Fx lies right of it (second stage, K7b's rule)
+  const bool edge_l = (i0 == 0), edge_r = (i0 + V >= nx);
+  const int64_t lidx = edge_l ? ((bc_x == XG_BC_PERIODIC) ? nx - 1 : 0) : i0 - 1;
+  const int64_t ridx = edge_r ? 0 : i0 + V;  // (periodic; extend and fill take no value from there)
+  const bool shl = V > 1 && (ntl & 1);
+  const bool own_l = !shl || (threadIdx.x & 63) == 0 || edge_l;
+  const bool own_r = !shl || (threadIdx.x & 63) == 63 || edge_r;
+  const bool form_r = own_r && !(edge_r && bc_x != XG_BC_PERIODIC);  // lanes that form the Fx right of them themselves
+  // Y: the row above the segment's last one (T, v / metrics there) -- row 0 at a periodic top
+  const int64_t q = j0 + nrow;
+  const bool top_edge = q >= ny;
+  const int64_t qr = top_edge ? 0 : q;
+  const bool top_own = !top_edge || bc_y == XG_BC_PERIODIC;  // else: extend (Fy of the last row) or fill (fill_y)
+
+  T tt[SEG + 1], ttop;  // tt[0]: the row below the segment; tt[1 + s]: row j0 + s (short tails repeat the last row)
+  real tl[SEG], tr[SEG];
+  {
+    const int64_t qb = j0 - 1;
+    bool f = false;
+    const real* src = pt + qb * nx + i0;
+    if (qb < 0) {
+      f = (bc_y == XG_BC_FILL);
+      src = pt + ((bc_y == XG_BC_PERIODIC) ? ny - 1 : 0) * nx + i0;
+    }
+    const T b = *reinterpret_cast<const T*>(src);
+    tt[0] = f ? splat<T>(fill_y) : b;
+  }
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    const int64_t jr = j0 + ((s_ < nrow) ? s_ : nrow - 1);
+    // rows the next segment does not read again stream past the caches (K7c)
+    if (shl && s_ + 1 < SEG) tt[s_ + 1] = __builtin_nontemporal_load(reinterpret_cast<const T*>(pt + jr * nx + i0));
+    else tt[s_ + 1] = *reinterpret_cast<const T*>(pt + jr * nx + i0);
+    tl[s_] = real(0);
+    tr[s_] = real(0);
+    if (own_l) tl[s_] = pt[jr * nx + lidx];
+    if (form_r) tr[s_] = pt[jr * nx + ridx];
+  }
+  ttop = *reinterpret_cast<const T*>(pt + qr * nx + i0);
+  T uu[SEG], vv[SEG], vtop;
+  real urt[SEG];
+  if (MODE == 1) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      const int64_t jr = j0 + ((s_ < nrow) ? s_ : nrow - 1);
+      uu[s_] = *reinterpret_cast<const T*>(u + base + jr * nx + i0);
+      vv[s_] = *reinterpret_cast<const T*>(v + base + jr * nx + i0);
+      urt[s_] = form_r ? u[base + jr * nx + ridx] : real(0);
+    }
+    vtop = *reinterpret_cast<const T*>(v + base + qr * nx + i0);
+  }
+  T ar[SEG];
+  if (HAS_AREA) load_rows<T, SEG>(ar, area, area_outer_off(ai, o) + j0 * a_sy + i0 * a_sx, a_sy, a_sx, nrow, (ntl & 4) != 0);
+  if (shl) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      const real left = from_lane_below(vec_last(tt[s_ + 1]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+      if (!own_l) tl[s_] = left;
+    }
+  }
+  int64_t mb[4] = {0, 0, 0, 0};
+  if (met) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) mb[k] = area_outer_off(mt.ai[k], o);
+  }
+  // the metric rows of the segment up front, in the host-decided form (`ntl` bit 3: every plane an aligned vector): with `ldm`
+  // inside the row loop below the laplacian ran 6 % slower (profiles/EXPERIMENTS.md, K7d)
+  T mr[4][SEG];
+  if (met) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) load_rows<T, SEG>(mr[k], mt.p[k], mb[k] + j0 * mt.sy[k] + i0 * mt.sx[k], mt.sy[k], mt.sx[k], nrow, (ntl & 8) != 0);
+  }
+  // the intermediates, each formed once: Fx at the lane's cells, Fy at its cells and at the row above the segment
+  T fx[SEG], fy[SEG], fytop;
+  real fxr[SEG];
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    const int64_t j = j0 + ((s_ < nrow) ? s_ : nrow - 1);
+    const real left = (edge_l && bc_x == XG_BC_FILL) ? fill_x : tl[s_];
+    const real last = vec_last(tt[s_ + 1]);
+    if (MODE == 1) {
+      fx[s_] = uu[s_] * interp_left_of(tt[s_ + 1], left);
+      fy[s_] = vv[s_] * op2<XG_OP_INTERP>(tt[s_], tt[s_ + 1]);
+      fxr[s_] = urt[s_] * interp_left_of(tr[s_], last);
+    } else {
+      fx[s_] = dvdx_of(tt[s_ + 1], left);
+      fy[s_] = tt[s_ + 1] - tt[s_];
+      fxr[s_] = tr[s_] - last;
+      if (met) {
+        fx[s_] = fx[s_] / mr[0][s_];
+        fx[s_] = fx[s_] * mr[1][s_];
+        fy[s_] = fy[s_] / mr[2][s_];
+        fy[s_] = fy[s_] * mr[3][s_];
+        if (form_r) {
+          fxr[s_] = fxr[s_] / mt.p[0][mb[0] + j * mt.sy[0] + ridx * mt.sx[0]];
+          fxr[s_] = fxr[s_] * mt.p[1][mb[1] + j * mt.sy[1] + ridx * mt.sx[1]];
+        }
+      }
+    }
+  }
+  if (MODE == 1) {
+    fytop = vtop * op2<XG_OP_INTERP>(tt[SEG], ttop);
+  } else {
+    fytop = ttop - tt[SEG];
+    if (met) {
+      fytop = fytop / ldm<T>(mt.p[2], mb[2] + qr * mt.sy[2] + i0 * mt.sx[2], mt.sx[2]);
+      fytop = fytop * ldm<T>(mt.p[3], mb[3] + qr * mt.sy[3] + i0 * mt.sx[3], mt.sx[3]);
+    }
+  }
+  if (shl) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      const real right = from_lane_above(vec_first(fx[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+      if (!own_r) fxr[s_] = right;
+    }
+  }
+  real* po = out + base + j0 * nx + i0;
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    if (s_ < nrow) {
+      real right = fxr[s_];
+      if (edge_r && bc_x == XG_BC_FILL) right = fill_x;
+      else if (edge_r && bc_x == XG_BC_EXTEND) right = vec_last(fx[s_]);
+      T up = (s_ + 1 < nrow) ? fy[s_ + 1] : fytop;
+      if (s_ + 1 >= nrow && !top_own) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : fy[s_];
+      T z = dudx_fwd(fx[s_], right) + (up - fy[s_]);
+      if (HAS_AREA) z = z / ar[s_];
+      stg_s<T, NTS>(po + s_ * nx, z);
     }
   }
 }
@@ -797,6 +978,104 @@ int XG_FN(xg_flux_halo)(const real* u, const real* v, const real* t, const real*
                      void* stream) {
   return pair2d_impl(1, t, u, v, out_x, out_y, shape, ndim, bc_x, fill_x, bc_y, fill_y, nullptr, nullptr, nullptr, nullptr,
                      stream, halo_x, halo_y);
+}
+
+// K7d's launcher: flux divergence (mode 1: u, v, t) or laplacian (mode 0: a = t, the four metrics all or none)
+static int div2d_impl(int mode, const real* t, const real* u, const real* v, const real* const met[4],
+                      const int64_t* const met_strides[4], const real* area, const int64_t* area_strides, real* out,
+                      const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, void* stream) {
+  if (!t || !out || !shape || (mode == 1 && (!u || !v))) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
+  if (bc_x < XG_BC_PERIODIC || bc_x > XG_BC_EXTEND || bc_y < XG_BC_PERIODIC || bc_y > XG_BC_EXTEND)
+    return fail(XG_ERR_INVALID, "flux divergence / laplacian need a periodic, fill or extend boundary on both axes");
+  const int nmet = met ? (met[0] != nullptr) + (met[1] != nullptr) + (met[2] != nullptr) + (met[3] != nullptr) : 0;
+  if (nmet != 0 && nmet != 4) return fail(XG_ERR_INVALID, "laplacian: the four metrics dxC, dyC, dyG, dxG, or none");
+  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
+  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
+  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Y,X) planes");
+  int rc;
+  AreaIdx ai;
+  int64_t a_sy, a_sx;
+  if ((rc = area_index(area, area_strides, shape, ndim, &ai, &a_sy, &a_sx))) return rc;
+  Div2dMet mt;
+  memset(&mt, 0, sizeof(mt));
+  for (int k = 0; k < 4; ++k) {
+    mt.p[k] = nmet ? met[k] : nullptr;
+    if ((rc = area_index(mt.p[k], nmet ? met_strides[k] : nullptr, shape, ndim, &mt.ai[k], &mt.sy[k], &mt.sx[k]))) return rc;
+  }
+  bool al = aligned16(t) && aligned16(out) && nx % NV == 0;
+  if (mode == 1) al = al && aligned16(u) && aligned16(v);
+  const int V = al ? NV : 1;
+  constexpr int SEG = XG_FUSED_SEG;  // (4 rows: the laplacian 12 % slower, the flux divergence 0.7 % faster -- EXPERIMENTS.md)
+  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
+  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
+  const u64 per_outer = ntile * nseg;
+  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the fused second-order kernel");
+  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
+  const u64 outer_per = MAX_ITEMS / per_outer;
+  hipStream_t st = (hipStream_t)stream;
+  const bool nts = tune().nt_store;
+  // bit 0: inner T rows non-temporal + the neighbours by DPP (K7c's scheme), bit 2: the area rows are aligned vectors
+  int vnt = (tune().nt_load ? (tune().vec_nt & 1) : 0) | ((V > 1 && plane_vec_ok(area, ai, a_sy, a_sx)) ? 4 : 0);
+  if (nmet) {  // bit 3: the four metric planes are aligned vectors as well
+    bool mv = V > 1;
+    for (int k = 0; k < 4; ++k) mv = mv && plane_vec_ok(mt.p[k], mt.ai[k], mt.sy[k], mt.sx[k]);
+    vnt |= mv ? 8 : 0;
+  }
+  // planes shared by every outer index (2-D metrics under a (Z, Y, X) field): band-major order, K7b's 16 rows per band for the
+  // area alone, 8 with the five planes of the weighted laplacian (K7c: the more planes, the lower the band)
+  auto shared = [](const real* m, const AreaIdx& a_) {
+    for (int d = 0; m && d < a_.n; ++d)
+      if (a_.stride[d] != 0) return false;
+    return true;
+  };
+  bool all_shared = (area || nmet) && shared(area, ai);
+  for (int k = 0; k < 4; ++k) all_shared = all_shared && shared(mt.p[k], mt.ai[k]);
+  const u32 zbr = (u32)(tune().vec_zb_rows > 1 ? tune().vec_zb_rows : 16);
+  const u32 ZB_SEGS = (u32)(((nmet ? (zbr + 1) / 2 : zbr) + SEG - 1) / SEG);
+  ZBand zb = make_zband(false, 0, 0, 1);
+  u64 outer_step = outer_per;
+  if (all_shared && tune().zband && outer >= 2) {
+    const u64 padded = ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile;
+    if (padded <= MAX_ITEMS) {
+      zb = make_zband(true, (u64)outer, nseg, ZB_SEGS);
+      if (zb.on) outer_step = (u64)outer;
+    }
+  }
+  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_step) {
+    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_step) ? outer - o0 : (int64_t)outer_step);
+    const u64 waves = zb.on ? ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile : (u64)nouter * per_outer;
+    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
+    if ((rc = check_grid((u64)nblk + 8))) return rc;
+    const u32 grid = ((nblk + 7) / 8) * 8;
+#define XG_GO(V_, M_, A_, NTS) do { hipLaunchKernelGGL((k_div2d<V_, M_, A_, NTS, SEG>), dim3(grid), dim3(BLOCK), 0, st, t, u, v, area, out, o0, nouter, nblk, ny, nx, fnt, fns, zb, bc_x, fill_x, bc_y, fill_y, ai, a_sy, a_sx, mt, vnt); } while (0)
+#define XG_A(V_, M_) do { if (area) { if (nts) XG_GO(V_, M_, true, true); else XG_GO(V_, M_, true, false); } \
+                          else { if (nts) XG_GO(V_, M_, false, true); else XG_GO(V_, M_, false, false); } } while (0)
+    if (V > 1) { if (mode) XG_A(NV, 1); else XG_A(NV, 0); }
+    else { if (mode) XG_A(1, 1); else XG_A(1, 0); }
+#undef XG_A
+#undef XG_GO
+  }
+  XG_LAUNCH_CHECK();
+  return XG_OK;
+}
+
+int XG_FN(xg_flux_divergence)(const real* u, const real* v, const real* t, const real* area, const int64_t* area_strides,
+                              real* out, const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y,
+                              void* stream) {
+  return div2d_impl(1, t, u, v, nullptr, nullptr, area, area_strides, out, shape, ndim, bc_x, fill_x, bc_y, fill_y, stream);
+}
+
+int XG_FN(xg_laplacian)(const real* a, const real* dxC, const int64_t* dxC_strides, const real* dyC,
+                        const int64_t* dyC_strides, const real* dyG, const int64_t* dyG_strides, const real* dxG,
+                        const int64_t* dxG_strides, const real* area, const int64_t* area_strides, real* out,
+                        const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, void* stream) {
+  const real* const met[4] = {dxC, dyG, dyC, dxG};  // K7d's order: the Fx pair, then the Fy pair
+  const int64_t* const ms[4] = {dxC_strides, dyG_strides, dyC_strides, dxG_strides};
+  return div2d_impl(0, a, nullptr, nullptr, met, ms, area, area_strides, out, shape, ndim, bc_x, fill_x, bc_y, fill_y,
+                    stream);
 }
 
 #endif  // !XG_INT

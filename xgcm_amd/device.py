@@ -1192,6 +1192,52 @@ def flux(u, v, t, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0
     return out_x, out_y
 
 
+def flux_divergence(u, v, t, area, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
+    """Fused divergence(flux(u, v, t)) in one pass (xg_flux_divergence_f64): the flux u * (t[x-1] + t) / 2,
+    v * (t[y-1] + t) / 2 never leaves the registers.  `bc_x` / `bc_y` pad the tracer below / left of the first cell
+    and the flux above / right of the last one, as the two operators of the chain do; `area` None = no division."""
+    lib = _MEM.lib()
+    dt, sfx = _common(u, v, t, area)
+    u, v, t = asdevice(u, dt), asdevice(v, dt), asdevice(t, dt)
+    if u.shape != t.shape or v.shape != t.shape:
+        raise ValueError("flux_divergence: u, v and t must have the same shape")
+    shape = list(t.shape)
+    area = _prep_metric(area, dt)
+    out = _empty(shape, dtype=dt, device=t.device)
+    if out.numel() == 0:
+        return out
+    _check(
+        getattr(lib, "xg_flux_divergence_" + sfx)(u.data_ptr(), v.data_ptr(), t.data_ptr(), _ptr(area),
+                                                  _hip.i64(_bstrides(area, shape, "area")), out.data_ptr(),
+                                                  _hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x),
+                                                  _hip.BC[bc_y], float(fill_y), _stream())
+    )
+    return out
+
+
+def laplacian(a, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, dxC=None, dyC=None, dyG=None,
+              dxG=None, area=None) -> torch.Tensor:
+    """Fused finite-volume del2 in one pass (xg_laplacian_f64): Fx = (a - a[x-1]) / dxC * dyG, Fy = (a - a[y-1]) / dyC
+    * dxG (the four metrics None: plain differences), then (Fx[x+1] - Fx + Fy[y+1] - Fy) / area -- gradient, the two
+    face-length products and divergence bit for bit, with the two boundary rules of that chain (see flux_divergence)."""
+    lib = _MEM.lib()
+    dt, sfx = _common(a, dxC, dyC, dyG, dxG, area)
+    a = asdevice(a, dt)
+    shape = list(a.shape)
+    dxC, dyC, dyG, dxG, area = (_prep_metric(m, dt) for m in (dxC, dyC, dyG, dxG, area))
+    out = _empty(shape, dtype=dt, device=a.device)
+    if out.numel() == 0:
+        return out
+    args = []
+    for m, what in ((dxC, "dxC"), (dyC, "dyC"), (dyG, "dyG"), (dxG, "dxG"), (area, "area")):
+        args += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
+    _check(
+        getattr(lib, "xg_laplacian_" + sfx)(a.data_ptr(), *args, out.data_ptr(), _hip.i64(shape), len(shape),
+                                            _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y), _stream())
+    )
+    return out
+
+
 def stencil2d_supported(x, padx, pady) -> bool:
     """Can xg_stencil2d_f64 serve this call (else run the two axes one after the other)?"""
     shape = tuple(x.shape)  # numpy (host) or torch (HBM) data

@@ -46,7 +46,8 @@ from .grid_ufunc import (
     apply_as_grid_ufunc,
 )
 from . import lazy as _lazy
-from .labeled import CHUNKED_INPUT_MESSAGE, DataArray, Dataset, _aligned_view, _is_tensor, from_xarray, is_xarray, to_xarray
+from .labeled import (CHUNKED_INPUT_MESSAGE, DataArray, Dataset, _aligned_view, _binary_coords, _is_chunked, _is_tensor,
+                      from_xarray, is_xarray, to_xarray)
 from .metrics import iterate_axis_combinations
 from .padding import FoldSpec, InteriorOf, halo_cells, no_boundary_error, pad
 
@@ -1224,6 +1225,132 @@ class Grid:
         ry = _reattach_coords([ry], self, None, {ya.coords["left"]}, [v, t])[0]
         return (to_xarray(rx), to_xarray(ry)) if was_xr else (rx, ry)
 
+    # ---- fused second-order operators: the staggered intermediate of a two-step chain never reaches memory ----------
+    def _second_order_plan(self, fields, x_axis, y_axis, padding, fill_value, metrics=()):
+        """(bc_x, bc_y, fill_x, fill_y) when the one-pass kernel may serve a chain over `fields` (all at the same shape and
+        float dtype, `metrics` in that dtype too, ordinary boundaries on both axes), else None: the chain itself runs"""
+        if any(gridops.complex_topology(self, ax) for ax in (x_axis, y_axis)):
+            return None  # the intermediate's own halo would have to be gathered across faces / the fold
+        dtype = _dt.np_dtype(fields[0].data)
+        if dtype not in (_dt.FLOAT32, _dt.FLOAT64) or any(_is_chunked(f.data) for f in fields):
+            return None
+        if any(tuple(f.shape) != tuple(fields[0].shape) or _dt.np_dtype(f.data) != dtype for f in fields):
+            return None
+        if any(_dt.np_dtype(m.data) != dtype for m in metrics):
+            return None
+        bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
+        fv = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
+        if bc[x_axis] is None or bc[y_axis] is None:
+            return None  # (the chain raises the missing-boundary error)
+        return bc[x_axis], bc[y_axis], float(fv[x_axis] or 0.0), float(fv[y_axis] or 0.0)
+
+    def flux_divergence(self, u, v, tracer, x_axis: str = "X", y_axis: str = "Y", padding=None, fill_value=None,
+                        metric_weighted: bool = True):
+        """Flux-form advection tendency `divergence(flux(u, v, tracer))` in ONE pass: u, v and the tracer are read once,
+        the result written once (32 B/cell in float64 instead of the chain's 64); the flux stays in registers.
+
+        u at (Y:center, X:left), v at (Y:left, X:center), the tracer and the result at the centre.  Bit-identical to
+        `grid.divergence(*grid.flux(u, v, tracer, x_axis, y_axis, padding=padding, fill_value=fill_value), x_axis, y_axis,
+        padding=padding, fill_value=fill_value, metric_weighted=metric_weighted)`, which pads twice: the tracer below /
+        left of the first cell, then the FLUX above / right of the last one -- periodic: the flux at index 0, extend: at
+        n-1, fill: `fill_value` itself.  That chain itself runs (the same calls in the same order) for integer, float16 or
+        mixed dtypes (their promotions are the chain's), for (Y, X) not last or fields of different shapes, for chunked
+        host arrays, and on grids with face connections or a fold along either axis."""
+        args = (u, v, tracer)
+        (u, xr1), (v, xr2), (t, xr3) = self._wrap_in(u), self._wrap_in(v), self._wrap_in(tracer)
+        was_xr = xr1 or xr2 or xr3
+        xa, ya = self.axes[x_axis], self.axes[y_axis]
+        tx_pos, tx_dim = xa._get_position_name(t)
+        ty_pos, ty_dim = ya._get_position_name(t)
+        ux_pos, ux_dim = xa._get_position_name(u)
+        uy_pos, uy_dim = ya._get_position_name(u)
+        vx_pos, vx_dim = xa._get_position_name(v)
+        vy_pos, vy_dim = ya._get_position_name(v)
+        if ((tx_pos, ty_pos, ux_pos, uy_pos, vx_pos, vy_pos) != ("center", "center", "left", "center", "center", "left")
+                or "left" not in xa.coords or "left" not in ya.coords):
+            raise NotImplementedError("fused flux divergence needs the tracer at (Y:center, X:center), u at (Y:center, "
+                                      "X:left) and v at (Y:left, X:center)")
+        out_x, out_y = xa.coords["center"], ya.coords["center"]
+        dims_x = t.dims[:-2] + (ty_dim, xa.coords["left"])
+        dims_y = t.dims[:-2] + (ya.coords["left"], tx_dim)
+        out_dims = t.dims[:-2] + (out_y, out_x)
+        plan = None
+        area = None
+        if t.dims[-2:] == (ty_dim, tx_dim) and u.dims == dims_x and v.dims == dims_y:
+            if metric_weighted:
+                area = self._resident(self.get_metric(_DimsOnly(out_dims), (x_axis, y_axis)), t.data)
+            plan = self._second_order_plan([u, v, t], x_axis, y_axis, padding, fill_value, [area] if area is not None else [])
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            fx, fy = self.flux(*args, x_axis, y_axis, **kw)
+            return self.divergence(fx, fy, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+        bcx, bcy, fvx, fvy = plan
+        host = not (_is_tensor(u.data) or _is_tensor(v.data) or _is_tensor(t.data))
+        out = _dev.flux_divergence(u.data, v.data, t.data, None if area is None else _aligned_view(area, out_dims),
+                                   bcx, bcy, fvx, fvy)
+        # coords as the chain's: the flux's (from u / v and the tracer), then the divergence's from the two fluxes
+        rx = _reattach_coords([DataArray(_placeholder(u.shape), dims_x)], self, None, {xa.coords["left"]}, [u, t])[0]
+        ry = _reattach_coords([DataArray(_placeholder(v.shape), dims_y)], self, None, {ya.coords["left"]}, [v, t])[0]
+        res = DataArray(_dev.tohost(out) if host else out, out_dims)
+        res = _reattach_coords([res], self, None, {out_x, out_y}, [rx, ry])[0]
+        return to_xarray(res) if was_xr else res
+
+    def laplacian(self, a, x_axis: str = "X", y_axis: str = "Y", padding=None, fill_value=None,
+                  metric_weighted: bool = True):
+        """Finite-volume Laplacian `(delta_x(dyG * delta_x(a) / dxC) + delta_y(dxG * delta_y(a) / dyC)) / rA` of a
+        cell-centre field in ONE pass (16 B/cell in float64: the field read once, the result written once; the metric
+        planes are read through the cache).  Bit-identical to the chain
+
+            gx, gy = grid.gradient(a, x_axis, y_axis, padding=padding, fill_value=fill_value, metric_weighted=metric_weighted)
+            if metric_weighted: gx = gx * grid.get_metric(gx, (y_axis,)); gy = gy * grid.get_metric(gy, (x_axis,))
+            grid.divergence(gx, gy, x_axis, y_axis, padding=padding, fill_value=fill_value, metric_weighted=metric_weighted)
+
+        which pads twice: the field below / left of the first cell, then the fluxes gx, gy above / right of the last one
+        (periodic: at index 0, extend: at n-1, fill: `fill_value` itself).  That chain itself runs for integer, float16
+        or mixed dtypes (the field's and the metrics'), for (Y, X) not last, metrics with dims the field lacks, chunked
+        host arrays, and on grids with face connections or a fold along either axis."""
+        arg = a
+        a, was_xr = self._wrap_in(a)
+        xa, ya = self.axes[x_axis], self.axes[y_axis]
+        x_pos, x_dim = xa._get_position_name(a)
+        y_pos, y_dim = ya._get_position_name(a)
+        if (x_pos, y_pos) != ("center", "center") or "left" not in xa.coords or "left" not in ya.coords:
+            raise NotImplementedError("fused laplacian needs a field at (Y:center, X:center) and left points on both axes")
+        out_dims = a.dims
+        dims_x = a.dims[:-1] + (xa.coords["left"],)
+        dims_y = a.dims[:-2] + (ya.coords["left"], x_dim)
+        plan = None
+        mets = {}
+        if a.dims[-2:] == (y_dim, x_dim):
+            if metric_weighted:
+                like = _DimsOnly(dims_x, a.name), _DimsOnly(dims_y, a.name)
+                for key, where, axes in (("dxC", 0, (x_axis,)), ("dyC", 1, (y_axis,)), ("dyG", 0, (y_axis,)),
+                                         ("dxG", 1, (x_axis,)), ("area", None, (x_axis, y_axis))):
+                    m = self.get_metric(_DimsOnly(out_dims) if where is None else like[where], axes)
+                    mets[key] = (self._resident(m, a.data), out_dims if where is None else like[where].dims)
+            if all(set(m.dims) <= set(dims) for m, dims in mets.values()):
+                plan = self._second_order_plan([a], x_axis, y_axis, padding, fill_value, [m for m, _ in mets.values()])
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            gx, gy = self.gradient(arg, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+            if metric_weighted:
+                gx = gx * self.get_metric(gx, (y_axis,))
+                gy = gy * self.get_metric(gy, (x_axis,))
+            return self.divergence(gx, gy, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+        bcx, bcy, fvx, fvy = plan
+        host = not _is_tensor(a.data)
+        views = {k: _aligned_view(m, dims) for k, (m, dims) in mets.items()}
+        out = _dev.laplacian(a.data, bcx, bcy, fvx, fvy, **views)
+        # coords as the chain's: the gradient's (from the field), times the face lengths, then the divergence's
+        gx = _reattach_coords([DataArray(_placeholder(a.shape), dims_x, name=a.name)], self, None, {xa.coords["left"]}, [a])[0]
+        gy = _reattach_coords([DataArray(_placeholder(a.shape), dims_y, name=a.name)], self, None, {ya.coords["left"]}, [a])[0]
+        if metric_weighted:
+            gx = gx._replace(coords=_binary_coords(gx, mets["dyG"][0], dims_x))
+            gy = gy._replace(coords=_binary_coords(gy, mets["dxG"][0], dims_y))
+        res = DataArray(_dev.tohost(out) if host else out, out_dims)
+        res = _reattach_coords([res], self, None, {xa.coords["center"], ya.coords["center"]}, [gx, gy])[0]
+        return to_xarray(res) if was_xr else res
+
     def transform(self, da, axis, target, **kwargs):
         """Convert `da` to new 1-D coordinates along `axis` (linear / log / conservative; reference
         grid.py:1687-1777 -> transform.py:284-514), one HIP kernel launch per call."""
@@ -1231,6 +1358,11 @@ class Grid:
 
         return _transform(self, axis, da, target, **kwargs)
 
+
+# ----------------------------------------------------------------------------------------------
+def _placeholder(shape):
+    """read-only stand-in of an intermediate the fused operators never form: carries a shape (for its coords), no memory"""
+    return np.broadcast_to(np.zeros((), dtype=np.int8), tuple(int(n) for n in shape))
 
 # ----------------------------------------------------------------------------------------------
 def _shifted_dims(grid: Grid, array, ax_name: str, to_pos: str, from_pos: Optional[str] = None) -> Tuple[str, ...]:

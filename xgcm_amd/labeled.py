@@ -293,15 +293,7 @@ class DataArray:
             for d in dims:
                 if d in self.dims and d in other.dims and self.sizes[d] != other.sizes[d]:
                     raise ValueError(f"cannot broadcast: dimension {d!r} has sizes {self.sizes[d]} and {other.sizes[d]}")
-            coords = OrderedDict(self.coords)
-            for k, v in other.coords.items():
-                mine = coords.get(k)
-                if mine is None:
-                    coords[k] = v
-                elif k not in dims and not _same_coord(mine, v):
-                    # xarray: "other [than index] coordinates are not aligned, and if their values conflict, they will be
-                    # dropped" (`arr[0] - arr[1]` loses its scalar coordinate)
-                    del coords[k]
+            coords = _binary_coords(self, other, dims)
         elif (isinstance(other, np.ndarray) or _is_tensor(other)) and other.ndim <= self.ndim:
             # an unlabelled array: numpy's positional broadcasting against this array's shape, as in xarray
             shape = (1,) * (self.ndim - other.ndim) + tuple(int(n) for n in other.shape)
@@ -382,6 +374,20 @@ class DataArray:
         if not isinstance(key, tuple):
             key = (key,)
         return self.isel({d: k for d, k in zip(self.dims, key)})
+
+
+def _binary_coords(a: "DataArray", b: "DataArray", dims) -> "OrderedDict":
+    """coords of `a OP b` for two DataArrays whose result has `dims`: a's, then b's new ones"""
+    coords = OrderedDict(a.coords)
+    for k, v in b.coords.items():
+        mine = coords.get(k)
+        if mine is None:
+            coords[k] = v
+        elif k not in dims and not _same_coord(mine, v):
+            # xarray: "other [than index] coordinates are not aligned, and if their values conflict, they will be
+            # dropped" (`arr[0] - arr[1]` loses its scalar coordinate)
+            del coords[k]
+    return coords
 
 
 def _same_coord(a, b) -> bool:
