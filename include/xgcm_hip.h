@@ -40,6 +40,7 @@
  *                      (one fused pass instead of three apply_ufunc passes, grid.py:798-800 TODO)
  *   xg_flux_divergence_f64 / xg_laplacian_f64  divergence(flux(u, v, T)) (the "Advection" tendency of
  *                      docs/ufunc_examples.md) and the finite-volume del2, two-step chains in one pass
+ *   xg_flux_divergence3d_f64  the same with the vertical flux w * interp(T, Z), divided by the cell volume
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -355,6 +356,21 @@ int xg_laplacian_f64(const double* a, const double* dxC, const int64_t* dxC_stri
                      const double* dxG, const int64_t* dxG_strides, const double* area,
                      const int64_t* area_strides, double* out, const int64_t* shape, int ndim, int bc_x,
                      double fill_x, int bc_y, double fill_y, void* stream);
+/* The 3-D tracer flux divergence (MITgcm's advection term (di Fx + dj Fy + dk Fr) / (rA drF hFacC)), one pass over arrays of
+ * identical `shape` (.., Z, Y, X): u at (Z:c, Y:c, X:left), v at (Z:c, Y:left, X:c), w at (Z:left, Y:c, X:c), t and out
+ * at the centre:
+ *   Fx, Fy  per level as xg_flux_divergence_f64 (both of its boundary stages on X and Y)
+ *   Fz[k] = w[k] * (t[k-1] + t[k]) / 2
+ *   out   = (((Fx[i+1] - Fx[i]) + (Fy[j+1] - Fy[j])) + (Fz[k+1] - Fz[k])) / vol      (vol NULL: no division)
+ * the divergence in INDEX space (k grows with the index; a model whose Z index grows downward with w positive upward
+ * passes -w).  Z pads twice as well: t above level 0 (periodic: t[nz-1], extend: t[0], fill: fill_z), then Fz below
+ * level nz-1 (periodic: Fz[0], extend: Fz[nz-1], fill: fill_z itself).  The volume is `vol`, or the product vol * vol2
+ * (in that order) formed per cell when `vol2` is given; both use broadcast strides (0 = broadcast) against `shape`.
+ * XG_BC_HALO is not accepted. */
+int xg_flux_divergence3d_f64(const double* u, const double* v, const double* w, const double* t, const double* vol,
+                             const int64_t* vol_strides, const double* vol2, const int64_t* vol2_strides, double* out,
+                             const int64_t* shape, int ndim, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
+                             double fill_z, void* stream);
 
 /* ---- the same two-point operator along the last TWO axes in one pass -------------------- */
 /* out = OP_second(pad(OP_first(pad(in)))) for (.., Y, X) arrays, order 0: X then Y, 1: Y then X;
@@ -458,6 +474,10 @@ int xg_laplacian_f32(const float* a, const float* dxC, const int64_t* dxC_stride
                      const float* dxG, const int64_t* dxG_strides, const float* area,
                      const int64_t* area_strides, float* out, const int64_t* shape, int ndim, int bc_x,
                      float fill_x, int bc_y, float fill_y, void* stream);
+int xg_flux_divergence3d_f32(const float* u, const float* v, const float* w, const float* t, const float* vol,
+                             const int64_t* vol_strides, const float* vol2, const int64_t* vol2_strides, float* out,
+                             const int64_t* shape, int ndim, int bc_x, float fill_x, int bc_y, float fill_y, int bc_z,
+                             float fill_z, void* stream);
 int xg_stencil2d_f32(int op, const float* in, float* out, const int64_t* shape, int ndim, int order,
                      int padx_lo, int padx_hi, int bc_x, float fill_x, int pady_lo, int pady_hi,
                      int bc_y, float fill_y, void* stream);

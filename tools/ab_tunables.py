@@ -98,6 +98,7 @@ def main():
         "flux": (lambda: D.flux(U, V, T, "periodic", "extend"), 40),
         "advT": (lambda: D.flux_divergence(U, V, T, dx, "periodic", "extend"), 32 + 8 / nz),  # divergence(flux(u, v, T)) in one pass
         "lapT": (lambda: D.laplacian(T, "periodic", "extend", 0.0, 0.0, dx, dx2, dx2, dx, dx), 16 + 16 / nz),  # del2: its five metrics from two planes
+        "adv3": (lambda: D.flux_divergence_3d(U, V, W, T, dx, dz, "periodic", "extend", "extend"), 40 + 8 / nz),  # 3-D flux divergence / (rA * drF)
     }
     cases = a.cases.split(",")
     dx2_off = None
@@ -147,8 +148,9 @@ def main():
             R = int(c[5:])
             TR = D.synthetic((R, nz, ny, nx), 4)
             CASES[c] = ((lambda TR=TR: D.cumsum1d(TR, 1, 0, 1, 1, 0, "fill")), 16 * R)
-    if any(c in cases for c in ("vort", "divg", "flux", "advT")):
+    if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3")):
         U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
+    W = D.synthetic((nz, ny, nx), 54) if "adv3" in cases else None
     variants = []
     for spec in a.variants.split(";"):
         kv = dict((k.strip(), int(v)) for k, v in (item.split("=") for item in spec.split(",") if item.strip()))
@@ -163,7 +165,7 @@ def main():
     for rnd in range(a.rounds):
         if a.realloc and rnd > 0:  # the big full-size operands on fresh allocations (small metrics and transform tables stay)
             _shift = None
-            T = U = V = None
+            T = U = V = W = None
             T2k, T3k = T2 is not None, T3 is not None
             T2 = T3 = None
             torch.cuda.synchronize()
@@ -176,8 +178,10 @@ def main():
                 T2 = D.synthetic((nz, ny, nx), 9, 0, 1000.0, 1000.0)
             if T3k:
                 T3 = D.synthetic((nz, ny, nx), 10, 0, 1000.0, 1000.0)
-            if any(c in cases for c in ("vort", "divg", "flux", "advT")):
+            if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3")):
                 U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
+            if "adv3" in cases:
+                W = D.synthetic((nz, ny, nx), 54)
             for c in cases:
                 CASES[c][0]()
             torch.cuda.synchronize()

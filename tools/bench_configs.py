@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian against their chains), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d against their chains), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -616,6 +616,29 @@ def main():
         rec(5, "laplacian as its chain (gradient, 2 products, divergence), fused-equivalent bytes", timeit(lap_chain, a.reps), c5, 16 + 40 / nz5)
         okl = bool(torch.equal(g2.laplacian(T5).data, lap_chain().data))
         print(json.dumps({"config": 5, "check": "fused laplacian == chain bit for bit at full size", "ok": okl}), flush=True)
+        # the 3-D tracer flux divergence (u, v, w, T) / (rA * drF) in one pass against its seven-launch chain
+        ds3 = Dataset({"rA": g2._ds["rA"], "drF": grid._ds["drF"]},
+                      {"XC": ("XC", np.arange(n5) + 0.5), "XG": ("XG", np.arange(n5) * 1.0), "YC": ("YC", np.arange(n5) + 0.5),
+                       "YG": ("YG", np.arange(n5) * 1.0), "Z": ("Z", np.arange(nz5) + 0.5), "Zl": ("Zl", np.arange(nz5) * 1.0)})
+        g3 = Grid(ds3, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                               "Z": {"center": "Z", "left": "Zl"}},
+                  padding={"X": "periodic", "Y": "extend", "Z": "fill"}, autoparse_metadata=False,
+                  metrics={("X", "Y"): ["rA"], ("Z",): ["drF"]})
+        U3 = U._replace(dims=("Z", "YC", "XG"))
+        V3 = V._replace(dims=("Z", "YG", "XC"))
+        W3 = DataArray(D.synthetic((nz5, n5, n5), 54), ("Zl", "YC", "XC"))
+
+        def adv3_chain():
+            fx, fy = g3.flux(U3, V3, T5)
+            fz = W3 * g3.interp(T5, "Z")
+            out = g3.divergence(fx, fy, metric_weighted=False) + g3.diff(fz, "Z")
+            return out / g3.get_metric(out, ("X", "Y", "Z"))
+
+        rec(5, "flux_divergence_3d fused (u, v, w, T) / (rA * drF), periodic/extend/fill: 4 reads + 1 write", timeit(lambda: g3.flux_divergence_3d(U3, V3, W3, T5), a.reps), c5, 40)
+        rec(5, "flux_divergence_3d as its chain (7 launches), fused-equivalent bytes", timeit(adv3_chain, max(3, a.reps // 2)), c5, 40)
+        ok3 = bool(torch.equal(g3.flux_divergence_3d(U3, V3, W3, T5).data, adv3_chain().data))
+        print(json.dumps({"config": 5, "check": "fused flux_divergence_3d == chain bit for bit at full size", "ok": ok3}), flush=True)
+        del W3
     ranks.close()
 
 

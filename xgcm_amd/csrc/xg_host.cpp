@@ -9,7 +9,7 @@
 // straightforward loops (one output cell at a time, index arithmetic in the open), written against the header's
 // semantics, not against the kernels or the oracle.  It serves the 1-D operators of SURVEY.md section 8(a):
 // stencil (+ pre-gathered halos), cumsum, reduce, pad, the broadcasting binary op and the synthetic generator, plus the
-// fused divergence / vorticity / flux divergence / laplacian; the other fused / topology / transform entry points exist
+// fused divergence / vorticity / flux divergence (2-D and 3-D) / laplacian; the other fused / topology / transform entry points exist
 // and return XG_ERR_UNSUPPORTED.
 //
 // Build: g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off  (no FMA contraction: same bit contract as the kernels)
@@ -419,6 +419,56 @@ int div2d(int mode, const R* t, const R* u, const R* v, const R* const met[4], c
   return XG_OK;
 }
 
+// the 3-D flux divergence of the header: the horizontal part per level as div2d (mode 1, no area), then the vertical flux
+// Fz[k] = w[k] * (T[k-1] + T[k]) / 2 with T's halo above level 0, its difference Fz[k+1] - Fz[k] with Fz's own halo below
+// the last level, added to it, then the division by vol (* vol2)
+template <typename R>
+int div3d(const R* u, const R* v, const R* w, const R* t, const R* vol, const int64_t* vs, const R* vol2,
+          const int64_t* vs2, R* out, const int64_t* shape, int ndim, int bc_x, R fill_x, int bc_y, R fill_y, int bc_z,
+          R fill_z) {
+  if (!u || !v || !w || !t || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  if (bc_z < XG_BC_PERIODIC || bc_z > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", bc_z);
+  if (vol2 && !vol) return fail(XG_ERR_INVALID, "a second volume factor without the first");
+  if ((vol && !vs) || (vol2 && !vs2)) return fail(XG_ERR_INVALID, "metric without strides");
+  int rc = div2d<R>(1, t, u, v, nullptr, nullptr, nullptr, nullptr, out, shape, ndim, bc_x, fill_x, bc_y, fill_y);
+  if (rc) return rc;
+  const int64_t nz = shape[ndim - 3], plane = shape[ndim - 2] * shape[ndim - 1];
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 3; ++d) outer *= shape[d];
+  if (outer == 0 || nz == 0 || plane == 0) return XG_OK;
+  std::vector<R> fz((size_t)(nz * plane));
+  for (int64_t o = 0; o < outer; ++o) {
+    const int64_t col = o * nz * plane;
+    for (int64_t k = 0; k < nz; ++k)
+      for (int64_t p = 0; p < plane; ++p) {
+        const R c = t[col + k * plane + p];
+        const R a = k > 0 ? t[col + (k - 1) * plane + p]
+                          : (bc_z == XG_BC_FILL ? fill_z : t[col + (bc_z == XG_BC_PERIODIC ? nz - 1 : 0) * plane + p]);
+        fz[k * plane + p] = w[col + k * plane + p] * ((a + c) / R(2));
+      }
+    for (int64_t k = 0; k < nz; ++k)
+      for (int64_t p = 0; p < plane; ++p) {
+        const R below = k + 1 < nz ? fz[(k + 1) * plane + p]
+                                   : (bc_z == XG_BC_FILL ? fill_z : fz[(bc_z == XG_BC_PERIODIC ? 0 : nz - 1) * plane + p]);
+        R& r = out[col + k * plane + p];
+        r = r + (below - fz[k * plane + p]);
+        if (vol) {
+          // the cell's multi-index, for the broadcast strides of the volume factor(s)
+          int64_t rem = col + k * plane + p, off = 0, off2 = 0;
+          for (int d = ndim - 1; d >= 0; --d) {
+            const int64_t i = rem % shape[d];
+            rem /= shape[d];
+            off += i * vs[d];
+            if (vol2) off2 += i * vs2[d];
+          }
+          r = r / (vol2 ? vol[off] * vol2[off2] : vol[off]);
+        }
+      }
+  }
+  return XG_OK;
+}
+
 
 }  // namespace
 
@@ -623,6 +673,11 @@ int xg_event_destroy(void* ev) { free(ev); return XG_OK; }
   int xg_flux_divergence_##SFX(const R* u, const R* v, const R* t, const R* area, const int64_t* as, R* out,            \
                                const int64_t* shape, int ndim, int bc_x, R fill_x, int bc_y, R fill_y, void*) {         \
     return div2d<R>(1, t, u, v, nullptr, nullptr, area, as, out, shape, ndim, bc_x, fill_x, bc_y, fill_y);              \
+  }                                                                                                                   \
+  int xg_flux_divergence3d_##SFX(const R* u, const R* v, const R* w, const R* t, const R* vol, const int64_t* vs,       \
+                                 const R* vol2, const int64_t* vs2, R* out, const int64_t* shape, int ndim, int bc_x,  \
+                                 R fill_x, int bc_y, R fill_y, int bc_z, R fill_z, void*) {                            \
+    return div3d<R>(u, v, w, t, vol, vs, vol2, vs2, out, shape, ndim, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z);     \
   }                                                                                                                   \
   int xg_laplacian_##SFX(const R* a, const R* dxC, const int64_t* dxCs, const R* dyC, const int64_t* dyCs, const R* dyG, \
                          const int64_t* dyGs, const R* dxG, const int64_t* dxGs, const R* area, const int64_t* as,     \

@@ -643,6 +643,178 @@ __global__ __launch_bounds__(BLOCK) void k_div2d(
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// K7e: the 3-D tracer flux divergence (MITgcm's advection term) in ONE pass over (lead, Z, Y, X):
+//   out = ((Fx[i+1] - Fx[i]) + (Fy[j+1] - Fy[j])) + (Fz[k+1] - Fz[k])  [/ vol]
+// Fx, Fy per level exactly as K7d MODE 1 (same helpers, same order, same X / Y boundaries); Fz[k] = w[k] * interp(T[k-1], T[k]).
+// Z pads twice, as the chain does: T above level 0 (periodic: T[nz-1], extend: T[0], fill: fill_z), then Fz below level nz-1
+// (periodic: Fz[0], extend: Fz[nz-1], fill: fill_z itself).  Each wave owns one (lead, Y segment, X tile) column and marches
+// k = 0 .. nz-1: the rows of T[k+1] and w[k+1] are read at level k (they form Fz[k+1]) and carry over in registers with
+// Fz[k+1] to level k+1, so u, v, w and T are each read once and out written once: 40 B/cell in float64.  The volume is one
+// broadcast array (`va`) or the product va * vb formed in registers in get_metric's order (area * thickness); rows that do
+// not vary along Z are loaded once per wave.
+// ------------------------------------------------------------------------------------------
+struct VolIdx {  // one volume factor: the lead dims as in AreaIdx, then (Z, Y, X) element strides (0 = broadcast)
+  const real* p;
+  AreaIdx ai;
+  int64_t sz, sy, sx;
+};
+
+template <int V, int NVOL, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_div3d(
+    const real* __restrict__ t, const real* __restrict__ u, const real* __restrict__ v, const real* __restrict__ w,
+    real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile,
+    FastDiv nseg, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx va, VolIdx vb, int ntl) {
+  typedef typename VecT<V>::type T;
+  const u32 pb = (nblk + 7) >> 3;
+  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
+  if (lb >= nblk) return;
+  const u32 wv = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
+  const u32 r = fdiv(wv, ntile);
+  const u32 tile = wv - r * ntile.d;
+  const u32 oo = fdiv(r, nseg);
+  if (oo >= nouter) return;
+  const u32 sg = r - oo * nseg.d;
+  const int64_t o = o0 + oo;
+  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
+  if (i0 >= nx) return;
+  const int64_t j0 = (int64_t)sg * SEG;
+  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  // X and Y exactly as K7d: T left of the lane, the column whose Fx lies right of it, the rows below / above the segment
+  const bool edge_l = (i0 == 0), edge_r = (i0 + V >= nx);
+  const int64_t lidx = edge_l ? ((bc_x == XG_BC_PERIODIC) ? nx - 1 : 0) : i0 - 1;
+  const int64_t ridx = edge_r ? 0 : i0 + V;
+  const bool shl = V > 1 && (ntl & 1);
+  const bool own_l = !shl || (threadIdx.x & 63) == 0 || edge_l;
+  const bool own_r = !shl || (threadIdx.x & 63) == 63 || edge_r;
+  const bool form_r = own_r && !(edge_r && bc_x != XG_BC_PERIODIC);
+  const int64_t q = j0 + nrow;
+  const bool top_edge = q >= ny;
+  const int64_t rq = (top_edge ? 0 : q) * nx;
+  const bool top_own = !top_edge || bc_y == XG_BC_PERIODIC;
+  const bool fill_b = j0 == 0 && bc_y == XG_BC_FILL;
+  const int64_t rb = (j0 > 0 ? j0 - 1 : ((bc_y == XG_BC_PERIODIC) ? ny - 1 : 0)) * nx;
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+
+  T fa[SEG], fb[SEG];
+  int64_t vao = 0, vbo = 0;
+  if (NVOL >= 1) {
+    vao = area_outer_off(va.ai, o) + j0 * va.sy + i0 * va.sx;
+    load_rows<T, SEG>(fa, va.p, vao, va.sy, va.sx, nrow, (ntl & 4) != 0);
+  }
+  if (NVOL >= 2) {
+    vbo = area_outer_off(vb.ai, o) + j0 * vb.sy + i0 * vb.sx;
+    load_rows<T, SEG>(fb, vb.p, vbo, vb.sy, vb.sx, nrow, (ntl & 8) != 0);
+  }
+  // level 0: Fz[0] from T padded above it; periodic Z keeps Fz[0] for the pad below the last level
+  T tc[SEG], fzc[SEG], fz0[SEG];
+  {
+    const int64_t ka = (bc_z == XG_BC_PERIODIC) ? nz - 1 : 0;
+    T ta[SEG], w0[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      tc[s_] = *reinterpret_cast<const T*>(t + col + ro[s_] + i0);
+      w0[s_] = *reinterpret_cast<const T*>(w + col + ro[s_] + i0);
+      ta[s_] = (bc_z == XG_BC_FILL) ? splat<T>(fill_z) : *reinterpret_cast<const T*>(t + col + ka * plane + ro[s_] + i0);
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      fzc[s_] = w0[s_] * op2<XG_OP_INTERP>(ta[s_], tc[s_]);
+      fz0[s_] = fzc[s_];
+    }
+  }
+  for (int64_t k = 0; k < nz; ++k) {
+    const int64_t lv = col + k * plane;
+    const real* pt = t + lv;
+    const bool more = k + 1 < nz;
+    // the next level's T and w rows first (Fz[k+1]), then this level's u, v and T halo
+    T tn[SEG], wn[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (more) {
+        tn[s_] = *reinterpret_cast<const T*>(pt + plane + ro[s_] + i0);
+        wn[s_] = *reinterpret_cast<const T*>(w + lv + plane + ro[s_] + i0);
+      } else {
+        tn[s_] = tc[s_];
+        wn[s_] = splat<T>(real(0));
+      }
+    }
+    T tb = *reinterpret_cast<const T*>(pt + rb + i0);
+    if (fill_b) tb = splat<T>(fill_y);
+    const T ttop = *reinterpret_cast<const T*>(pt + rq + i0);
+    T uu[SEG], vv[SEG];
+    real tl[SEG], tr[SEG], urt[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      uu[s_] = *reinterpret_cast<const T*>(u + lv + ro[s_] + i0);
+      vv[s_] = *reinterpret_cast<const T*>(v + lv + ro[s_] + i0);
+      tl[s_] = own_l ? pt[ro[s_] + lidx] : real(0);
+      tr[s_] = form_r ? pt[ro[s_] + ridx] : real(0);
+      urt[s_] = form_r ? u[lv + ro[s_] + ridx] : real(0);
+    }
+    const T vtop = *reinterpret_cast<const T*>(v + lv + rq + i0);
+    if (NVOL >= 1 && k > 0 && va.sz != 0)
+      load_rows<T, SEG>(fa, va.p, vao + k * va.sz, va.sy, va.sx, nrow, (ntl & 4) != 0);
+    if (NVOL >= 2 && k > 0 && vb.sz != 0)
+      load_rows<T, SEG>(fb, vb.p, vbo + k * vb.sz, vb.sy, vb.sx, nrow, (ntl & 8) != 0);
+    if (shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real left = from_lane_below(vec_last(tc[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+        if (!own_l) tl[s_] = left;
+      }
+    }
+    T fx[SEG], fy[SEG];
+    real fxr[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      const real left = (edge_l && bc_x == XG_BC_FILL) ? fill_x : tl[s_];
+      fx[s_] = uu[s_] * interp_left_of(tc[s_], left);
+      fy[s_] = vv[s_] * op2<XG_OP_INTERP>(s_ == 0 ? tb : tc[s_ - 1], tc[s_]);
+      fxr[s_] = urt[s_] * interp_left_of(tr[s_], vec_last(tc[s_]));
+    }
+    const T fytop = vtop * op2<XG_OP_INTERP>(tc[SEG - 1], ttop);
+    if (shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real right = from_lane_above(vec_first(fx[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+        if (!own_r) fxr[s_] = right;
+      }
+    }
+    T fzn[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (more) fzn[s_] = wn[s_] * op2<XG_OP_INTERP>(tc[s_], tn[s_]);
+      else fzn[s_] = (bc_z == XG_BC_PERIODIC) ? fz0[s_] : ((bc_z == XG_BC_EXTEND) ? fzc[s_] : splat<T>(fill_z));
+    }
+    real* po = out + lv + j0 * nx + i0;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        real right = fxr[s_];
+        if (edge_r && bc_x == XG_BC_FILL) right = fill_x;
+        else if (edge_r && bc_x == XG_BC_EXTEND) right = vec_last(fx[s_]);
+        T up = (s_ + 1 < nrow) ? fy[s_ + 1] : fytop;
+        if (s_ + 1 >= nrow && !top_own) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : fy[s_];
+        const T h = dudx_fwd(fx[s_], right) + (up - fy[s_]);
+        T z = h + (fzn[s_] - fzc[s_]);
+        if (NVOL == 1) z = z / fa[s_];
+        if (NVOL == 2) z = z / (fa[s_] * fb[s_]);
+        stg_s<T, NTS>(po + s_ * nx, z);
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      tc[s_] = tn[s_];
+      fzc[s_] = fzn[s_];
+    }
+  }
+}
+
 #endif  // !XG_INT
 
 }  // namespace
@@ -857,8 +1029,9 @@ int XG_FN(xg_divergence_halo)(const real* u, const real* v, const real* halo_x, 
   return curl_div_impl(true, u, v, area, area_strides, out, shape, ndim, bc_x, fill_x, bc_y, fill_y, stream, halo_x, halo_y);
 }
 
+// `core`: the trailing dims that are not leading dims (2: (Y, X); K7e's volume: 3, (Z, Y, X))
 static int area_index(const real* m, const int64_t* strides, const int64_t* shape, int ndim, AreaIdx* ai, int64_t* sy,
-                      int64_t* sx) {
+                      int64_t* sx, int core = 2) {
   memset(ai, 0, sizeof(*ai));
   for (int d = 0; d < XG_MAX_NDIM; ++d) ai->fd[d] = make_fastdiv(1);
   *sy = *sx = 0;
@@ -866,7 +1039,7 @@ static int area_index(const real* m, const int64_t* strides, const int64_t* shap
   if (!strides) return fail(XG_ERR_INVALID, "metric without strides");
   *sy = strides[ndim - 2];
   *sx = strides[ndim - 1];
-  for (int d = 0; d < ndim - 2; ++d) {
+  for (int d = 0; d < ndim - core; ++d) {
     if (shape[d] == 1) continue;
     const int64_t st = strides[d];
     if (ai->n > 0 && ai->stride[ai->n - 1] == st * shape[d]) {
@@ -1076,6 +1249,67 @@ int XG_FN(xg_laplacian)(const real* a, const real* dxC, const int64_t* dxC_strid
   const int64_t* const ms[4] = {dxC_strides, dyG_strides, dyC_strides, dxG_strides};
   return div2d_impl(0, a, nullptr, nullptr, met, ms, area, area_strides, out, shape, ndim, bc_x, fill_x, bc_y, fill_y,
                     stream);
+}
+
+// K7e's launcher: (lead, Z, Y, X) fields, the volume `vol` (* `vol2`) with broadcast strides, one wave per column
+int XG_FN(xg_flux_divergence3d)(const real* u, const real* v, const real* w, const real* t, const real* vol,
+                                const int64_t* vol_strides, const real* vol2, const int64_t* vol2_strides, real* out,
+                                const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
+                                real fill_z, void* stream) {
+  if (!u || !v || !w || !t || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  for (int b : {bc_x, bc_y, bc_z})
+    if (b < XG_BC_PERIODIC || b > XG_BC_EXTEND)
+      return fail(XG_ERR_INVALID, "3-D flux divergence needs a periodic, fill or extend boundary on all three axes");
+  if (vol2 && !vol) return fail(XG_ERR_INVALID, "3-D flux divergence: a second volume factor without the first");
+  if ((vol && !vol_strides) || (vol2 && !vol2_strides)) return fail(XG_ERR_INVALID, "metric without strides");
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1];
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 3; ++d) outer *= shape[d];
+  if (outer == 0 || nz == 0 || ny == 0 || nx == 0) return XG_OK;
+  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Z,Y,X) volumes");
+  int rc;
+  VolIdx vi[2];
+  const real* vp[2] = {vol, vol2};
+  const int64_t* vs[2] = {vol_strides, vol2_strides};
+  for (int k = 0; k < 2; ++k) {
+    memset(&vi[k], 0, sizeof(VolIdx));
+    vi[k].p = vp[k];
+    if ((rc = area_index(vp[k], vs[k], shape, ndim, &vi[k].ai, &vi[k].sy, &vi[k].sx, 3))) return rc;
+    vi[k].sz = vp[k] ? vs[k][ndim - 3] : 0;
+  }
+  const int V = (aligned16(t) && aligned16(u) && aligned16(v) && aligned16(w) && aligned16(out) && nx % NV == 0) ? NV : 1;
+  constexpr int SEG = XG_FUSED_SEG;
+  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
+  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
+  const u64 per_outer = ntile * nseg;
+  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the 3-D flux divergence kernel");
+  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
+  const u64 outer_per = MAX_ITEMS / per_outer;
+  hipStream_t st = (hipStream_t)stream;
+  const bool nts = tune().nt_store;
+  // bit 0: the lane neighbours by DPP (K7d), bits 2 / 3: the rows of volume factor 0 / 1 are aligned vectors
+  int vnt = tune().nt_load ? (tune().vec_nt & 1) : 0;
+  for (int k = 0; k < 2; ++k)
+    if (V > 1 && vi[k].sz % NV == 0 && plane_vec_ok(vi[k].p, vi[k].ai, vi[k].sy, vi[k].sx)) vnt |= 4 << k;
+  const int nvol = (vol != nullptr) + (vol2 != nullptr);
+  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_per) {
+    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_per) ? outer - o0 : (int64_t)outer_per);
+    const u64 waves = (u64)nouter * per_outer;
+    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
+    if ((rc = check_grid((u64)nblk + 8))) return rc;
+    const u32 grid = ((nblk + 7) / 8) * 8;
+#define XG_GO(V_, N_, NTS) do { hipLaunchKernelGGL((k_div3d<V_, N_, NTS, SEG>), dim3(grid), dim3(BLOCK), 0, st, t, u, v, w, out, o0, nouter, nblk, nz, ny, nx, fnt, fns, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, vi[0], vi[1], vnt); } while (0)
+#define XG_N(V_, N_) do { if (nts) XG_GO(V_, N_, true); else XG_GO(V_, N_, false); } while (0)
+#define XG_V(V_) do { if (nvol == 2) XG_N(V_, 2); else if (nvol == 1) XG_N(V_, 1); else XG_N(V_, 0); } while (0)
+    if (V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_N
+#undef XG_GO
+  }
+  XG_LAUNCH_CHECK();
+  return XG_OK;
 }
 
 #endif  // !XG_INT

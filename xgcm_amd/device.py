@@ -1215,6 +1215,31 @@ def flux_divergence(u, v, t, area, bc_x: str, bc_y: str, fill_x: float = 0.0, fi
     return out
 
 
+def flux_divergence_3d(u, v, w, t, vol, vol2, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0, fill_y: float = 0.0,
+                       fill_z: float = 0.0) -> torch.Tensor:
+    """Fused 3-D tracer flux divergence in one pass (xg_flux_divergence3d_f64): flux_divergence's horizontal part plus
+    Fz[k+1] - Fz[k] with Fz = w * (t[z-1] + t) / 2, divided by `vol` (* `vol2`, the product formed per cell); `vol` None = no
+    division.  Each axis pads twice as the chain does: the tracer below the first cell, then the flux above the last one."""
+    lib = _MEM.lib()
+    dt, sfx = _common(u, v, w, t, vol, vol2)
+    u, v, w, t = asdevice(u, dt), asdevice(v, dt), asdevice(w, dt), asdevice(t, dt)
+    if u.shape != t.shape or v.shape != t.shape or w.shape != t.shape:
+        raise ValueError("flux_divergence_3d: u, v, w and t must have the same shape")
+    shape = list(t.shape)
+    vol, vol2 = _prep_metric(vol, dt), _prep_metric(vol2, dt)
+    out = _empty(shape, dtype=dt, device=t.device)
+    if out.numel() == 0:
+        return out
+    _check(
+        getattr(lib, "xg_flux_divergence3d_" + sfx)(u.data_ptr(), v.data_ptr(), w.data_ptr(), t.data_ptr(), _ptr(vol),
+                                                    _hip.i64(_bstrides(vol, shape, "volume")), _ptr(vol2),
+                                                    _hip.i64(_bstrides(vol2, shape, "volume")), out.data_ptr(),
+                                                    _hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x),
+                                                    _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z), _stream())
+    )
+    return out
+
+
 def laplacian(a, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, dxC=None, dyC=None, dyG=None,
               dxG=None, area=None) -> torch.Tensor:
     """Fused finite-volume del2 in one pass (xg_laplacian_f64): Fx = (a - a[x-1]) / dxC * dyG, Fy = (a - a[y-1]) / dyC

@@ -47,6 +47,7 @@ from .grid_ufunc import (
 )
 from . import lazy as _lazy
 from .labeled import (CHUNKED_INPUT_MESSAGE, DataArray, Dataset, _aligned_view, _binary_coords, _is_chunked, _is_tensor,
+                      _result_name,
                       from_xarray, is_xarray, to_xarray)
 from .metrics import iterate_axis_combinations
 from .padding import FoldSpec, InteriorOf, halo_cells, no_boundary_error, pad
@@ -1349,6 +1350,94 @@ class Grid:
             gy = gy._replace(coords=_binary_coords(gy, mets["dxG"][0], dims_y))
         res = DataArray(_dev.tohost(out) if host else out, out_dims)
         res = _reattach_coords([res], self, None, {xa.coords["center"], ya.coords["center"]}, [gx, gy])[0]
+        return to_xarray(res) if was_xr else res
+
+    def flux_divergence_3d(self, u, v, w, tracer, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", padding=None,
+                           fill_value=None, metric_weighted: bool = True):
+        """3-D flux-form advection tendency of a tracer in ONE pass -- MITgcm's (di Fx + dj Fy + dk Fr) / (rA drF hFacC):
+        u, v, w and the tracer are read once, the result written once (40 B/cell in float64); the fluxes stay in registers.
+
+        u at (Z:center, Y:center, X:left), v at (Z:center, Y:left, X:center), w at (Z:left, Y:center, X:center), the tracer
+        and the result at the centre.  Bit-identical to the chain
+
+            kw = dict(padding=padding, fill_value=fill_value)
+            fx, fy = grid.flux(u, v, tracer, x_axis, y_axis, **kw)
+            fz = w * grid.interp(tracer, z_axis, **kw)
+            h = grid.divergence(fx, fy, x_axis, y_axis, metric_weighted=False, **kw)
+            out = h + grid.diff(fz, z_axis, **kw)
+            if metric_weighted:
+                out = out / grid.get_metric(out, (x_axis, y_axis, z_axis))
+
+        which pads twice on every axis: the tracer below / left of / above the first cell (center -> left), then the fluxes
+        beyond the last one (left -> center; periodic: the flux at index 0, extend: at n-1, fill: `fill_value` itself).
+        This is the divergence in INDEX space: the vertical term is fz[k+1] - fz[k].  For a model whose Z index grows
+        downward and whose w is positive upward (MITgcm's WVEL), pass -w (exact: negation commutes with *, + and -).
+
+        The volume is what `get_metric(out, (X, Y, Z))` returns: a registered (Z, Y, X) volume, or the product of an area and
+        a thickness, whose two factors the kernel multiplies per cell in the same order.  The chain itself runs (the same
+        calls in the same order) for integer, float16 or mixed dtypes, for (Z, Y, X) not last or fields of different
+        shapes, for chunked host arrays, for a volume with dims the result lacks, and on grids with face connections or a
+        fold."""
+        args = (u, v, w, tracer)
+        (u, xr1), (v, xr2), (w, xr3), (t, xr4) = (self._wrap_in(a) for a in args)
+        was_xr = xr1 or xr2 or xr3 or xr4
+        axes = (self.axes[z_axis], self.axes[y_axis], self.axes[x_axis])
+        za, ya, xa = axes
+        want = {"t": ("center", "center", "center"), "u": ("center", "center", "left"), "v": ("center", "left", "center"),
+                "w": ("left", "center", "center")}
+        got = {k: tuple(ax._get_position_name(f) for ax in axes) for k, f in (("t", t), ("u", u), ("v", v), ("w", w))}
+        if any(tuple(p for p, _ in got[k]) != want[k] for k in want) or any("left" not in ax.coords for ax in axes):
+            raise NotImplementedError("fused 3-D flux divergence needs the tracer at the centre, u at (Z:center, Y:center, "
+                                      "X:left), v at (Z:center, Y:left, X:center) and w at (Z:left, Y:center, X:center)")
+        (_, tz), (_, ty), (_, tx) = got["t"]
+        zl, yl, xl = (ax.coords["left"] for ax in axes)
+        lead = t.dims[:-3]
+        out_dims = lead + (tz, ty, tx)
+        plan = None
+        factors = ()
+        if t.dims == out_dims and u.dims == lead + (tz, ty, xl) and v.dims == lead + (tz, yl, tx) and w.dims == lead + (zl, ty, tx):
+            if metric_weighted:
+                factors = self.get_metric(_DimsOnly(out_dims), (x_axis, y_axis, z_axis), _factors=True)
+                if len(factors) > 2:  # (formed as get_metric forms it; the kernel multiplies two factors at most)
+                    factors = (functools.reduce(operator.mul, factors[1:], factors[0]),)
+                factors = tuple(self._resident(f, t.data) for f in factors)
+            if all(set(f.dims) <= set(out_dims) for f in factors) and not gridops.complex_topology(self, z_axis):
+                plan = self._second_order_plan([u, v, w, t], x_axis, y_axis, padding, fill_value, list(factors))
+            if plan is not None:
+                bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
+                fv = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
+                plan = None if bc[z_axis] is None else plan + (bc[z_axis], float(fv[z_axis] or 0.0))
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            fx, fy = self.flux(args[0], args[1], args[3], x_axis, y_axis, **kw)
+            fz = args[2] * self.interp(args[3], z_axis, **kw)
+            h = self.divergence(fx, fy, x_axis, y_axis, metric_weighted=False, **kw)
+            out = h + self.diff(fz, z_axis, **kw)
+            if metric_weighted:
+                out = out / self.get_metric(out, (x_axis, y_axis, z_axis))
+            return out
+        bcx, bcy, fvx, fvy, bcz, fvz = plan
+        host = not any(_is_tensor(f.data) for f in (u, v, w, t))
+        views = [_aligned_view(f, out_dims) for f in factors] + [None, None]
+        out = _dev.flux_divergence_3d(u.data, v.data, w.data, t.data, views[0], views[1], bcx, bcy, bcz, fvx, fvy, fvz)
+        # coords and name as the chain's, step by step over placeholders: the fluxes, their divergence; the tracer along Z,
+        # its product with w, that product's difference; the sum; the quotient by the volume
+        rx = _reattach_coords([DataArray(_placeholder(u.shape), u.dims)], self, None, {xl}, [u, t])[0]
+        ry = _reattach_coords([DataArray(_placeholder(v.shape), v.dims)], self, None, {yl}, [v, t])[0]
+        h = _reattach_coords([DataArray(_placeholder(t.shape), out_dims)], self, None, {tx, ty}, [rx, ry])[0]
+        tz_l = _reattach_coords([DataArray(_placeholder(t.shape), w.dims, name=t.name)], self, None, {zl}, [t])[0]
+        fz = DataArray(_placeholder(w.shape), w.dims, coords=_binary_coords(w, tz_l, w.dims), name=_result_name(w, tz_l))
+        dz = _reattach_coords([DataArray(_placeholder(t.shape), out_dims, name=fz.name)], self, None, {tz}, [fz])[0]
+        res = DataArray(_placeholder(t.shape), out_dims, coords=_binary_coords(h, dz, out_dims), name=_result_name(h, dz))
+        if factors:
+            vol = factors[0]
+            if len(factors) == 2:
+                vdims = vol.dims + tuple(d for d in factors[1].dims if d not in vol.dims)
+                vshape = tuple(res.sizes[d] for d in vdims)
+                vol = DataArray(_placeholder(vshape), vdims, coords=_binary_coords(vol, factors[1], vdims),
+                                name=_result_name(vol, factors[1]))
+            res = res._replace(coords=_binary_coords(res, vol, out_dims), name=_result_name(res, vol))
+        res = res._replace(data=_dev.tohost(out) if host else out)
         return to_xarray(res) if was_xr else res
 
     def transform(self, da, axis, target, **kwargs):
