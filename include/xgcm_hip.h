@@ -41,6 +41,7 @@
  *   xg_flux_divergence_f64 / xg_laplacian_f64  divergence(flux(u, v, T)) (the "Advection" tendency of
  *                      docs/ufunc_examples.md) and the finite-volume del2, two-step chains in one pass
  *   xg_flux_divergence3d_f64  the same with the vertical flux w * interp(T, Z), divided by the cell volume
+ *   xg_vertical_velocity_f64  w from continuity: -cumsum(divergence(u, v), Z) / area, one pass
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -371,6 +372,24 @@ int xg_flux_divergence3d_f64(const double* u, const double* v, const double* w, 
                              const int64_t* vol_strides, const double* vol2, const int64_t* vol2_strides, double* out,
                              const int64_t* shape, int ndim, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
                              double fill_z, void* stream);
+/* The vertical transport (or velocity) from continuity, one pass over arrays of identical `shape` (.., Z, Y, X): u at
+ * (Z:c, Y:c, X:left), v at (Z:c, Y:left, X:c), out at (Z:left, Y:c, X:c).  It replaces the chain
+ *   U = u * (mu * mu2), V = v * (mv * mv2)        (face weights; NULL: the field itself; mu and mv come together)
+ *   d = (U[i+1] - U[i]) + (V[j+1] - V[j])         xg_divergence_f64 without an area, its X / Y boundaries
+ *   c = nancumsum of d along Z, center -> left    xg_cumsum1d_f64 with skipna: a NaN d counts as 0, levels added in sequence
+ *   out = (-1 * c) / area                         (area NULL: no division)
+ * reverse == 0: c[0] is the Z pad (XG_BC_FILL: fill_z, XG_BC_EXTEND: c[1]) and c[k] = d[0] + .. + d[k-1]; the last level
+ * of d is not used.  XG_BC_PERIODIC needs the column total first and is refused (XG_ERR_UNSUPPORTED): run the chain.
+ * reverse != 0: c[k] = d[nz-1] + .. + d[k], no pad (bc_z and fill_z are ignored).
+ * Argument order: the fields, then (pointer, strides) of u's two face-weight factors, of v's two, and of the area, then out,
+ * shape, ndim and the boundary codes (XG_BC_PERIODIC, XG_BC_FILL, XG_BC_EXTEND; XG_BC_HALO is not accepted) with their
+ * fill values for X, Y and Z.  Every metric uses broadcast strides (0 = broadcast) against `shape`; a second factor
+ * (mu2, mv2) may vary along Z and leading dims only. */
+int xg_vertical_velocity_f64(const double* u, const double* v, const double* mu, const int64_t* mu_strides,
+                             const double* mu2, const int64_t* mu2_strides, const double* mv, const int64_t* mv_strides,
+                             const double* mv2, const int64_t* mv2_strides, const double* area,
+                             const int64_t* area_strides, double* out, const int64_t* shape, int ndim, int bc_x,
+                             double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, int reverse, void* stream);
 
 /* ---- the same two-point operator along the last TWO axes in one pass -------------------- */
 /* out = OP_second(pad(OP_first(pad(in)))) for (.., Y, X) arrays, order 0: X then Y, 1: Y then X;
@@ -478,6 +497,11 @@ int xg_flux_divergence3d_f32(const float* u, const float* v, const float* w, con
                              const int64_t* vol_strides, const float* vol2, const int64_t* vol2_strides, float* out,
                              const int64_t* shape, int ndim, int bc_x, float fill_x, int bc_y, float fill_y, int bc_z,
                              float fill_z, void* stream);
+int xg_vertical_velocity_f32(const float* u, const float* v, const float* mu, const int64_t* mu_strides,
+                             const float* mu2, const int64_t* mu2_strides, const float* mv, const int64_t* mv_strides,
+                             const float* mv2, const int64_t* mv2_strides, const float* area,
+                             const int64_t* area_strides, float* out, const int64_t* shape, int ndim, int bc_x,
+                             float fill_x, int bc_y, float fill_y, int bc_z, float fill_z, int reverse, void* stream);
 int xg_stencil2d_f32(int op, const float* in, float* out, const int64_t* shape, int ndim, int order,
                      int padx_lo, int padx_hi, int bc_x, float fill_x, int pady_lo, int pady_hi,
                      int bc_y, float fill_y, void* stream);

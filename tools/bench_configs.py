@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d against their chains), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity against their chains), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -639,6 +639,17 @@ def main():
         ok3 = bool(torch.equal(g3.flux_divergence_3d(U3, V3, W3, T5).data, adv3_chain().data))
         print(json.dumps({"config": 5, "check": "fused flux_divergence_3d == chain bit for bit at full size", "ok": ok3}), flush=True)
         del W3
+        # w from continuity, -cumsum(divergence(u, v), Z) / rA, in one pass against its four-launch chain (transports in)
+
+        def wcont_chain():
+            d = g3.divergence(U3, V3, metric_weighted=False)
+            w = -g3.cumsum(d, "Z", to="left")
+            return w / g3.get_metric(w, ("X", "Y"))
+
+        rec(5, "vertical_velocity fused -cumsum(divergence(u, v), Z) / rA, periodic/extend/fill: 2 reads + 1 write", timeit(lambda: g3.vertical_velocity(U3, V3), a.reps), c5, 24 + 8 / nz5)
+        rec(5, "vertical_velocity as its chain (4 launches), fused-equivalent bytes", timeit(wcont_chain, max(3, a.reps // 2)), c5, 24 + 8 / nz5)
+        okw = bool(torch.equal(g3.vertical_velocity(U3, V3).data, wcont_chain().data))
+        print(json.dumps({"config": 5, "check": "fused vertical_velocity == chain bit for bit at full size", "ok": okw}), flush=True)
     ranks.close()
 
 

@@ -9,7 +9,7 @@
 // straightforward loops (one output cell at a time, index arithmetic in the open), written against the header's
 // semantics, not against the kernels or the oracle.  It serves the 1-D operators of SURVEY.md section 8(a):
 // stencil (+ pre-gathered halos), cumsum, reduce, pad, the broadcasting binary op and the synthetic generator, plus the
-// fused divergence / vorticity / flux divergence (2-D and 3-D) / laplacian; the other fused / topology / transform entry points exist
+// fused divergence / vorticity / flux divergence (2-D and 3-D) / vertical velocity / laplacian; the other fused / topology / transform entry points exist
 // and return XG_ERR_UNSUPPORTED.
 //
 // Build: g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off  (no FMA contraction: same bit contract as the kernels)
@@ -470,6 +470,80 @@ int div3d(const R* u, const R* v, const R* w, const R* t, const R* vol, const in
 }
 
 
+// the vertical velocity of the header: per lead index, the weighted transports of a level, their divergence, the running
+// nan-sum along Z (upward with the pad at level 0, or downward), then the negation and the division by the area
+template <typename R>
+int wcont(const R* u, const R* v, const R* const met[5], const int64_t* const ms[5], R* out, const int64_t* shape, int ndim,
+          int bc_x, R fill_x, int bc_y, R fill_y, int bc_z, R fill_z, int reverse) {
+  if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  for (int b : {bc_x, bc_y})
+    if (b < XG_BC_PERIODIC || b > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", b);
+  if (!reverse && bc_z != XG_BC_FILL && bc_z != XG_BC_EXTEND)
+    return fail(XG_ERR_UNSUPPORTED, "vertical velocity summed upward pads Z with fill or extend");
+  if ((met[0] != nullptr) != (met[2] != nullptr)) return fail(XG_ERR_INVALID, "face weights for both u and v, or for neither");
+  if ((met[1] && !met[0]) || (met[3] && !met[2])) return fail(XG_ERR_INVALID, "a second face-weight factor without the first");
+  for (int k = 0; k < 5; ++k)
+    if (met[k] && !ms[k]) return fail(XG_ERR_INVALID, "metric without strides");
+  for (int k : {1, 3})
+    if (met[k] && (ms[k][ndim - 2] != 0 || ms[k][ndim - 1] != 0))
+      return fail(XG_ERR_UNSUPPORTED, "the second face-weight factor varies along Z (and leading dims) only");
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx;
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 3; ++d) outer *= shape[d];
+  if (outer == 0 || nz == 0 || plane == 0) return XG_OK;
+  auto wrap = [](int64_t q, int64_t n, int bc) { return bc == XG_BC_PERIODIC ? ((q % n + n) % n) : (q < 0 ? 0 : n - 1); };
+  std::vector<R> tu((size_t)plane), tv((size_t)plane), acc((size_t)plane);
+  for (int64_t o = 0; o < outer; ++o) {
+    int64_t rem = o, moff[5] = {0, 0, 0, 0, 0};  // the lead index decomposed for the broadcast strides
+    for (int d = ndim - 4; d >= 0; --d) {
+      const int64_t i = rem % shape[d];
+      rem /= shape[d];
+      for (int k = 0; k < 5; ++k)
+        if (met[k]) moff[k] += i * ms[k][d];
+    }
+    auto m = [&](int k, int64_t z, int64_t j, int64_t i) {
+      return met[k][moff[k] + z * ms[k][ndim - 3] + j * ms[k][ndim - 2] + i * ms[k][ndim - 1]];
+    };
+    auto put = [&](int64_t z, int64_t p, R c) {
+      const R neg = R(-1) * c;
+      out[(o * nz + z) * plane + p] = met[4] ? neg / m(4, z, p / nx, p % nx) : neg;
+    };
+    if (!reverse && bc_z == XG_BC_FILL)
+      for (int64_t p = 0; p < plane; ++p) put(0, p, fill_z);
+    const int64_t n = reverse ? nz : (nz > 1 ? nz - 1 : (bc_z == XG_BC_EXTEND ? 1 : 0));  // the last level is trimmed
+    for (int64_t t = 0; t < n; ++t) {
+      const int64_t z = reverse ? nz - 1 - t : t;
+      const R* pu = u + (o * nz + z) * plane;
+      const R* pv = v + (o * nz + z) * plane;
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          R a = pu[j * nx + i], b = pv[j * nx + i];
+          if (met[0]) a = a * (met[1] ? m(0, z, j, i) * m(1, z, j, i) : m(0, z, j, i));
+          if (met[2]) b = b * (met[3] ? m(2, z, j, i) * m(3, z, j, i) : m(2, z, j, i));
+          tu[j * nx + i] = a;
+          tv[j * nx + i] = b;
+        }
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t p = j * nx + i;
+          const R ur = i + 1 < nx ? tu[p + 1] : (bc_x == XG_BC_FILL ? fill_x : tu[j * nx + wrap(nx, nx, bc_x)]);
+          const R vu = j + 1 < ny ? tv[p + nx] : (bc_y == XG_BC_FILL ? fill_y : tv[wrap(ny, ny, bc_y) * nx + i]);
+          R d = (ur - tu[p]) + (vu - tv[p]);
+          if (d != d) d = R(0);
+          acc[p] = t == 0 ? d : acc[p] + d;
+          if (reverse) {
+            put(z, p, acc[p]);
+          } else {
+            if (t == 0 && bc_z == XG_BC_EXTEND) put(0, p, acc[p]);
+            if (z + 1 < nz) put(z + 1, p, acc[p]);
+          }
+        }
+    }
+  }
+  return XG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -678,6 +752,15 @@ int xg_event_destroy(void* ev) { free(ev); return XG_OK; }
                                  const R* vol2, const int64_t* vs2, R* out, const int64_t* shape, int ndim, int bc_x,  \
                                  R fill_x, int bc_y, R fill_y, int bc_z, R fill_z, void*) {                            \
     return div3d<R>(u, v, w, t, vol, vs, vol2, vs2, out, shape, ndim, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z);     \
+  }                                                                                                                   \
+  int xg_vertical_velocity_##SFX(const R* u, const R* v, const R* mu, const int64_t* mus, const R* mu2,               \
+                                 const int64_t* mu2s, const R* mv, const int64_t* mvs, const R* mv2,                   \
+                                 const int64_t* mv2s, const R* area, const int64_t* as, R* out, const int64_t* shape,  \
+                                 int ndim, int bc_x, R fill_x, int bc_y, R fill_y, int bc_z, R fill_z, int reverse,    \
+                                 void*) {                                                                              \
+    const R* const met[5] = {mu, mu2, mv, mv2, area};                                                                 \
+    const int64_t* const ms[5] = {mus, mu2s, mvs, mv2s, as};                                                          \
+    return wcont<R>(u, v, met, ms, out, shape, ndim, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, reverse);             \
   }                                                                                                                   \
   int xg_laplacian_##SFX(const R* a, const R* dxC, const int64_t* dxCs, const R* dyC, const int64_t* dyCs, const R* dyG, \
                          const int64_t* dyGs, const R* dxG, const int64_t* dxGs, const R* area, const int64_t* as,     \

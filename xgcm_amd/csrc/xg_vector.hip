@@ -815,6 +815,214 @@ __global__ __launch_bounds__(BLOCK) void k_div3d(
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// K7f: the vertical transport from continuity in ONE pass over (lead, Z, Y, X):
+//   d[k] = (U[i+1] - U[i]) + (V[j+1] - V[j])     K7b's arithmetic and X / Y boundaries, U = u [* face area], V = v [* face area]
+//   forward:  w[0] = Z pad (fill: fill_z, extend: d[0]),  w[k] = d[0] + .. + d[k-1]
+//   reverse:  w[k] = d[nz-1] + .. + d[k]
+//   out = (-1 * w) [/ area]
+// i.e. divergence -> nancumsum along Z (center -> left) -> negation -> division, the levels of a column added IN SEQUENCE as
+// k_cumsum_strided adds them (a NaN divergence counts as 0; the first sum is d itself, not 0 + d).  The decomposition is
+// K7e's: a wave owns one (lead, Y segment, X tile) column and marches Z, upward or downward (`reverse`, wave-uniform); the
+// running sum stays in registers, so u and v are read once and w written once: 24 B/cell in float64 against 72 for the chain.
+// The loads form a rolling window of U levels ahead of the sum (k_cumsum_strided's PIPE): a march whose loads wait behind
+// its own stores loses the memory system (K5c).  Face weights: factor `a` of a field is any broadcast array (its rows stay
+// in registers when it does not vary along Z), factor `b` varies along Z only and is one wave-uniform load per level.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ real nan0(real x) { return (x != x) ? real(0) : x; }  // as the scans' (xg_scan.hip)
+__device__ __forceinline__ dv nan0(dv x) {
+  dv o;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) o[k] = nan0(x[k]);
+  return o;
+}
+
+template <typename T, int SEG>
+struct WcLevel {  // what one level of a column brings: SEG rows of u with the element right of the lane, SEG + 1 rows of v
+  T uu[SEG], vv[SEG], vtop;
+  real urt[SEG];
+};
+
+template <int V, bool FW, bool AR, bool NTS, int SEG, int U>
+__global__ __launch_bounds__(BLOCK) void k_wcont(
+    const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk,
+    int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
+    real fill_z, int reverse, VolIdx ua, VolIdx ub, VolIdx va, VolIdx vb, VolIdx ar, int ntl) {
+  typedef typename VecT<V>::type T;
+  typedef WcLevel<T, SEG> L;
+  const u32 pb = (nblk + 7) >> 3;
+  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
+  if (lb >= nblk) return;
+  const u32 wv = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
+  const u32 r = fdiv(wv, ntile);
+  const u32 tile = wv - r * ntile.d;
+  const u32 oo = fdiv(r, nseg);
+  if (oo >= nouter) return;
+  const u32 sg = r - oo * nseg.d;
+  const int64_t o = o0 + oo;
+  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
+  if (i0 >= nx) return;
+  const int64_t j0 = (int64_t)sg * SEG;
+  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  // X as K7e: the element right of the lane's vector comes from the lane above (DPP) or, for the tile's last lane and the
+  // row's last vector, from memory (periodic: column 0); fill / extend at the row's end need no load
+  const bool edge_r = (i0 + V >= nx);
+  const int64_t ridx = edge_r ? 0 : i0 + V;
+  const bool shl = V > 1 && (ntl & 1);
+  const bool own_r = !shl || (threadIdx.x & 63) == 63 || edge_r;
+  const bool form_r = own_r && !(edge_r && bc_x != XG_BC_PERIODIC);
+  // Y as K7b: the row above the segment (periodic: row 0; fill / extend at the top need no row, row 0 is loaded and unused)
+  const int64_t q = j0 + nrow;
+  const bool top_edge = q >= ny;
+  const int64_t rq = (top_edge ? 0 : q) * nx;
+  const bool top_own = !top_edge || bc_y == XG_BC_PERIODIC;
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+  const real* pu = u + col + i0;
+  const real* pv = v + col + i0;
+  const real* pur = u + col + ridx;
+
+  // the marched levels in scan order: forward drops the last level (center -> left trims it), except that `extend` pads
+  // with the first partial sum, which exists for nz == 1 too
+  const bool fwd = !reverse;
+  const int64_t n = fwd ? ((nz > 1) ? nz - 1 : ((bc_z == XG_BC_EXTEND) ? 1 : 0)) : nz;
+  auto level = [&](int64_t t) -> int64_t { return fwd ? t : nz - 1 - t; };
+  auto fetch = [&](int64_t k) -> L {
+    L x;
+    const int64_t lv = k * plane;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.uu[s_] = *reinterpret_cast<const T*>(pu + lv + ro[s_]);
+      x.vv[s_] = *reinterpret_cast<const T*>(pv + lv + ro[s_]);
+      x.urt[s_] = form_r ? pur[lv + ro[s_]] : real(0);
+    }
+    x.vtop = *reinterpret_cast<const T*>(pv + lv + rq);
+    return x;
+  };
+
+  // face weights: factor a's rows (u: SEG rows and the element at `ridx`; v: SEG + 1 rows) stay in registers and are
+  // loaded again per level only when the factor varies along Z
+  T fu[SEG], fv[SEG], fvt = splat<T>(real(1));
+  real fur[SEG];
+  int64_t uao = 0, vao = 0, ubo = 0, vbo = 0;
+  auto weights = [&](int64_t k) {
+    const int64_t ou = uao + k * ua.sz, ov = vao + k * va.sz;
+    load_rows<T, SEG>(fu, ua.p, ou + j0 * ua.sy + i0 * ua.sx, ua.sy, ua.sx, nrow, (ntl & 4) != 0);
+    load_rows<T, SEG>(fv, va.p, ov + j0 * va.sy + i0 * va.sx, va.sy, va.sx, nrow, (ntl & 8) != 0);
+    T top[1];
+    load_rows<T, 1>(top, va.p, ov + (top_edge ? 0 : q) * va.sy + i0 * va.sx, va.sy, va.sx, 1, (ntl & 8) != 0);
+    fvt = top[0];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_)
+      fur[s_] = form_r ? ua.p[ou + (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * ua.sy + ridx * ua.sx] : real(0);
+  };
+  if (FW) {
+    uao = area_outer_off(ua.ai, o);
+    vao = area_outer_off(va.ai, o);
+    if (ub.p) ubo = area_outer_off(ub.ai, o);
+    if (vb.p) vbo = area_outer_off(vb.ai, o);
+    if (n > 0) weights(level(0));
+  }
+  T aa[SEG];
+  int64_t aro = 0;
+  if (AR) {
+    aro = area_outer_off(ar.ai, o) + j0 * ar.sy + i0 * ar.sx;
+    load_rows<T, SEG>(aa, ar.p, aro, ar.sy, ar.sx, nrow, (ntl & 16) != 0);
+  }
+  real* po = out + col + j0 * nx + i0;
+  auto put = [&](int64_t k, const T (&a)[SEG]) {  // output level k: negation, division, SEG rows in linear order
+    if (AR && ar.sz != 0) load_rows<T, SEG>(aa, ar.p, aro + k * ar.sz, ar.sy, ar.sx, nrow, (ntl & 16) != 0);
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        T z = splat<T>(real(-1)) * a[s_];
+        if (AR) z = z / aa[s_];
+        stg_s<T, NTS>(po + k * plane + s_ * nx, z);
+      }
+    }
+  };
+
+  T acc[SEG];
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) acc[s_] = splat<T>(fill_z);
+  if (fwd && bc_z == XG_BC_FILL) put(0, acc);
+  bool started = false;
+  auto step = [&](int64_t t, const L& x) {
+    const int64_t k = level(t);
+    T uc[SEG], vc[SEG], vt = x.vtop;
+    real right[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      uc[s_] = x.uu[s_];
+      vc[s_] = x.vv[s_];
+      right[s_] = x.urt[s_];
+    }
+    if (FW) {
+      if (t > 0 && (ua.sz != 0 || va.sz != 0)) weights(k);
+      // (products commute bit for bit: a * b is get_metric's product whichever of its two factors varies along Z)
+      const bool ubz = ub.p != nullptr, vbz = vb.p != nullptr;
+      const real zu = ubz ? ub.p[ubo + k * ub.sz] : real(1), zv = vbz ? vb.p[vbo + k * vb.sz] : real(1);
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        uc[s_] = uc[s_] * (ubz ? fu[s_] * splat<T>(zu) : fu[s_]);
+        right[s_] = right[s_] * (ubz ? fur[s_] * zu : fur[s_]);
+        vc[s_] = vc[s_] * (vbz ? fv[s_] * splat<T>(zv) : fv[s_]);
+      }
+      vt = vt * (vbz ? fvt * splat<T>(zv) : fvt);
+    }
+    if (shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real above = from_lane_above(vec_first(uc[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+        if (!own_r) right[s_] = above;
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      real rt = right[s_];
+      if (edge_r && bc_x == XG_BC_FILL) rt = fill_x;
+      else if (edge_r && bc_x == XG_BC_EXTEND) rt = vec_last(uc[s_]);
+      T up = (s_ + 1 < nrow) ? vc[(s_ + 1 < SEG) ? s_ + 1 : s_] : vt;
+      if (s_ + 1 >= nrow && !top_own) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : vc[s_];
+      const T d = nan0(dudx_fwd(uc[s_], rt) + (up - vc[s_]));
+      acc[s_] = started ? acc[s_] + d : d;
+    }
+    started = true;
+    if (fwd) {  // center -> left: the sum through level k is w[k + 1]; `extend` pads with the first one
+      if (t == 0 && bc_z == XG_BC_EXTEND) put(0, acc);
+      if (k + 1 < nz) put(k + 1, acc);
+    } else {
+      put(k, acc);
+    }
+  };
+
+  // the rolling window: every consumed level is replaced by the load of the level U steps ahead
+  L win[U];
+#pragma unroll
+  for (int p = 0; p < U; ++p)
+    if (p < n) win[p] = fetch(level(p));
+  int64_t t = 0;
+  for (; t + 2 * U <= n; t += U) {
+#pragma unroll
+    for (int p = 0; p < U; ++p) {
+      const L x = win[p];
+      win[p] = fetch(level(t + U + p));
+      step(t + p, x);
+    }
+  }
+  for (; t < n; t += U) {  // the last one or two windows: refills and consumes guarded (wave-uniform tests)
+#pragma unroll
+    for (int p = 0; p < U; ++p) {
+      const L x = win[p];
+      if (t + U + p < n) win[p] = fetch(level(t + U + p));
+      if (t + p < n) step(t + p, x);
+    }
+  }
+}
+
 #endif  // !XG_INT
 
 }  // namespace
@@ -1305,6 +1513,84 @@ int XG_FN(xg_flux_divergence3d)(const real* u, const real* v, const real* w, con
     if (V > 1) XG_V(NV);
     else XG_V(1);
 #undef XG_V
+#undef XG_N
+#undef XG_GO
+  }
+  XG_LAUNCH_CHECK();
+  return XG_OK;
+}
+
+// K7f's launcher: (lead, Z, Y, X) fields, five optional broadcast metrics (face weights of u and of v, two factors each,
+// and the area of the result), one wave per column
+#ifndef XG_WCONT_WINDOW
+#define XG_WCONT_WINDOW 3  // levels in flight ahead of the running sum
+#endif
+int XG_FN(xg_vertical_velocity)(const real* u, const real* v, const real* mu, const int64_t* mu_strides, const real* mu2,
+                                const int64_t* mu2_strides, const real* mv, const int64_t* mv_strides, const real* mv2,
+                                const int64_t* mv2_strides, const real* area, const int64_t* area_strides, real* out,
+                                const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
+                                real fill_z, int reverse, void* stream) {
+  if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  for (int b : {bc_x, bc_y})
+    if (b < XG_BC_PERIODIC || b > XG_BC_EXTEND)
+      return fail(XG_ERR_INVALID, "vertical velocity needs a periodic, fill or extend boundary on X and Y");
+  if (!reverse && bc_z != XG_BC_FILL && bc_z != XG_BC_EXTEND)
+    return fail(XG_ERR_UNSUPPORTED, "vertical velocity summed upward pads Z with fill or extend (periodic needs the column total first)");
+  if ((mu != nullptr) != (mv != nullptr)) return fail(XG_ERR_INVALID, "vertical velocity: face weights for both u and v, or for neither");
+  if ((mu2 && !mu) || (mv2 && !mv)) return fail(XG_ERR_INVALID, "vertical velocity: a second face-weight factor without the first");
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1];
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 3; ++d) outer *= shape[d];
+  if (outer == 0 || nz == 0 || ny == 0 || nx == 0) return XG_OK;
+  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Z,Y,X) volumes");
+  int rc;
+  VolIdx mi[5];  // u: a, b; v: a, b; area
+  const real* mp[5] = {mu, mu2, mv, mv2, area};
+  const int64_t* ms[5] = {mu_strides, mu2_strides, mv_strides, mv2_strides, area_strides};
+  for (int k = 0; k < 5; ++k) {
+    if (mp[k] && !ms[k]) return fail(XG_ERR_INVALID, "metric without strides");
+    memset(&mi[k], 0, sizeof(VolIdx));
+    mi[k].p = mp[k];
+    if ((rc = area_index(mp[k], ms[k], shape, ndim, &mi[k].ai, &mi[k].sy, &mi[k].sx, 3))) return rc;
+    mi[k].sz = mp[k] ? ms[k][ndim - 3] : 0;
+  }
+  for (int k : {1, 3})
+    if (mp[k] && (mi[k].sy != 0 || mi[k].sx != 0))
+      return fail(XG_ERR_UNSUPPORTED, "vertical velocity: the second face-weight factor varies along Z (and leading dims) only");
+  const int V = (aligned16(u) && aligned16(v) && aligned16(out) && nx % NV == 0) ? NV : 1;
+  constexpr int SEG = XG_FUSED_SEG;
+  constexpr int U = XG_WCONT_WINDOW;
+  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
+  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
+  const u64 per_outer = ntile * nseg;
+  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the vertical velocity kernel");
+  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
+  const u64 outer_per = MAX_ITEMS / per_outer;
+  hipStream_t st = (hipStream_t)stream;
+  const bool nts = tune().nt_store;
+  // bit 0: the lane neighbour by DPP (K7d), bits 2 / 3 / 4: the rows of u's factor a / v's factor a / the area are aligned vectors
+  int vnt = tune().nt_load ? (tune().vec_nt & 1) : 0;
+  const int vec_of[3] = {0, 2, 4};
+  for (int k = 0; k < 3; ++k) {
+    const VolIdx& m = mi[vec_of[k]];
+    if (V > 1 && m.p && m.sz % NV == 0 && plane_vec_ok(m.p, m.ai, m.sy, m.sx)) vnt |= 4 << k;
+  }
+  const bool fw = mu != nullptr, ar = area != nullptr;
+  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_per) {
+    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_per) ? outer - o0 : (int64_t)outer_per);
+    const u64 waves = (u64)nouter * per_outer;
+    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
+    if ((rc = check_grid((u64)nblk + 8))) return rc;
+    const u32 grid = ((nblk + 7) / 8) * 8;
+#define XG_GO(V_, F_, A_, NTS) do { hipLaunchKernelGGL((k_wcont<V_, F_, A_, NTS, SEG, U>), dim3(grid), dim3(BLOCK), 0, st, u, v, out, o0, nouter, nblk, nz, ny, nx, fnt, fns, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, reverse ? 1 : 0, mi[0], mi[1], mi[2], mi[3], mi[4], vnt); } while (0)
+#define XG_N(V_, F_, A_) do { if (nts) XG_GO(V_, F_, A_, true); else XG_GO(V_, F_, A_, false); } while (0)
+#define XG_A(V_, F_) do { if (ar) XG_N(V_, F_, true); else XG_N(V_, F_, false); } while (0)
+#define XG_V(V_) do { if (fw) XG_A(V_, true); else XG_A(V_, false); } while (0)
+    if (V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_A
 #undef XG_N
 #undef XG_GO
   }

@@ -1240,6 +1240,32 @@ def flux_divergence_3d(u, v, w, t, vol, vol2, bc_x: str, bc_y: str, bc_z: str, f
     return out
 
 
+def vertical_velocity(u, v, mu, mu2, mv, mv2, area, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0,
+                      fill_y: float = 0.0, fill_z: float = 0.0, reverse: bool = False) -> torch.Tensor:
+    """Fused w from continuity in one pass (xg_vertical_velocity_f64): the divergence of u * (mu * mu2) and v * (mv * mv2)
+    (None: the field itself), its nancumsum along Z from the centre to the left position (upward with the Z pad at level 0,
+    or `reverse`), negated and divided by `area` (None = no division).  The second factors vary along Z only."""
+    lib = _MEM.lib()
+    dt, sfx = _common(u, v, mu, mu2, mv, mv2, area)
+    u, v = asdevice(u, dt), asdevice(v, dt)
+    if u.shape != v.shape:
+        raise ValueError("vertical_velocity: u and v must have the same shape")
+    shape = list(u.shape)
+    mets = [_prep_metric(m, dt) for m in (mu, mu2, mv, mv2, area)]
+    out = _empty(shape, dtype=dt, device=u.device)
+    if out.numel() == 0:
+        return out
+    margs = []
+    for m, what in zip(mets, ("face weight", "face weight", "face weight", "face weight", "area")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
+    _check(
+        getattr(lib, "xg_vertical_velocity_" + sfx)(u.data_ptr(), v.data_ptr(), *margs, out.data_ptr(), _hip.i64(shape),
+                                                    len(shape), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y),
+                                                    _hip.BC[bc_z], float(fill_z), int(bool(reverse)), _stream())
+    )
+    return out
+
+
 def laplacian(a, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, dxC=None, dyC=None, dyG=None,
               dxG=None, area=None) -> torch.Tensor:
     """Fused finite-volume del2 in one pass (xg_laplacian_f64): Fx = (a - a[x-1]) / dxC * dyG, Fy = (a - a[y-1]) / dyC

@@ -321,7 +321,7 @@ class DataArray:
     def __rsub__(self, o): return self._binary(o, "sub", True)
 
     def __neg__(self):
-        return self._binary(-1.0 if np.dtype(self.dtype).kind == "f" else -1, "mul", True)
+        return self._binary(-1.0 if _dt.np_dtype(self.data).kind == "f" else -1, "mul", True)  # (np_dtype: HBM tensors too)
 
     def __abs__(self):
         data = self.data
