@@ -391,6 +391,34 @@ int xg_vertical_velocity_f64(const double* u, const double* v, const double* mu,
                              const int64_t* area_strides, double* out, const int64_t* shape, int ndim, int bc_x,
                              double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, int reverse, void* stream);
 
+/* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
+/* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).
+ * xg_kinetic_energy replaces the chain of six launches
+ *   ke = 0.5 * (interp(u * u, X) + interp(v * v, Y))        both left -> center, out at the centre
+ *      = 0.5 * ((u[j,i]^2 + u[j,i+1]^2) / 2 + (v[j,i]^2 + v[j+1,i]^2) / 2)
+ * whose interpolations pad the SQUARES right of / above the last column / row -- periodic: the square at index 0,
+ * extend: at n-1, fill: fill_x / fill_y itself (not its square).
+ * xg_momentum_advection replaces the chain of twenty launches
+ *   zeta = xg_vorticity_f64(u, v, rAz) [+ coriolis]                          (Y:left, X:left)
+ *   ke   = as above
+ *   vbar = interp(interp(v, X), Y),  ubar = interp(interp(u, Y), X)          v at u's points, u at v's
+ *   gx, gy = xg_gradient_f64(ke, dxC, dyC)
+ *   out_u = interp(zeta, Y) * vbar - gx                                       at u's points
+ *   out_v = -(interp(zeta, X) * ubar) - gy                                    at v's points
+ * bit for bit, every stage with the same bc / fill per axis on the side the chain pads it: u below the first row and v
+ * left of the first column (vorticity, the first means), zeta and the first means above / right of the last row / column,
+ * the squares above / right, ke below / left.  Periodic: the STAGE's value at the wrapped index, extend: at the clamped
+ * index, fill: the fill value itself (a filled zeta is fill, not fill + coriolis).  rAz, dxC, dyC come together or are all
+ * NULL (the plain differences); coriolis NULL: no Coriolis term.  The four planes use broadcast strides (0 = broadcast)
+ * against `shape`.  XG_BC_HALO is not accepted. */
+int xg_kinetic_energy_f64(const double* u, const double* v, double* out, const int64_t* shape, int ndim, int bc_x,
+                          double fill_x, int bc_y, double fill_y, void* stream);
+int xg_momentum_advection_f64(const double* u, const double* v, const double* coriolis, const int64_t* coriolis_strides,
+                              const double* rAz, const int64_t* rAz_strides, const double* dxC,
+                              const int64_t* dxC_strides, const double* dyC, const int64_t* dyC_strides, double* out_u,
+                              double* out_v, const int64_t* shape, int ndim, int bc_x, double fill_x, int bc_y,
+                              double fill_y, void* stream);
+
 /* ---- the same two-point operator along the last TWO axes in one pass -------------------- */
 /* out = OP_second(pad(OP_first(pad(in)))) for (.., Y, X) arrays, order 0: X then Y, 1: Y then X;
  * replaces two sequential apply_as_grid_ufunc passes of Grid.interp/diff/min/max(da, [ax1, ax2])
@@ -502,6 +530,13 @@ int xg_vertical_velocity_f32(const float* u, const float* v, const float* mu, co
                              const float* mv2, const int64_t* mv2_strides, const float* area,
                              const int64_t* area_strides, float* out, const int64_t* shape, int ndim, int bc_x,
                              float fill_x, int bc_y, float fill_y, int bc_z, float fill_z, int reverse, void* stream);
+int xg_kinetic_energy_f32(const float* u, const float* v, float* out, const int64_t* shape, int ndim, int bc_x,
+                          float fill_x, int bc_y, float fill_y, void* stream);
+int xg_momentum_advection_f32(const float* u, const float* v, const float* coriolis, const int64_t* coriolis_strides,
+                              const float* rAz, const int64_t* rAz_strides, const float* dxC,
+                              const int64_t* dxC_strides, const float* dyC, const int64_t* dyC_strides, float* out_u,
+                              float* out_v, const int64_t* shape, int ndim, int bc_x, float fill_x, int bc_y,
+                              float fill_y, void* stream);
 int xg_stencil2d_f32(int op, const float* in, float* out, const int64_t* shape, int ndim, int order,
                      int padx_lo, int padx_hi, int bc_x, float fill_x, int pady_lo, int pady_hi,
                      int bc_y, float fill_y, void* stream);

@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity against their chains), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection against their chains), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -52,6 +52,30 @@ def timeit(fn, reps):
     torch.cuda.synchronize()
     ts = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(reps))
     return ts[len(ts) // 2]
+
+
+def timeit_interleaved(fa, fb, reps):
+    """medians of `fa` and `fb` timed in turns (a, b, a, b, ...) in one process: both see the same clocks and neighbours"""
+    import time
+
+    t0 = time.perf_counter()
+    while True:
+        fa()
+        fb()
+        torch.cuda.synchronize()
+        if time.perf_counter() - t0 >= 0.15:
+            break
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * reps + 1)]
+    ev[0].record()
+    for i in range(reps):
+        fa()
+        ev[2 * i + 1].record()
+        fb()
+        ev[2 * i + 2].record()
+    torch.cuda.synchronize()
+    ta = sorted(ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(reps))
+    tb = sorted(ev[2 * i + 1].elapsed_time(ev[2 * i + 2]) for i in range(reps))
+    return ta[len(ta) // 2], tb[len(tb) // 2]
 
 
 def rec(cfg, name, ms, cells, bpc):
@@ -650,6 +674,39 @@ def main():
         rec(5, "vertical_velocity as its chain (4 launches), fused-equivalent bytes", timeit(wcont_chain, max(3, a.reps // 2)), c5, 24 + 8 / nz5)
         okw = bool(torch.equal(g3.vertical_velocity(U3, V3).data, wcont_chain().data))
         print(json.dumps({"config": 5, "check": "fused vertical_velocity == chain bit for bit at full size", "ok": okw}), flush=True)
+        del T5, U3, V3
+        torch.cuda.empty_cache()
+        # the momentum side on the MITgcm grid (dxC, dyC, rAz; periodic / extend) with f at the vorticity point: kinetic energy
+        # and the vector-invariant advection term in one pass each against their chains of six / twenty launches of the
+        # operators above, timed in turns with them
+        F5 = DataArray(D.synthetic((n5, n5), 55, 0, 1.0e-4, 0.0), ("YG", "XG"))
+
+        def ke_chain():
+            return 0.5 * (grid.interp(U * U, "X") + grid.interp(V * V, "Y"))
+
+        def mom_chain():
+            zeta = grid.vorticity(U, V) + F5
+            ke = 0.5 * (grid.interp(U * U, "X") + grid.interp(V * V, "Y"))
+            vbar = grid.interp(grid.interp(V, "X"), "Y")
+            ubar = grid.interp(grid.interp(U, "Y"), "X")
+            gx, gy = grid.gradient(ke, metric_weighted=True)
+            return grid.interp(zeta, "Y") * vbar - gx, -(grid.interp(zeta, "X") * ubar) - gy
+
+        rk = max(3, a.reps // 2)
+        t_f, t_c = timeit_interleaved(lambda: grid.kinetic_energy(U, V), ke_chain, rk)
+        rec(5, "kinetic_energy fused 0.5*(interp(u*u,X)+interp(v*v,Y)), periodic/extend: 2 reads + 1 write", t_f, c5, 24)
+        rec(5, "kinetic_energy as its chain (6 launches), fused-equivalent bytes", t_c, c5, 24)
+        okk = bool(torch.equal(grid.kinetic_energy(U, V).data, ke_chain().data))
+        print(json.dumps({"config": 5, "check": "fused kinetic_energy == chain bit for bit at full size", "ok": okk,
+                          "speedup": round(t_c / t_f, 2)}), flush=True)
+        t_f, t_c = timeit_interleaved(lambda: grid.momentum_advection(U, V, F5), mom_chain, rk)
+        rec(5, "momentum_advection fused (rAz, dxC, dyC, coriolis), periodic/extend: 2 reads + 2 writes", t_f, c5, 32 + 32 / nz5)
+        rec(5, "momentum_advection as its chain (20 launches), fused-equivalent bytes", t_c, c5, 32 + 32 / nz5)
+        gu, gv = grid.momentum_advection(U, V, F5)
+        wu, wv = mom_chain()
+        okm = bool(torch.equal(gu.data, wu.data) and torch.equal(gv.data, wv.data))
+        print(json.dumps({"config": 5, "check": "fused momentum_advection == chain bit for bit at full size", "ok": okm,
+                          "speedup": round(t_c / t_f, 2)}), flush=True)
     ranks.close()
 
 

@@ -9,7 +9,8 @@
 // straightforward loops (one output cell at a time, index arithmetic in the open), written against the header's
 // semantics, not against the kernels or the oracle.  It serves the 1-D operators of SURVEY.md section 8(a):
 // stencil (+ pre-gathered halos), cumsum, reduce, pad, the broadcasting binary op and the synthetic generator, plus the
-// fused divergence / vorticity / flux divergence (2-D and 3-D) / vertical velocity / laplacian; the other fused / topology / transform entry points exist
+// fused divergence / vorticity / flux divergence (2-D and 3-D) / vertical velocity / laplacian / kinetic energy / momentum
+// advection; the other fused / topology / transform entry points exist
 // and return XG_ERR_UNSUPPORTED.
 //
 // Build: g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off  (no FMA contraction: same bit contract as the kernels)
@@ -544,6 +545,85 @@ int wcont(const R* u, const R* v, const R* const met[5], const int64_t* const ms
   return XG_OK;
 }
 
+// kinetic energy (ke_only) and the vector-invariant momentum advection of the header: the stages of the chain one after
+// the other over whole planes, each read through `get`, which pads a plane by one cell on one axis at a time (periodic:
+// the plane's own value at the wrapped index, extend: at the clamped index, fill: the fill value of that axis).
+// met[] = {rAz, coriolis, dxC, dyC}: the three metrics all or none, coriolis on its own
+template <typename R>
+int momentum(bool ke_only, const R* u, const R* v, const R* const met[4], const int64_t* const ms[4], R* out_u, R* out_v,
+             const int64_t* shape, int ndim, int bc_x, R fill_x, int bc_y, R fill_y) {
+  if (!u || !v || !out_u || (!ke_only && !out_v) || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
+  for (int b : {bc_x, bc_y})
+    if (b < XG_BC_PERIODIC || b > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", b);
+  for (int k = 0; k < 4; ++k)
+    if (met[k] && !ms[k]) return fail(XG_ERR_INVALID, "metric without strides");
+  const int nmet = (met[0] != nullptr) + (met[2] != nullptr) + (met[3] != nullptr);
+  if (nmet != 0 && nmet != 3) return fail(XG_ERR_INVALID, "momentum advection: the three metrics rAz, dxC, dyC, or none");
+  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
+  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
+  const size_t n = (size_t)(ny * nx);
+  std::vector<R> zeta(n), uu(n), vv(n), ke(n), vx(n), uy(n);
+  auto get = [&](const R* a, int64_t j, int64_t i) -> R {
+    if (i < 0 || i >= nx) {
+      if (bc_x == XG_BC_FILL) return fill_x;
+      i = bc_x == XG_BC_PERIODIC ? (i + nx) % nx : (i < 0 ? 0 : nx - 1);
+    }
+    if (j < 0 || j >= ny) {
+      if (bc_y == XG_BC_FILL) return fill_y;
+      j = bc_y == XG_BC_PERIODIC ? (j + ny) % ny : (j < 0 ? 0 : ny - 1);
+    }
+    return a[j * nx + i];
+  };
+  for (int64_t o = 0; o < outer; ++o) {
+    int64_t rem = o, moff[4] = {0, 0, 0, 0};  // the outer index decomposed for the broadcast strides
+    for (int d = ndim - 3; d >= 0; --d) {
+      const int64_t i = rem % shape[d];
+      rem /= shape[d];
+      for (int k = 0; k < 4; ++k)
+        if (met[k]) moff[k] += i * ms[k][d];
+    }
+    auto m = [&](int k, int64_t j, int64_t i) { return met[k][moff[k] + j * ms[k][ndim - 2] + i * ms[k][ndim - 1]]; };
+    const R* pu = u + o * ny * nx;
+    const R* pv = v + o * ny * nx;
+    auto each = [&](auto&& body) {
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) body(j, i, j * nx + i);
+    };
+    each([&](int64_t, int64_t, int64_t c) { uu[c] = pu[c] * pu[c]; vv[c] = pv[c] * pv[c]; });
+    each([&](int64_t j, int64_t i, int64_t c) {
+      ke[c] = R(0.5) * ((uu[c] + get(uu.data(), j, i + 1)) / R(2) + (vv[c] + get(vv.data(), j + 1, i)) / R(2));
+    });
+    if (ke_only) {
+      each([&](int64_t, int64_t, int64_t c) { out_u[o * ny * nx + c] = ke[c]; });
+      continue;
+    }
+    each([&](int64_t j, int64_t i, int64_t c) {
+      R z = (pv[c] - get(pv, j, i - 1)) - (pu[c] - get(pu, j - 1, i));
+      if (nmet) z = z / m(0, j, i);
+      if (met[1]) z = z + m(1, j, i);
+      zeta[c] = z;
+      vx[c] = (get(pv, j, i - 1) + pv[c]) / R(2);
+      uy[c] = (get(pu, j - 1, i) + pu[c]) / R(2);
+    });
+    each([&](int64_t j, int64_t i, int64_t c) {
+      const R zy = (zeta[c] + get(zeta.data(), j + 1, i)) / R(2), vbar = (vx[c] + get(vx.data(), j + 1, i)) / R(2);
+      const R zx = (zeta[c] + get(zeta.data(), j, i + 1)) / R(2), ubar = (uy[c] + get(uy.data(), j, i + 1)) / R(2);
+      R gx = ke[c] - get(ke.data(), j, i - 1), gy = ke[c] - get(ke.data(), j - 1, i);
+      if (nmet) {
+        gx = gx / m(2, j, i);
+        gy = gy / m(3, j, i);
+      }
+      const R pu_ = zy * vbar, pv_ = zx * ubar;
+      out_u[o * ny * nx + c] = pu_ - gx;
+      out_v[o * ny * nx + c] = R(-1) * pv_ - gy;
+    });
+  }
+  return XG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -761,6 +841,20 @@ int xg_event_destroy(void* ev) { free(ev); return XG_OK; }
     const R* const met[5] = {mu, mu2, mv, mv2, area};                                                                 \
     const int64_t* const ms[5] = {mus, mu2s, mvs, mv2s, as};                                                          \
     return wcont<R>(u, v, met, ms, out, shape, ndim, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, reverse);             \
+  }                                                                                                                   \
+  int xg_kinetic_energy_##SFX(const R* u, const R* v, R* out, const int64_t* shape, int ndim, int bc_x, R fill_x,     \
+                              int bc_y, R fill_y, void*) {                                                            \
+    const R* const met[4] = {nullptr, nullptr, nullptr, nullptr};                                                     \
+    const int64_t* const ms[4] = {nullptr, nullptr, nullptr, nullptr};                                                \
+    return momentum<R>(true, u, v, met, ms, out, nullptr, shape, ndim, bc_x, fill_x, bc_y, fill_y);                   \
+  }                                                                                                                   \
+  int xg_momentum_advection_##SFX(const R* u, const R* v, const R* cor, const int64_t* cors, const R* rAz,            \
+                                  const int64_t* rAzs, const R* dxC, const int64_t* dxCs, const R* dyC,               \
+                                  const int64_t* dyCs, R* out_u, R* out_v, const int64_t* shape, int ndim, int bc_x,  \
+                                  R fill_x, int bc_y, R fill_y, void*) {                                              \
+    const R* const met[4] = {rAz, cor, dxC, dyC};                                                                     \
+    const int64_t* const ms[4] = {rAzs, cors, dxCs, dyCs};                                                            \
+    return momentum<R>(false, u, v, met, ms, out_u, out_v, shape, ndim, bc_x, fill_x, bc_y, fill_y);                  \
   }                                                                                                                   \
   int xg_laplacian_##SFX(const R* a, const R* dxC, const int64_t* dxCs, const R* dyC, const int64_t* dyCs, const R* dyG, \
                          const int64_t* dyGs, const R* dxG, const int64_t* dxGs, const R* area, const int64_t* as,     \

@@ -1023,6 +1023,299 @@ __global__ __launch_bounds__(BLOCK) void k_wcont(
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// K7g: kinetic energy at the cell centre, 0.5 * (interp(u * u, X) + interp(v * v, Y)), both interpolations left -> center.
+// K7b's shape: SEG rows of u with the value right of the lane's vector (DPP; lane 63 and the edge lane load their own), SEG+1
+// rows of v.  The SQUARES are padded above / right of the last row / column, as the chain pads them: periodic -> the square
+// at index 0, extend -> at n-1, fill -> the fill value itself.  24 B/cell instead of the chain's ~120 (six launches).
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ dv interp_right_of(dv c, real r) {
+  dv o;
+#pragma unroll
+  for (int k = 0; k < NV - 1; ++k) o[k] = (c[k] + c[k + 1]) * real(0.5);
+  o[NV - 1] = (c[NV - 1] + r) * real(0.5);
+  return o;
+}
+__device__ __forceinline__ real interp_right_of(real c, real r) { return (c + r) * real(0.5); }
+
+template <int V, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_kinetic(
+    const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk,
+    int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int bc_x, real fill_x, int bc_y, real fill_y, int ntl) {
+  typedef typename VecT<V>::type T;
+  const u32 pb = (nblk + 7) >> 3;
+  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
+  if (lb >= nblk) return;
+  const u32 w = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
+  const u32 r = fdiv(w, ntile);
+  const u32 tile = w - r * ntile.d;
+  const u32 oo = fdiv(r, nseg);
+  if (oo >= nouter) return;
+  const u32 sg = r - oo * nseg.d;
+  const int64_t o = o0 + oo;
+  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
+  if (i0 >= nx) return;
+  const int64_t j0 = (int64_t)sg * SEG;
+  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  const bool edge = (i0 + V >= nx);
+  const int64_t ridx = edge ? ((bc_x == XG_BC_PERIODIC) ? 0 : nx - 1) : i0 + V;
+  const bool fill_edge = edge && (bc_x == XG_BC_FILL);
+  const bool shl = V > 1 && (ntl & 1);
+  const bool own = !shl || (threadIdx.x & 63) == 63 || edge;
+  const real* pu = u + (o * ny + j0) * nx;
+  const real* pv = v + o * ny * nx + i0;
+  T uu[SEG], vv[SEG + 1];
+  real ur[SEG];
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    const int64_t jr = (s_ < nrow) ? s_ : nrow - 1;
+    uu[s_] = *reinterpret_cast<const T*>(pu + jr * nx + i0);
+    ur[s_] = own ? pu[jr * nx + ridx] : real(0);
+    vv[s_] = *reinterpret_cast<const T*>(pv + (j0 + jr) * nx);
+  }
+  bool ftop = false;
+  {
+    const int64_t q = j0 + nrow;  // the row above the segment's last row
+    const real* src = pv + q * nx;
+    if (q >= ny) {
+      ftop = (bc_y == XG_BC_FILL);
+      src = pv + ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1) * nx;
+    }
+    vv[SEG] = *reinterpret_cast<const T*>(src);
+  }
+  if (shl) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      const real right = from_lane_above(vec_first(uu[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own`)
+      if (!own) ur[s_] = right;
+    }
+  }
+  real* po = out + (o * ny + j0) * nx + i0;
+  const T top = ftop ? splat<T>(fill_y) : vv[SEG] * vv[SEG];
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    if (s_ < nrow) {
+      const real sr = fill_edge ? fill_x : ur[s_] * ur[s_];
+      const T ix = interp_right_of(uu[s_] * uu[s_], sr);
+      const T up = (s_ + 1 < nrow) ? vv[s_ + 1] * vv[s_ + 1] : top;
+      const T iy = op2<XG_OP_INTERP>(vv[s_] * vv[s_], up);
+      stg_s<T, NTS>(po + s_ * nx, splat<T>(real(0.5)) * (ix + iy));
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// K7h: the vector-invariant momentum advection (+ Coriolis) tendencies in ONE pass, two fields in, two out:
+//   zeta = ((v[j,i] - v[j,i-1]) - (u[j,i] - u[j-1,i])) [/ rAz] [+ f]              (Y:left, X:left)    K7
+//   ke   = 0.5 * (interp(u * u, X) + interp(v * v, Y))                             centre              K7g
+//   gu   = interp(zeta, Y) * interp(interp(v, X), Y) - (ke[j,i] - ke[j,i-1]) [/ dxC]         at u's points
+//   gv   = -(interp(zeta, X) * interp(interp(u, Y), X)) - (ke[j,i] - ke[j-1,i]) [/ dyC]      at v's points
+// in the chain's operation order (-ffp-contract=off, the compiler's IEEE quotients).  Per wave-task (SEG rows, one x-tile) a
+// lane holds the patch of u and v it needs: rows j0-1 .. j0+SEG, columns i0-1 .. i0+V -- the columns left and right of its
+// vector from the neighbouring lanes (DPP), lane 0 / lane 63 / the edge lanes load their own.  A periodic axis wraps the
+// patch's indices: every stage's periodic pad is then the stage's own value at the wrapped index.  At an extend / fill
+// boundary the raw patch carries the pads of the FIRST stages (u below row 0, v left of column 0: the clamped index or the
+// fill value) and every later stage overrides its own pad: zeta, the X-mean of v above the last row; zeta, the Y-mean of u
+// right of the last column; u * u right, v * v above; ke below and left -- extend: the stage's value at the clamped index,
+// fill: the fill value itself.  Every intermediate is formed once per lane; the two outputs of a cell share them.
+// 32 B/cell in float64 (coriolis and the three metric planes are 2-D and stay in the L2) instead of ~400 for the 20 launches.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ real vec_at(dv v, int k) { return v[k]; }
+__device__ __forceinline__ real vec_at(real v, int) { return v; }
+__device__ __forceinline__ void vec_set(dv& v, int k, real x) { v[k] = x; }
+__device__ __forceinline__ void vec_set(real& v, int, real x) { v = x; }
+
+template <int V, bool MET, bool COR, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_momadv(
+    const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ out_u, real* __restrict__ out_v, int64_t o0,
+    u32 nouter, u32 nblk, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, ZBand zb, int bc_x, real fill_x, int bc_y,
+    real fill_y, Div2dMet mt, int ntl) {  // mt: rAz, coriolis (Y:l, X:l), dxC (Y:c, X:l), dyC (Y:l, X:c)
+  typedef typename VecT<V>::type T;
+  const u32 pb = (nblk + 7) >> 3;
+  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
+  if (lb >= nblk) return;
+  const u32 w = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
+  const u32 r = fdiv(w, ntile);
+  const u32 tile = w - r * ntile.d;
+  u32 oo, sg;
+  if (zb.on) {  // band-major: the metric rows of a band stay in the XCD's L2 for all outer indices
+    if (!zband_map(zb, r, oo, sg)) return;
+  } else {
+    oo = fdiv(r, nseg);
+    if (oo >= nouter) return;
+    sg = r - oo * nseg.d;
+  }
+  const int64_t o = o0 + oo;
+  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
+  if (i0 >= nx) return;
+  const int64_t j0 = (int64_t)sg * SEG;
+  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  const int64_t base = o * ny * nx;
+  const bool per_x = bc_x == XG_BC_PERIODIC, per_y = bc_y == XG_BC_PERIODIC;
+  const bool edge_l = (i0 == 0), edge_r = (i0 + V >= nx);
+  const bool bot = (j0 == 0);  // patch row -1 lies below the array
+  const int64_t lidx = edge_l ? (per_x ? nx - 1 : 0) : i0 - 1;
+  const int64_t ridx = edge_r ? (per_x ? 0 : nx - 1) : i0 + V;
+  const bool shl = V > 1 && (ntl & 1);
+  const bool own_l = !shl || (threadIdx.x & 63) == 0 || edge_l;
+  const bool own_r = !shl || (threadIdx.x & 63) == 63 || edge_r;
+  // patch row p (0 .. SEG+1) is array row j0 + p - 1, wrapped (periodic) or clamped; rows beyond ny (short tails) repeat
+  // row ny-1 and feed nothing that is stored
+  int64_t rw[SEG + 2];
+#pragma unroll
+  for (int p = 0; p < SEG + 2; ++p) {
+    const int64_t g = j0 + p - 1;
+    rw[p] = g < 0 ? (per_y ? ny - 1 : 0) : (g >= ny ? ((per_y && g == ny) ? 0 : ny - 1) : g);
+  }
+  // U[p][1 + k] / W[p][1 + k]: u / v at patch row p, column i0 + k; [0]: column i0 - 1, [V + 1]: column i0 + V
+  real U[SEG + 2][V + 2], W[SEG + 2][V + 2];
+  {
+    const real* pu = u + base;
+    const real* pv = v + base;
+#pragma unroll
+    for (int p = 0; p < SEG + 2; ++p) {
+      const T tu = *reinterpret_cast<const T*>(pu + rw[p] * nx + i0);
+      const T tv = *reinterpret_cast<const T*>(pv + rw[p] * nx + i0);
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        U[p][1 + k] = vec_at(tu, k);
+        W[p][1 + k] = vec_at(tv, k);
+      }
+      U[p][0] = own_l ? pu[rw[p] * nx + lidx] : real(0);
+      W[p][0] = own_l ? pv[rw[p] * nx + lidx] : real(0);
+      U[p][V + 1] = own_r ? pu[rw[p] * nx + ridx] : real(0);
+      W[p][V + 1] = own_r ? pv[rw[p] * nx + ridx] : real(0);
+    }
+  }
+  // the metric planes at the patch's points (wrapped / clamped like the fields: what a clamped index reads is overridden)
+  real RZ[SEG + 1][V + 1], CF[SEG + 1][V + 1];
+  T DX[SEG], DY[SEG];
+  if (MET || COR) {
+    int64_t mb[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) mb[k] = mt.p[k] ? area_outer_off(mt.ai[k], o) : 0;
+    const bool vec = (ntl & 8) != 0;
+    auto plane = [&](real (&dst)[SEG + 1][V + 1], const real* m, int64_t mbase, int64_t sy, int64_t sx) {
+#pragma unroll
+      for (int p = 0; p < SEG + 1; ++p) {
+        const int64_t off = mbase + rw[p + 1] * sy;
+        const T row = vec ? *reinterpret_cast<const T*>(m + off + i0) : ldm<T>(m, off + i0 * sx, sx);
+#pragma unroll
+        for (int c = 0; c < V; ++c) dst[p][c] = vec_at(row, c);
+        dst[p][V] = m[off + ridx * sx];
+      }
+    };
+    if (MET) plane(RZ, mt.p[0], mb[0], mt.sy[0], mt.sx[0]);
+    if (COR) plane(CF, mt.p[1], mb[1], mt.sy[1], mt.sx[1]);
+    if (MET) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const int64_t ox = mb[2] + rw[s_ + 1] * mt.sy[2], oy = mb[3] + rw[s_ + 1] * mt.sy[3];
+        DX[s_] = vec ? *reinterpret_cast<const T*>(mt.p[2] + ox + i0) : ldm<T>(mt.p[2], ox + i0 * mt.sx[2], mt.sx[2]);
+        DY[s_] = vec ? *reinterpret_cast<const T*>(mt.p[3] + oy + i0) : ldm<T>(mt.p[3], oy + i0 * mt.sx[3], mt.sx[3]);
+      }
+    }
+  }
+  if (shl) {
+#pragma unroll
+    for (int p = 0; p < SEG + 2; ++p) {
+      const real ul = from_lane_below(U[p][V]), wl = from_lane_below(W[p][V]);   // DPP wave_shr:1 (lane 0 is `own_l`)
+      const real ur = from_lane_above(U[p][1]), wr = from_lane_above(W[p][1]);   // DPP wave_shl:1 (lane 63 is `own_r`)
+      if (!own_l) { U[p][0] = ul; W[p][0] = wl; }
+      if (!own_r) { U[p][V + 1] = ur; W[p][V + 1] = wr; }
+    }
+  }
+  // the pads of the first stages at a fill boundary: u below row 0, v left of column 0
+  if (bot && bc_y == XG_BC_FILL) {
+#pragma unroll
+    for (int c = 0; c < V + 2; ++c) U[0][c] = fill_y;
+  }
+  if (edge_l && bc_x == XG_BC_FILL) {
+#pragma unroll
+    for (int p = 0; p < SEG + 2; ++p) W[p][0] = fill_x;
+  }
+  const bool ovr_x_hi = edge_r && !per_x, ovr_x_lo = edge_l && !per_x, ovr_y_lo = bot && !per_y;
+  const bool ext_x = bc_x == XG_BC_EXTEND, ext_y = bc_y == XG_BC_EXTEND;
+  // zeta at rows j0 .. j0+SEG, columns i0 .. i0+V; the X-mean of v at the same rows; the Y-mean of u at the same columns
+  real Z[SEG + 1][V + 1], VX[SEG + 1][V], UY[SEG][V + 1];
+#pragma unroll
+  for (int p = 0; p < SEG + 1; ++p) {
+#pragma unroll
+    for (int c = 0; c < V + 1; ++c) {
+      real z = (W[p + 1][c + 1] - W[p + 1][c]) - (U[p + 1][c + 1] - U[p][c + 1]);
+      if (MET) z = z / RZ[p][c];
+      if (COR) z = z + CF[p][c];
+      Z[p][c] = z;
+      if (c < V) VX[p][c] = (W[p + 1][c] + W[p + 1][c + 1]) * real(0.5);
+      if (p < SEG) UY[p][c] = (U[p][c + 1] + U[p + 1][c + 1]) * real(0.5);
+    }
+    if (ovr_x_hi) {
+      Z[p][V] = ext_x ? Z[p][V - 1] : fill_x;
+      if (p < SEG) UY[p][V] = ext_x ? UY[p][V - 1] : fill_x;
+    }
+    if (p > 0 && j0 + p == ny && !per_y) {  // the row above the last one (wave-uniform)
+#pragma unroll
+      for (int c = 0; c < V + 1; ++c) {
+        Z[p][c] = ext_y ? Z[p - 1][c] : fill_y;
+        if (c < V) VX[p][c] = ext_y ? VX[p - 1][c] : fill_y;
+      }
+    }
+  }
+  // ke at rows j0-1 .. j0+SEG-1, columns i0-1 .. i0+V-1: KE[p][c] is row j0 + p - 1, column i0 + c - 1
+  real KE[SEG + 1][V + 1];
+  {
+    real UU[SEG + 1][V + 2], VV[SEG + 2][V + 1];
+#pragma unroll
+    for (int p = 0; p < SEG + 2; ++p) {
+#pragma unroll
+      for (int c = 0; c < V + 2; ++c) {
+        if (p < SEG + 1) UU[p][c] = U[p][c] * U[p][c];
+        if (c < V + 1) VV[p][c] = W[p][c] * W[p][c];
+      }
+      if (p < SEG + 1 && ovr_x_hi && !ext_x) UU[p][V + 1] = fill_x;
+      if (p > 0 && j0 + p - 1 == ny && bc_y == XG_BC_FILL) {
+#pragma unroll
+        for (int c = 0; c < V + 1; ++c) VV[p][c] = fill_y;
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < SEG + 1; ++p) {
+#pragma unroll
+      for (int c = 0; c < V + 1; ++c)
+        KE[p][c] = real(0.5) * ((UU[p][c] + UU[p][c + 1]) * real(0.5) + (VV[p][c] + VV[p + 1][c]) * real(0.5));
+    }
+  }
+#pragma unroll
+  for (int p = 1; p < SEG + 1; ++p)
+    if (ovr_x_lo) KE[p][0] = ext_x ? KE[p][1] : fill_x;
+  if (ovr_y_lo) {
+#pragma unroll
+    for (int c = 1; c < V + 1; ++c) KE[0][c] = ext_y ? KE[1][c] : fill_y;
+  }
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    if (s_ < nrow) {
+      T gu, gv;
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const real zy = (Z[s_][c] + Z[s_ + 1][c]) * real(0.5);
+        const real vbar = (VX[s_][c] + VX[s_ + 1][c]) * real(0.5);
+        real gx = KE[s_ + 1][c + 1] - KE[s_ + 1][c];
+        if (MET) gx = gx / vec_at(DX[s_], c);
+        vec_set(gu, c, zy * vbar - gx);
+        const real zx = (Z[s_][c] + Z[s_][c + 1]) * real(0.5);
+        const real ubar = (UY[s_][c] + UY[s_][c + 1]) * real(0.5);
+        real gy = KE[s_ + 1][c + 1] - KE[s_][c + 1];
+        if (MET) gy = gy / vec_at(DY[s_], c);
+        vec_set(gv, c, real(-1) * (zx * ubar) - gy);
+      }
+      const int64_t off = base + (j0 + s_) * nx + i0;
+      stg<T, NTS>(out_u + off, gu);  // (two outputs: plain `nt`, as K7c's gradient)
+      stg<T, NTS>(out_v + off, gv);
+    }
+  }
+}
+
 #endif  // !XG_INT
 
 }  // namespace
@@ -1591,6 +1884,127 @@ int XG_FN(xg_vertical_velocity)(const real* u, const real* v, const real* mu, co
     else XG_V(1);
 #undef XG_V
 #undef XG_A
+#undef XG_N
+#undef XG_GO
+  }
+  XG_LAUNCH_CHECK();
+  return XG_OK;
+}
+
+// K7g's launcher
+int XG_FN(xg_kinetic_energy)(const real* u, const real* v, real* out, const int64_t* shape, int ndim, int bc_x, real fill_x,
+                             int bc_y, real fill_y, void* stream) {
+  if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
+  if (bc_x < XG_BC_PERIODIC || bc_x > XG_BC_EXTEND || bc_y < XG_BC_PERIODIC || bc_y > XG_BC_EXTEND)
+    return fail(XG_ERR_INVALID, "kinetic energy needs a periodic, fill or extend boundary on both axes");
+  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
+  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
+  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Y,X) planes");
+  const int V = (aligned16(u) && aligned16(v) && aligned16(out) && nx % NV == 0) ? NV : 1;
+  constexpr int SEG = XG_FUSED_SEG;
+  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
+  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
+  const u64 per_outer = ntile * nseg;
+  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the kinetic energy kernel");
+  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
+  const u64 outer_per = MAX_ITEMS / per_outer;
+  hipStream_t st = (hipStream_t)stream;
+  const bool nts = tune().nt_store;
+  const int vnt = tune().nt_load ? (tune().vec_nt & 1) : 0;  // bit 0: the right neighbour by DPP (K7d)
+  int rc;
+  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_per) {
+    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_per) ? outer - o0 : (int64_t)outer_per);
+    const u64 waves = (u64)nouter * per_outer;
+    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
+    if ((rc = check_grid((u64)nblk + 8))) return rc;
+    const u32 grid = ((nblk + 7) / 8) * 8;
+#define XG_GO(V_, NTS) do { hipLaunchKernelGGL((k_kinetic<V_, NTS, SEG>), dim3(grid), dim3(BLOCK), 0, st, u, v, out, o0, nouter, nblk, ny, nx, fnt, fns, bc_x, fill_x, bc_y, fill_y, vnt); } while (0)
+    if (V > 1) { if (nts) XG_GO(NV, true); else XG_GO(NV, false); }
+    else { if (nts) XG_GO(1, true); else XG_GO(1, false); }
+#undef XG_GO
+  }
+  XG_LAUNCH_CHECK();
+  return XG_OK;
+}
+
+// K7h's launcher: the three metrics all or none; the coriolis plane on its own
+int XG_FN(xg_momentum_advection)(const real* u, const real* v, const real* coriolis, const int64_t* coriolis_strides,
+                                 const real* rAz, const int64_t* rAz_strides, const real* dxC, const int64_t* dxC_strides,
+                                 const real* dyC, const int64_t* dyC_strides, real* out_u, real* out_v,
+                                 const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, void* stream) {
+  if (!u || !v || !out_u || !out_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
+  if (bc_x < XG_BC_PERIODIC || bc_x > XG_BC_EXTEND || bc_y < XG_BC_PERIODIC || bc_y > XG_BC_EXTEND)
+    return fail(XG_ERR_INVALID, "momentum advection needs a periodic, fill or extend boundary on both axes");
+  const int nmet = (rAz != nullptr) + (dxC != nullptr) + (dyC != nullptr);
+  if (nmet != 0 && nmet != 3) return fail(XG_ERR_INVALID, "momentum advection: the three metrics rAz, dxC, dyC, or none");
+  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
+  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
+  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Y,X) planes");
+  int rc;
+  Div2dMet mt;
+  memset(&mt, 0, sizeof(mt));
+  const real* mp[4] = {rAz, coriolis, dxC, dyC};
+  const int64_t* ms[4] = {rAz_strides, coriolis_strides, dxC_strides, dyC_strides};
+  for (int k = 0; k < 4; ++k) {
+    mt.p[k] = mp[k];
+    if ((rc = area_index(mp[k], ms[k], shape, ndim, &mt.ai[k], &mt.sy[k], &mt.sx[k]))) return rc;
+  }
+  const int V = (aligned16(u) && aligned16(v) && aligned16(out_u) && aligned16(out_v) && nx % NV == 0) ? NV : 1;
+  constexpr int SEG = XG_FUSED_SEG;
+  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
+  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
+  const u64 per_outer = ntile * nseg;
+  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the momentum advection kernel");
+  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
+  const u64 outer_per = MAX_ITEMS / per_outer;
+  hipStream_t st = (hipStream_t)stream;
+  const bool nts = tune().nt_store;
+  // bit 0: the lane neighbours by DPP (K7d), bit 3: every plane that is there is an aligned vector in every row
+  int vnt = tune().nt_load ? (tune().vec_nt & 1) : 0;
+  const bool met = nmet != 0, cor = coriolis != nullptr;
+  if (met || cor) {
+    bool mv = V > 1;
+    for (int k = 0; k < 4; ++k)
+      if (mt.p[k]) mv = mv && plane_vec_ok(mt.p[k], mt.ai[k], mt.sy[k], mt.sx[k]);
+    vnt |= mv ? 8 : 0;
+  }
+  // planes shared by every outer index (2-D metrics under a (Z, Y, X) field): band-major order, 8-row bands as the weighted
+  // laplacian's five planes (K7d)
+  bool all_shared = met || cor;
+  for (int k = 0; k < 4; ++k)
+    for (int d = 0; mt.p[k] && d < mt.ai[k].n; ++d)
+      if (mt.ai[k].stride[d] != 0) all_shared = false;
+  const u32 zbr = (u32)(tune().vec_zb_rows > 1 ? tune().vec_zb_rows : 16);
+  const u32 ZB_SEGS = (u32)(((zbr + 1) / 2 + SEG - 1) / SEG);
+  ZBand zb = make_zband(false, 0, 0, 1);
+  u64 outer_step = outer_per;
+  if (all_shared && tune().zband && outer >= 2) {
+    const u64 padded = ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile;
+    if (padded <= MAX_ITEMS) {
+      zb = make_zband(true, (u64)outer, nseg, ZB_SEGS);
+      if (zb.on) outer_step = (u64)outer;
+    }
+  }
+  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_step) {
+    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_step) ? outer - o0 : (int64_t)outer_step);
+    const u64 waves = zb.on ? ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile : (u64)nouter * per_outer;
+    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
+    if ((rc = check_grid((u64)nblk + 8))) return rc;
+    const u32 grid = ((nblk + 7) / 8) * 8;
+#define XG_GO(V_, M_, C_, NTS) do { hipLaunchKernelGGL((k_momadv<V_, M_, C_, NTS, SEG>), dim3(grid), dim3(BLOCK), 0, st, u, v, out_u, out_v, o0, nouter, nblk, ny, nx, fnt, fns, zb, bc_x, fill_x, bc_y, fill_y, mt, vnt); } while (0)
+#define XG_N(V_, M_, C_) do { if (nts) XG_GO(V_, M_, C_, true); else XG_GO(V_, M_, C_, false); } while (0)
+#define XG_C(V_, M_) do { if (cor) XG_N(V_, M_, true); else XG_N(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (met) XG_C(V_, true); else XG_C(V_, false); } while (0)
+    if (V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_C
 #undef XG_N
 #undef XG_GO
   }

@@ -1266,6 +1266,51 @@ def vertical_velocity(u, v, mu, mu2, mv, mv2, area, bc_x: str, bc_y: str, bc_z: 
     return out
 
 
+def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
+    """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
+    squares are padded right of / above the last column / row (fill: the fill value itself)."""
+    lib = _MEM.lib()
+    dt, sfx = _common(u, v)
+    u, v = asdevice(u, dt), asdevice(v, dt)
+    if u.shape != v.shape:
+        raise ValueError("kinetic_energy: u and v must have the same shape")
+    shape = list(u.shape)
+    out = _empty(shape, dtype=dt, device=u.device)
+    if out.numel() == 0:
+        return out
+    _check(
+        getattr(lib, "xg_kinetic_energy_" + sfx)(u.data_ptr(), v.data_ptr(), out.data_ptr(), _hip.i64(shape), len(shape),
+                                                 _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y), _stream())
+    )
+    return out
+
+
+def momentum_advection(u, v, coriolis, rAz, dxC, dyC, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0):
+    """Fused vector-invariant momentum advection (+ Coriolis) in one pass (xg_momentum_advection_f64): (gu, gv) with
+    gu = interp(zeta, Y) * interp(interp(v, X), Y) - d ke / dx, gv = -(interp(zeta, X) * interp(interp(u, Y), X)) - d ke / dy,
+    zeta = vorticity(u, v) / rAz + coriolis.  rAz, dxC, dyC all given or all None; `coriolis` None = no Coriolis term."""
+    lib = _MEM.lib()
+    dt, sfx = _common(u, v, coriolis, rAz, dxC, dyC)
+    u, v = asdevice(u, dt), asdevice(v, dt)
+    if u.shape != v.shape:
+        raise ValueError("momentum_advection: u and v must have the same shape")
+    shape = list(u.shape)
+    out_u = _empty(shape, dtype=dt, device=u.device)
+    out_v = _empty(shape, dtype=dt, device=u.device)
+    if out_u.numel() == 0:
+        return out_u, out_v
+    mets = [_prep_metric(m, dt) for m in (coriolis, rAz, dxC, dyC)]
+    margs = []
+    for m, what in zip(mets, ("coriolis", "rAz", "dxC", "dyC")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
+    _check(
+        getattr(lib, "xg_momentum_advection_" + sfx)(u.data_ptr(), v.data_ptr(), *margs, out_u.data_ptr(),
+                                                     out_v.data_ptr(), _hip.i64(shape), len(shape), _hip.BC[bc_x],
+                                                     float(fill_x), _hip.BC[bc_y], float(fill_y), _stream())
+    )
+    return out_u, out_v
+
+
 def laplacian(a, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, dxC=None, dyC=None, dyG=None,
               dxG=None, area=None) -> torch.Tensor:
     """Fused finite-volume del2 in one pass (xg_laplacian_f64): Fx = (a - a[x-1]) / dxC * dyG, Fy = (a - a[y-1]) / dyC

@@ -1574,6 +1574,143 @@ class Grid:
         res = res._replace(data=_dev.tohost(out) if host else out)
         return to_xarray(res) if was_xr else res
 
+    # ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---------------------
+    def _c_grid_vector(self, u, v, x_axis, y_axis, what):
+        """dims of a C-grid vector's points: (lead, at u, at v, centre, vorticity point); raises when u / v sit elsewhere"""
+        xa, ya = self.axes[x_axis], self.axes[y_axis]
+        (ux_pos, ux_dim), (uy_pos, uy_dim) = xa._get_position_name(u), ya._get_position_name(u)
+        (vx_pos, vx_dim), (vy_pos, vy_dim) = xa._get_position_name(v), ya._get_position_name(v)
+        if ((ux_pos, uy_pos, vx_pos, vy_pos) != ("left", "center", "center", "left")
+                or "left" not in xa.coords or "left" not in ya.coords):
+            raise NotImplementedError(f"fused {what} needs u at (Y:center, X:left) and v at (Y:left, X:center)")
+        lead = u.dims[:-2]
+        return lead, lead + (uy_dim, ux_dim), lead + (vy_dim, vx_dim), lead + (uy_dim, vx_dim), lead + (vy_dim, ux_dim)
+
+    def _labels_of_step(self, src, dims, out_dim):
+        """placeholder with the dims, coords and name a one-axis operator gives its result (gridops.HipGridUFunc)"""
+        return _reattach_coords([DataArray(_placeholder(src.shape), dims, name=src.name)], self, None, {out_dim}, [src])[0]
+
+    @staticmethod
+    def _labels_of_binary(a, b):
+        """placeholder with the coords and name of `a OP b` for two arrays of the same dims"""
+        return DataArray(_placeholder(a.shape), a.dims, coords=_binary_coords(a, b, a.dims), name=_result_name(a, b))
+
+    def _labels_of_ke(self, u, v, c_dims):
+        """dims, coords and name of 0.5 * (interp(u * u, X) + interp(v * v, Y)), step by step over placeholders"""
+        ix = self._labels_of_step(self._labels_of_binary(u, u), c_dims, c_dims[-1])
+        iy = self._labels_of_step(self._labels_of_binary(v, v), c_dims, c_dims[-2])
+        return self._labels_of_binary(ix, iy)  # (the scaling by 0.5 changes neither coords nor name)
+
+    def kinetic_energy(self, u, v, x_axis: str = "X", y_axis: str = "Y", padding=None, fill_value=None):
+        """Kinetic energy of a C-grid velocity at the cell centre in ONE pass: u and v are read once, the result written
+        once (24 B/cell in float64 instead of about 120 for the six launches of the chain).
+
+        u at (Y:center, X:left), v at (Y:left, X:center).  Bit-identical, coords and name included, to the chain
+
+            kw = dict(padding=padding, fill_value=fill_value)
+            ke = 0.5 * (grid.interp(u * u, x_axis, **kw) + grid.interp(v * v, y_axis, **kw))
+
+        Both interpolations go left -> center, so each SQUARE is padded right of / above the last cell (periodic: the
+        square at index 0, extend: at n-1, fill: `fill_value` itself, not its square).  That chain itself runs (the same
+        calls in the same order) for integer, float16 or mixed dtypes, for (Y, X) not last or fields of different shapes,
+        for chunked host arrays, and on grids with face connections or a fold along either axis."""
+        args = (u, v)
+        (u, xr1), (v, xr2) = self._wrap_in(u), self._wrap_in(v)
+        was_xr = xr1 or xr2
+        lead, u_dims, v_dims, c_dims, z_dims = self._c_grid_vector(u, v, x_axis, y_axis, "kinetic energy")
+        plan = None
+        if u.dims == u_dims and v.dims == v_dims:
+            plan = self._second_order_plan([u, v], x_axis, y_axis, padding, fill_value)
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            return 0.5 * (self.interp(args[0] * args[0], x_axis, **kw) + self.interp(args[1] * args[1], y_axis, **kw))
+        bcx, bcy, fvx, fvy = plan
+        host = not (_is_tensor(u.data) or _is_tensor(v.data))
+        out = _dev.kinetic_energy(u.data, v.data, bcx, bcy, fvx, fvy)
+        res = self._labels_of_ke(u, v, c_dims)._replace(data=_dev.tohost(out) if host else out)
+        return to_xarray(res) if was_xr else res
+
+    def momentum_advection(self, u, v, coriolis=None, x_axis: str = "X", y_axis: str = "Y", padding=None, fill_value=None,
+                           metric_weighted: bool = True):
+        """Vector-invariant horizontal momentum advection, plus the Coriolis term when `coriolis` (f at the vorticity
+        point, (Y:left, X:left)) is given, in ONE pass: u and v are read once and the two tendencies written once (32 B/cell
+        in float64 instead of about 400 for the twenty launches of the chain).  Returns `(gu, gv)`, gu at u's points,
+        gv at v's.
+
+        u at (Y:center, X:left), v at (Y:left, X:center).  Bit-identical, coords and names included, to the chain
+
+            kw = dict(padding=padding, fill_value=fill_value)
+            zeta = grid.vorticity(u, v, x_axis, y_axis, metric_weighted=metric_weighted, **kw)   # (Y:left, X:left)
+            if coriolis is not None:
+                zeta = zeta + coriolis
+            ke = 0.5 * (grid.interp(u * u, x_axis, **kw) + grid.interp(v * v, y_axis, **kw))     # centre
+            vbar = grid.interp(grid.interp(v, x_axis, **kw), y_axis, **kw)                       # v at u's points
+            ubar = grid.interp(grid.interp(u, y_axis, **kw), x_axis, **kw)                       # u at v's points
+            gx, gy = grid.gradient(ke, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+            gu = grid.interp(zeta, y_axis, **kw) * vbar - gx
+            gv = -(grid.interp(zeta, x_axis, **kw) * ubar) - gy
+
+        Every stage pads with its axis's own boundary and fill value on the side the chain pads it: u below and v left of
+        the first cell (vorticity and the first means), zeta and those means above / right of the last one, the squares
+        above / right, ke below / left -- periodic: the stage's own value at the wrapped index, extend: at the clamped
+        index, fill: `fill_value` itself (a filled zeta is `fill_value`, not `fill_value + coriolis`).  With
+        `metric_weighted` zeta is divided by the (X, Y) metric at the vorticity point and the gradient by the X / Y
+        metrics at u's / v's points.  That chain itself runs (the same calls in the same order) for integer, float16 or
+        mixed dtypes (`coriolis` and the metrics included), for (Y, X) not last or fields of different shapes, for a
+        `coriolis` or a metric with dims the result lacks, for chunked host arrays, and on grids with face connections or
+        a fold along either axis."""
+        args = (u, v, coriolis)
+        (u, xr1), (v, xr2), (cor, xr3) = self._wrap_in(u), self._wrap_in(v), self._wrap_in(coriolis)
+        was_xr = xr1 or xr2 or xr3
+        lead, u_dims, v_dims, c_dims, z_dims = self._c_grid_vector(u, v, x_axis, y_axis, "momentum advection")
+        plan = None
+        mets = {}
+        if u.dims == u_dims and v.dims == v_dims and (cor is None or isinstance(cor, DataArray)):
+            try:
+                if metric_weighted:
+                    for key, dims, axes in (("rAz", z_dims, (x_axis, y_axis)), ("dxC", u_dims, (x_axis,)),
+                                            ("dyC", v_dims, (y_axis,))):
+                        mets[key] = (self._resident(self.get_metric(_DimsOnly(dims), axes), u.data), dims)
+            except (KeyError, ValueError):
+                mets = None  # (the chain raises it where the chain looks the metric up)
+            if mets is not None:
+                if cor is not None:
+                    mets["coriolis"] = (self._resident(cor, u.data), z_dims)
+                if all(set(m.dims) <= set(dims) and not _is_chunked(m.data) for m, dims in mets.values()):
+                    plan = self._second_order_plan([u, v], x_axis, y_axis, padding, fill_value, [m for m, _ in mets.values()])
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            u, v, coriolis = args
+            zeta = self.vorticity(u, v, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+            if coriolis is not None:
+                zeta = zeta + coriolis
+            ke = 0.5 * (self.interp(u * u, x_axis, **kw) + self.interp(v * v, y_axis, **kw))
+            vbar = self.interp(self.interp(v, x_axis, **kw), y_axis, **kw)
+            ubar = self.interp(self.interp(u, y_axis, **kw), x_axis, **kw)
+            gx, gy = self.gradient(ke, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+            gu = self.interp(zeta, y_axis, **kw) * vbar - gx
+            gv = -(self.interp(zeta, x_axis, **kw) * ubar) - gy
+            return gu, gv
+        bcx, bcy, fvx, fvy = plan
+        host = not (_is_tensor(u.data) or _is_tensor(v.data))
+        views = {k: _aligned_view(m, dims) for k, (m, dims) in mets.items()}
+        ou, ov = _dev.momentum_advection(u.data, v.data, views.get("coriolis"), views.get("rAz"), views.get("dxC"),
+                                         views.get("dyC"), bcx, bcy, fvx, fvy)
+        # dims, coords and names as the chain's, step by step over placeholders
+        xl, yl, xc, yc = u_dims[-1], v_dims[-2], v_dims[-1], u_dims[-2]
+        zeta = _reattach_coords([DataArray(_placeholder(u.shape), z_dims)], self, None, {xl, yl}, [u, v])[0]
+        if cor is not None:
+            zeta = self._labels_of_binary(zeta, mets["coriolis"][0])
+        ke = self._labels_of_ke(u, v, c_dims)
+        vbar = self._labels_of_step(self._labels_of_step(v, z_dims, xl), u_dims, yc)
+        ubar = self._labels_of_step(self._labels_of_step(u, z_dims, yl), v_dims, xc)
+        gx, gy = self._labels_of_step(ke, u_dims, xl), self._labels_of_step(ke, v_dims, yl)
+        gu = self._labels_of_binary(self._labels_of_binary(self._labels_of_step(zeta, u_dims, yc), vbar), gx)
+        gv = self._labels_of_binary(self._labels_of_binary(self._labels_of_step(zeta, v_dims, xc), ubar), gy)
+        gu = gu._replace(data=_dev.tohost(ou) if host else ou)
+        gv = gv._replace(data=_dev.tohost(ov) if host else ov)
+        return (to_xarray(gu), to_xarray(gv)) if was_xr else (gu, gv)
+
     def transform(self, da, axis, target, **kwargs):
         """Convert `da` to new 1-D coordinates along `axis` (linear / log / conservative; reference
         grid.py:1687-1777 -> transform.py:284-514), one HIP kernel launch per call."""
