@@ -73,6 +73,27 @@ def _battery(D, dtype):
     calls["flux"] = (lambda: D.flux(u, v, u, "periodic", "extend"), True)
     calls["i2"] = (lambda: D.stencil2d("interp", u, 0, (1, 0), "periodic", 0.0, (1, 0), "extend", 0.0), True)
     calls["i2mw"] = (lambda: D.stencil2d("interp", u, 0, (1, 0), "periodic", 0.0, (1, 0), "extend", 0.0, (area[0], area[0], area[0])), True)
+    # the one-pass operators K7d - K7h: level-shared (1, Y, X) planes (band-major work order under the defaults), metrics of
+    # the fields' own shape (the plain order), and the 3-D entries; inputs uploaded once
+    dev = lambda x: D.asdevice(x)  # noqa: E731
+    du, dv = dev(u), dev(v)
+    shared = [dev(m((1, 64, 256), 20 + k)) for k in range(5)]
+    full = [dev(m((6, 64, 256), 30 + k)) for k in range(5)]
+    for tag, (m0, m1, m2, m3, m4) in (("", shared), ("u", full)):   # "u": unshared metrics
+        cor = dev(f(tuple(m0.shape), 40) * dtype(3.0))
+        calls["fdiv" + tag] = (lambda m4=m4: D.flux_divergence(du, dv, du, m4, "periodic", "extend", 1.5, -0.5), True)
+        calls["lap" + tag] = (lambda m0=m0, m1=m1, m2=m2, m3=m3, m4=m4: D.laplacian(du, "fill", "periodic", 1.5, -0.5, m0, m1, m2, m3, m4), True)
+        calls["lapa" + tag] = (lambda m4=m4: D.laplacian(du, "extend", "fill", 1.5, -0.5, area=m4), True)
+        calls["madv" + tag] = (lambda cor=cor, m0=m0, m1=m1, m2=m2: D.momentum_advection(du, dv, cor, m0, m1, m2, "periodic", "fill", 1.5, -0.5), True)
+    calls["madv0"] = (lambda: D.momentum_advection(du, dv, None, None, None, None, "extend", "periodic"), True)
+    calls["ke"] = (lambda: D.kinetic_energy(du, dv, "fill", "extend", 1.5, -0.5), True)
+    u3, v3, w3, t3 = (dev(f((2, 6, 64, 256), 50 + k)) for k in range(4))
+    vol, vol2, mu, mv, ar3 = (dev(m((1, 6, 64, 256), 60 + k)) for k in range(5))
+    drf, ra = dev(m((1, 6, 1, 1), 66)), dev(m((1, 1, 64, 256), 67))
+    calls["fdiv3"] = (lambda: D.flux_divergence_3d(u3, v3, w3, t3, vol, vol2, "periodic", "extend", "fill", 1.5, -0.5, 0.25), True)
+    calls["fdiv3p"] = (lambda: D.flux_divergence_3d(u3, v3, w3, t3, ra, drf, "fill", "periodic", "extend", 1.5, -0.5, 0.25), True)
+    calls["wcont"] = (lambda: D.vertical_velocity(u3, v3, mu, drf, mv, drf, ar3, "periodic", "extend", "fill", 1.5, -0.5, 0.25), True)
+    calls["wcontr"] = (lambda: D.vertical_velocity(u3, v3, ra, drf, ra, drf, ra, "extend", "fill", "periodic", 1.5, -0.5, 0.25, True), True)
     phi = f((20, 24, 128), 11)
     theta = np.cumsum(R.synthetic_field((20, 24, 128), 12).astype(dtype) + dtype(0.55), axis=0)
     theta_o = np.cumsum(R.synthetic_field((21, 24, 128), 13).astype(dtype) + dtype(0.55), axis=0)
