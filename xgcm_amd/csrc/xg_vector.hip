@@ -1,6 +1,8 @@
 // xg_vector.hip -- fused two-component operators (vorticity K7, divergence K7b, gradient / flux K7c) and the broadcasting binary op
 // Part of libxgcm_hip.so; compiled twice (real = double / -DXG_F32), see xg_common.hpp.
 
+#include <initializer_list>
+
 #include "xg_common.hpp"
 
 // rows of Y per wave-task of the fused two-component kernels (see STENCIL_SEG in xg_stencil.hip): A/B on one GPU
@@ -157,6 +159,64 @@ __device__ __forceinline__ real vec_last(real v) { return v; }
 __device__ __forceinline__ real vec_first(dv v) { return v[0]; }
 __device__ __forceinline__ real vec_first(real v) { return v; }
 
+// The wave-task every fused kernel starts from: blocks in XCD-banded order, WPB waves per block, the wave id (on the scalar
+// unit: readfirstlane) peeled into (x-tile, outer index of this launch, Y segment) -- segment-major inside an outer index, or
+// band-major (`BANDED`; a literal false where the kernel has no bands, and the branch is gone): a band of segments stays in
+// the XCD's L2 for all outer indices.  Declares `oo` (outer index inside the launch; ZK levels per task: K7 / K7b), `sg`,
+// `o` = o0 + oo, and the lane's V columns from `i0` in SEG rows from `j0` (`nrow` of them exist); returns from the kernel,
+// before its first load, for a wave or a lane without work.  Reads the kernel's parameters nblk, ntile, nseg, nouter, o0,
+// ny, nx by name.  A macro and not a function: to a function the FastDiv / ZBand kernel arguments go as copies made at the
+// call, which moves their loads in front of the first return and changed the registers of K7d, K7e, K7f and K7h (up to +2
+// VGPRs, one K7e instance from 3 to 2 waves per SIMD); expanded in place, every kernel compiles to the code it had.
+#define XG_WAVE_TASK(V_, SEG_, BANDED, ZB, ZK_)                                          \
+  const u32 pb_ = (nblk + 7) >> 3;                                                       \
+  const u32 lb_ = (blockIdx.x & 7) * pb_ + (blockIdx.x >> 3);                            \
+  if (lb_ >= nblk) return;                                                               \
+  const u32 w_ = __builtin_amdgcn_readfirstlane(lb_ * WPB + (threadIdx.x >> 6));         \
+  const u32 r_ = fdiv(w_, ntile);                                                        \
+  const u32 tile_ = w_ - r_ * ntile.d;                                                   \
+  u32 oo, sg;                                                                            \
+  if (BANDED) {                                                                          \
+    if (!zband_map(ZB, r_, oo, sg)) return;                                              \
+    oo *= ZK_;                                                                           \
+  } else {                                                                               \
+    oo = fdiv(r_, nseg);                                                                 \
+    if (oo >= nouter) return;                                                            \
+    sg = r_ - oo * nseg.d;                                                               \
+  }                                                                                      \
+  const int64_t o = o0 + oo;                                                             \
+  const int64_t i0 = ((int64_t)tile_ * WAVE + (threadIdx.x & 63)) * V_;                  \
+  if (i0 >= nx) return;                                                                  \
+  const int64_t j0 = (int64_t)sg * SEG_;                                                 \
+  const int64_t nrow = (ny - j0 < SEG_) ? ny - j0 : SEG_
+
+// The X neighbours of a lane's vector where they come from the lanes beside it (`ntl` bit 0 with vector lanes: DPP after the
+// loads, K7c's scheme): `lidx` / `ridx` are the columns left / right of the vector, wrapped at a periodic edge and clamped
+// (0, nx - 1) at any other, so both are always inside the row; `own_l` / `own_r`: the lane loads that neighbour itself (no
+// shuffle, the tile's first / last lane, the row's edge); `form_r`: it also forms the staggered value right of it itself --
+// not at an extend / fill right edge, where the pad replaces that value.  K7e reads column `ridx` under `form_r` only, so the
+// clamped form that K7g needs (it reads it under `own_r`: the extend pad) serves both.  K7d, K7f and K7h keep these lines
+// written out (K7d's and K7f's with 0 for the unread clamped `ridx`): through this helper some of their instances came out
+// with other VGPR counts (K7d -1, K7f -2, K7h -2 .. +3; occupancy as before), whichever `ridx` form it had.
+struct LaneEdges {
+  bool edge_l, edge_r, shl, own_l, own_r, form_r;
+  int64_t lidx, ridx;
+};
+template <int V>
+__device__ __forceinline__ LaneEdges lane_edges(int64_t i0, int64_t nx, int bc_x, int ntl) {
+  LaneEdges e;
+  const bool per = bc_x == XG_BC_PERIODIC;
+  e.edge_l = (i0 == 0);
+  e.edge_r = (i0 + V >= nx);
+  e.lidx = e.edge_l ? (per ? nx - 1 : 0) : i0 - 1;
+  e.ridx = e.edge_r ? (per ? 0 : nx - 1) : i0 + V;
+  e.shl = V > 1 && (ntl & 1);
+  e.own_l = !e.shl || (threadIdx.x & 63) == 0 || e.edge_l;
+  e.own_r = !e.shl || (threadIdx.x & 63) == 63 || e.edge_r;
+  e.form_r = e.own_r && !(e.edge_r && !per);
+  return e;
+}
+
 template <int V, bool HAS_AREA, bool NTS, int SEG, int ZK = 1>
 __global__ __launch_bounds__(BLOCK) void k_vorticity(
     const real* __restrict__ u, const real* __restrict__ v, const real* __restrict__ area,
@@ -164,28 +224,9 @@ __global__ __launch_bounds__(BLOCK) void k_vorticity(
     FastDiv nseg, ZBand zb, int bc_x, real fill_x, int bc_y, real fill_y, AreaIdx ai, int64_t a_sy,
     int64_t a_sx, const real* __restrict__ halo_x, const real* __restrict__ halo_y, int ntl) {
   typedef typename VecT<V>::type T;
-  const u32 pb = (nblk + 7) >> 3;
-  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
-  if (lb >= nblk) return;
-  const u32 w = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
-  const u32 r = fdiv(w, ntile);
-  const u32 tile = w - r * ntile.d;
-  u32 oo, sg;
-  if (HAS_AREA && zb.on) {  // band-major: a (Y,X) area band stays in the XCD's L2 for all levels
-    if (!zband_map(zb, r, oo, sg)) return;
-    oo *= ZK;
-  } else {
-    oo = fdiv(r, nseg);
-    if (oo >= nouter) return;
-    sg = r - oo * nseg.d;
-  }
+  XG_WAVE_TASK(V, SEG, HAS_AREA && zb.on, zb, ZK);  // (band-major: a (Y,X) area band stays in the XCD's L2 for all levels)
   const int nk = (ZK > 1 && (int64_t)nouter - (int64_t)oo < ZK) ? (int)(nouter - oo) : ZK;
-  const int64_t o = o0 + oo;
   const int64_t a_base = HAS_AREA ? area_outer_off(ai, o) : 0;
-  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
-  if (i0 >= nx) return;
-  const int64_t j0 = (int64_t)sg * SEG;
-  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
   const bool edge = (i0 == 0);
   const int64_t nidx = edge ? ((bc_x == XG_BC_PERIODIC) ? nx - 1 : 0) : i0 - 1;
   const bool fill_edge = edge && (bc_x == XG_BC_FILL);
@@ -273,28 +314,9 @@ __global__ __launch_bounds__(BLOCK) void k_divergence(
     FastDiv nseg, ZBand zb, int bc_x, real fill_x, int bc_y, real fill_y, AreaIdx ai, int64_t a_sy,
     int64_t a_sx, const real* __restrict__ halo_x, const real* __restrict__ halo_y, int ntl) {
   typedef typename VecT<V>::type T;
-  const u32 pb = (nblk + 7) >> 3;
-  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
-  if (lb >= nblk) return;
-  const u32 w = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
-  const u32 r = fdiv(w, ntile);
-  const u32 tile = w - r * ntile.d;
-  u32 oo, sg;
-  if (HAS_AREA && zb.on) {
-    if (!zband_map(zb, r, oo, sg)) return;
-    oo *= ZK;
-  } else {
-    oo = fdiv(r, nseg);
-    if (oo >= nouter) return;
-    sg = r - oo * nseg.d;
-  }
+  XG_WAVE_TASK(V, SEG, HAS_AREA && zb.on, zb, ZK);
   const int nk = (ZK > 1 && (int64_t)nouter - (int64_t)oo < ZK) ? (int)(nouter - oo) : ZK;
-  const int64_t o = o0 + oo;
   const int64_t a_base = HAS_AREA ? area_outer_off(ai, o) : 0;
-  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
-  if (i0 >= nx) return;
-  const int64_t j0 = (int64_t)sg * SEG;
-  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
   const bool edge = (i0 + V >= nx);
   const int64_t ridx = edge ? ((bc_x == XG_BC_PERIODIC) ? 0 : nx - 1) : i0 + V;
   const bool fill_edge = edge && (bc_x == XG_BC_FILL);
@@ -360,25 +382,7 @@ __global__ __launch_bounds__(BLOCK) void k_pair2d(
     int64_t mx_sx, const real* __restrict__ my, AreaIdx aiy, int64_t my_sy, int64_t my_sx,
     const real* __restrict__ halo_x, const real* __restrict__ halo_y, ZBand zb, int ntl) {
   typedef typename VecT<V>::type T;
-  const u32 pb = (nblk + 7) >> 3;
-  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
-  if (lb >= nblk) return;
-  const u32 w = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
-  const u32 r = fdiv(w, ntile);
-  const u32 tile = w - r * ntile.d;
-  u32 oo, sg;
-  if (zb.on) {  // band-major: the metric rows of a band of segments stay in the XCD's L2 for all outer indices (rule 4)
-    if (!zband_map(zb, r, oo, sg)) return;
-  } else {
-    oo = fdiv(r, nseg);
-    if (oo >= nouter) return;
-    sg = r - oo * nseg.d;
-  }
-  const int64_t o = o0 + oo;
-  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
-  if (i0 >= nx) return;
-  const int64_t j0 = (int64_t)sg * SEG;
-  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  XG_WAVE_TASK(V, SEG, zb.on, zb, 1);  // (band-major: the metric rows of a band of segments stay in the XCD's L2 for all outer indices, rule 4)
   const int64_t base = o * ny * nx;
   const real* pa = a + base + i0;
   const bool edge = (i0 == 0);
@@ -489,25 +493,7 @@ __global__ __launch_bounds__(BLOCK) void k_div2d(
     real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg,
     ZBand zb, int bc_x, real fill_x, int bc_y, real fill_y, AreaIdx ai, int64_t a_sy, int64_t a_sx, Div2dMet mt, int ntl) {
   typedef typename VecT<V>::type T;
-  const u32 pb = (nblk + 7) >> 3;
-  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
-  if (lb >= nblk) return;
-  const u32 w = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
-  const u32 r = fdiv(w, ntile);
-  const u32 tile = w - r * ntile.d;
-  u32 oo, sg;
-  if (zb.on) {  // band-major: the area / metric rows of a band stay in the XCD's L2 for all outer indices
-    if (!zband_map(zb, r, oo, sg)) return;
-  } else {
-    oo = fdiv(r, nseg);
-    if (oo >= nouter) return;
-    sg = r - oo * nseg.d;
-  }
-  const int64_t o = o0 + oo;
-  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
-  if (i0 >= nx) return;
-  const int64_t j0 = (int64_t)sg * SEG;
-  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  XG_WAVE_TASK(V, SEG, zb.on, zb, 1);  // (band-major: the area / metric rows of a band stay in the XCD's L2 for all outer indices)
   const int64_t base = o * ny * nx;
   const real* pt = t + base;
   const bool met = MODE == 0 && mt.p[0] != nullptr;
@@ -666,30 +652,11 @@ __global__ __launch_bounds__(BLOCK) void k_div3d(
     real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile,
     FastDiv nseg, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx va, VolIdx vb, int ntl) {
   typedef typename VecT<V>::type T;
-  const u32 pb = (nblk + 7) >> 3;
-  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
-  if (lb >= nblk) return;
-  const u32 wv = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
-  const u32 r = fdiv(wv, ntile);
-  const u32 tile = wv - r * ntile.d;
-  const u32 oo = fdiv(r, nseg);
-  if (oo >= nouter) return;
-  const u32 sg = r - oo * nseg.d;
-  const int64_t o = o0 + oo;
-  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
-  if (i0 >= nx) return;
-  const int64_t j0 = (int64_t)sg * SEG;
-  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
   const int64_t plane = ny * nx;
   const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
   // X and Y exactly as K7d: T left of the lane, the column whose Fx lies right of it, the rows below / above the segment
-  const bool edge_l = (i0 == 0), edge_r = (i0 + V >= nx);
-  const int64_t lidx = edge_l ? ((bc_x == XG_BC_PERIODIC) ? nx - 1 : 0) : i0 - 1;
-  const int64_t ridx = edge_r ? 0 : i0 + V;
-  const bool shl = V > 1 && (ntl & 1);
-  const bool own_l = !shl || (threadIdx.x & 63) == 0 || edge_l;
-  const bool own_r = !shl || (threadIdx.x & 63) == 63 || edge_r;
-  const bool form_r = own_r && !(edge_r && bc_x != XG_BC_PERIODIC);
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);
   const int64_t q = j0 + nrow;
   const bool top_edge = q >= ny;
   const int64_t rq = (top_edge ? 0 : q) * nx;
@@ -752,37 +719,37 @@ __global__ __launch_bounds__(BLOCK) void k_div3d(
     for (int s_ = 0; s_ < SEG; ++s_) {
       uu[s_] = *reinterpret_cast<const T*>(u + lv + ro[s_] + i0);
       vv[s_] = *reinterpret_cast<const T*>(v + lv + ro[s_] + i0);
-      tl[s_] = own_l ? pt[ro[s_] + lidx] : real(0);
-      tr[s_] = form_r ? pt[ro[s_] + ridx] : real(0);
-      urt[s_] = form_r ? u[lv + ro[s_] + ridx] : real(0);
+      tl[s_] = e.own_l ? pt[ro[s_] + e.lidx] : real(0);
+      tr[s_] = e.form_r ? pt[ro[s_] + e.ridx] : real(0);
+      urt[s_] = e.form_r ? u[lv + ro[s_] + e.ridx] : real(0);
     }
     const T vtop = *reinterpret_cast<const T*>(v + lv + rq + i0);
     if (NVOL >= 1 && k > 0 && va.sz != 0)
       load_rows<T, SEG>(fa, va.p, vao + k * va.sz, va.sy, va.sx, nrow, (ntl & 4) != 0);
     if (NVOL >= 2 && k > 0 && vb.sz != 0)
       load_rows<T, SEG>(fb, vb.p, vbo + k * vb.sz, vb.sy, vb.sx, nrow, (ntl & 8) != 0);
-    if (shl) {
+    if (e.shl) {
 #pragma unroll
       for (int s_ = 0; s_ < SEG; ++s_) {
         const real left = from_lane_below(vec_last(tc[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
-        if (!own_l) tl[s_] = left;
+        if (!e.own_l) tl[s_] = left;
       }
     }
     T fx[SEG], fy[SEG];
     real fxr[SEG];
 #pragma unroll
     for (int s_ = 0; s_ < SEG; ++s_) {
-      const real left = (edge_l && bc_x == XG_BC_FILL) ? fill_x : tl[s_];
+      const real left = (e.edge_l && bc_x == XG_BC_FILL) ? fill_x : tl[s_];
       fx[s_] = uu[s_] * interp_left_of(tc[s_], left);
       fy[s_] = vv[s_] * op2<XG_OP_INTERP>(s_ == 0 ? tb : tc[s_ - 1], tc[s_]);
       fxr[s_] = urt[s_] * interp_left_of(tr[s_], vec_last(tc[s_]));
     }
     const T fytop = vtop * op2<XG_OP_INTERP>(tc[SEG - 1], ttop);
-    if (shl) {
+    if (e.shl) {
 #pragma unroll
       for (int s_ = 0; s_ < SEG; ++s_) {
         const real right = from_lane_above(vec_first(fx[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
-        if (!own_r) fxr[s_] = right;
+        if (!e.own_r) fxr[s_] = right;
       }
     }
     T fzn[SEG];
@@ -796,8 +763,8 @@ __global__ __launch_bounds__(BLOCK) void k_div3d(
     for (int s_ = 0; s_ < SEG; ++s_) {
       if (s_ < nrow) {
         real right = fxr[s_];
-        if (edge_r && bc_x == XG_BC_FILL) right = fill_x;
-        else if (edge_r && bc_x == XG_BC_EXTEND) right = vec_last(fx[s_]);
+        if (e.edge_r && bc_x == XG_BC_FILL) right = fill_x;
+        else if (e.edge_r && bc_x == XG_BC_EXTEND) right = vec_last(fx[s_]);
         T up = (s_ + 1 < nrow) ? fy[s_ + 1] : fytop;
         if (s_ + 1 >= nrow && !top_own) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : fy[s_];
         const T h = dudx_fwd(fx[s_], right) + (up - fy[s_]);
@@ -850,20 +817,7 @@ __global__ __launch_bounds__(BLOCK) void k_wcont(
     real fill_z, int reverse, VolIdx ua, VolIdx ub, VolIdx va, VolIdx vb, VolIdx ar, int ntl) {
   typedef typename VecT<V>::type T;
   typedef WcLevel<T, SEG> L;
-  const u32 pb = (nblk + 7) >> 3;
-  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
-  if (lb >= nblk) return;
-  const u32 wv = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
-  const u32 r = fdiv(wv, ntile);
-  const u32 tile = wv - r * ntile.d;
-  const u32 oo = fdiv(r, nseg);
-  if (oo >= nouter) return;
-  const u32 sg = r - oo * nseg.d;
-  const int64_t o = o0 + oo;
-  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
-  if (i0 >= nx) return;
-  const int64_t j0 = (int64_t)sg * SEG;
-  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
   const int64_t plane = ny * nx;
   const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
   // X as K7e: the element right of the lane's vector comes from the lane above (DPP) or, for the tile's last lane and the
@@ -1043,25 +997,9 @@ __global__ __launch_bounds__(BLOCK) void k_kinetic(
     const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk,
     int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int bc_x, real fill_x, int bc_y, real fill_y, int ntl) {
   typedef typename VecT<V>::type T;
-  const u32 pb = (nblk + 7) >> 3;
-  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
-  if (lb >= nblk) return;
-  const u32 w = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
-  const u32 r = fdiv(w, ntile);
-  const u32 tile = w - r * ntile.d;
-  const u32 oo = fdiv(r, nseg);
-  if (oo >= nouter) return;
-  const u32 sg = r - oo * nseg.d;
-  const int64_t o = o0 + oo;
-  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
-  if (i0 >= nx) return;
-  const int64_t j0 = (int64_t)sg * SEG;
-  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
-  const bool edge = (i0 + V >= nx);
-  const int64_t ridx = edge ? ((bc_x == XG_BC_PERIODIC) ? 0 : nx - 1) : i0 + V;
-  const bool fill_edge = edge && (bc_x == XG_BC_FILL);
-  const bool shl = V > 1 && (ntl & 1);
-  const bool own = !shl || (threadIdx.x & 63) == 63 || edge;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);  // (the right side only)
+  const bool fill_edge = e.edge_r && (bc_x == XG_BC_FILL);
   const real* pu = u + (o * ny + j0) * nx;
   const real* pv = v + o * ny * nx + i0;
   T uu[SEG], vv[SEG + 1];
@@ -1070,7 +1008,7 @@ __global__ __launch_bounds__(BLOCK) void k_kinetic(
   for (int s_ = 0; s_ < SEG; ++s_) {
     const int64_t jr = (s_ < nrow) ? s_ : nrow - 1;
     uu[s_] = *reinterpret_cast<const T*>(pu + jr * nx + i0);
-    ur[s_] = own ? pu[jr * nx + ridx] : real(0);
+    ur[s_] = e.own_r ? pu[jr * nx + e.ridx] : real(0);
     vv[s_] = *reinterpret_cast<const T*>(pv + (j0 + jr) * nx);
   }
   bool ftop = false;
@@ -1083,11 +1021,11 @@ __global__ __launch_bounds__(BLOCK) void k_kinetic(
     }
     vv[SEG] = *reinterpret_cast<const T*>(src);
   }
-  if (shl) {
+  if (e.shl) {
 #pragma unroll
     for (int s_ = 0; s_ < SEG; ++s_) {
-      const real right = from_lane_above(vec_first(uu[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own`)
-      if (!own) ur[s_] = right;
+      const real right = from_lane_above(vec_first(uu[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+      if (!e.own_r) ur[s_] = right;
     }
   }
   real* po = out + (o * ny + j0) * nx + i0;
@@ -1131,25 +1069,7 @@ __global__ __launch_bounds__(BLOCK) void k_momadv(
     u32 nouter, u32 nblk, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, ZBand zb, int bc_x, real fill_x, int bc_y,
     real fill_y, Div2dMet mt, int ntl) {  // mt: rAz, coriolis (Y:l, X:l), dxC (Y:c, X:l), dyC (Y:l, X:c)
   typedef typename VecT<V>::type T;
-  const u32 pb = (nblk + 7) >> 3;
-  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
-  if (lb >= nblk) return;
-  const u32 w = __builtin_amdgcn_readfirstlane(lb * WPB + (threadIdx.x >> 6));
-  const u32 r = fdiv(w, ntile);
-  const u32 tile = w - r * ntile.d;
-  u32 oo, sg;
-  if (zb.on) {  // band-major: the metric rows of a band stay in the XCD's L2 for all outer indices
-    if (!zband_map(zb, r, oo, sg)) return;
-  } else {
-    oo = fdiv(r, nseg);
-    if (oo >= nouter) return;
-    sg = r - oo * nseg.d;
-  }
-  const int64_t o = o0 + oo;
-  const int64_t i0 = ((int64_t)tile * WAVE + (threadIdx.x & 63)) * V;
-  if (i0 >= nx) return;
-  const int64_t j0 = (int64_t)sg * SEG;
-  const int64_t nrow = (ny - j0 < SEG) ? ny - j0 : SEG;
+  XG_WAVE_TASK(V, SEG, zb.on, zb, 1);  // (band-major: the metric rows of a band stay in the XCD's L2 for all outer indices)
   const int64_t base = o * ny * nx;
   const bool per_x = bc_x == XG_BC_PERIODIC, per_y = bc_y == XG_BC_PERIODIC;
   const bool edge_l = (i0 == 0), edge_r = (i0 + V >= nx);
@@ -1316,6 +1236,155 @@ __global__ __launch_bounds__(BLOCK) void k_momadv(
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// host side of the fused kernels
+// ------------------------------------------------------------------------------------------
+// may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
+// every outer index?  (lanes start at multiples of NV along X)
+bool plane_vec_ok(const real* m, const AreaIdx& ai, int64_t sy, int64_t sx) {
+  if (!m || sx != 1 || sy % NV != 0 || !aligned16(m)) return false;
+  for (int d = 0; d < ai.n; ++d)
+    if (ai.stride[d] % NV != 0) return false;
+  return true;
+}
+
+// a metric / area plane with broadcast strides: its (Y, X) strides + one stride per leading dim (0 = broadcast); adjacent
+// leading dims are merged.  `core`: the trailing dims that are not leading dims (2: (Y, X); K7e's volume: 3, (Z, Y, X))
+int area_index(const real* m, const int64_t* strides, const int64_t* shape, int ndim, AreaIdx* ai, int64_t* sy,
+                      int64_t* sx, int core = 2) {
+  memset(ai, 0, sizeof(*ai));
+  for (int d = 0; d < XG_MAX_NDIM; ++d) ai->fd[d] = make_fastdiv(1);
+  *sy = *sx = 0;
+  if (!m) return 0;
+  if (!strides) return fail(XG_ERR_INVALID, "metric without strides");
+  *sy = strides[ndim - 2];
+  *sx = strides[ndim - 1];
+  for (int d = 0; d < ndim - core; ++d) {
+    if (shape[d] == 1) continue;
+    const int64_t st = strides[d];
+    if (ai->n > 0 && ai->stride[ai->n - 1] == st * shape[d]) {  // merges with the previous (slower) dim
+      ai->fd[ai->n - 1] = make_fastdiv((u64)ai->fd[ai->n - 1].d * (u64)shape[d]);
+      ai->stride[ai->n - 1] = st;
+      continue;
+    }
+    ai->fd[ai->n] = make_fastdiv((u64)shape[d]);
+    ai->stride[ai->n] = st;
+    ++ai->n;
+  }
+  return 0;
+}
+
+// one factor of a 3-D metric (K7e's volume, K7f's face weights and area): area_index + its stride along Z
+int vol_index(VolIdx* vi, const real* m, const int64_t* strides, const int64_t* shape, int ndim) {
+  memset(vi, 0, sizeof(*vi));
+  vi->p = m;
+  const int rc = area_index(m, strides, shape, ndim, &vi->ai, &vi->sy, &vi->sx, 3);
+  if (rc) return rc;
+  vi->sz = m ? strides[ndim - 3] : 0;
+  return 0;
+}
+
+// absent, or broadcast along every leading dim: every outer index reads the same plane
+bool planes_shared(const real* m, const AreaIdx& ai) {
+  for (int d = 0; m && d < ai.n; ++d)
+    if (ai.stride[d] != 0) return false;
+  return true;
+}
+
+// the `ntl` bits that the `vec_nt` tunable governs (bit 0: the neighbours by lane shuffle; K7 also bit 1)
+int vec_nt_bits(int mask) { return tune().nt_load ? (tune().vec_nt & mask) : 0; }
+// rows of a band at its full height (the `vec_zb_rows` tunable; the launchers halve or double it, see there)
+u32 band_rows() { return (u32)(tune().vec_zb_rows > 1 ? tune().vec_zb_rows : 16); }
+
+// ------------------------------------------------------------------------------------------
+// What the launchers of the fused kernels share: the view (outer, [Z,] Y, X) of the fields, the decomposition into
+// wave-tasks (x-tiles of WAVE * V columns, segments of FSEG rows), the band-major order and the launches.
+// ------------------------------------------------------------------------------------------
+constexpr int FSEG = XG_FUSED_SEG;  // (K7d with 4 rows: the laplacian 12 % slower, the flux divergence 0.7 % faster -- EXPERIMENTS.md)
+
+struct FusedPlan {
+  const char* name;
+  bool empty;                   // an extent is 0: nothing to do
+  int64_t ny, nx, nz, outer;    // nz = 1 for the 2-D operators
+  int V;
+  u64 ntile, nseg, per_outer;   // x-tiles, Y segments, wave-tasks per outer index
+  FastDiv fnt, fns;
+  ZBand zb;                     // band-major order (fused_band), off by default
+  u64 band_waves;               // wave-tasks of the one banded launch (tail bands padded)
+  u64 outer_step;               // outer indices per launch
+  bool nts;
+  hipStream_t st;
+};
+
+// the argument checks every fused operator makes first: ndim, and each boundary mode in [periodic, bc_max].  The operator's
+// own argument checks follow it and precede fused_plan, as they always did, so a bad call keeps its error code.
+int fused_dims(const char* name, int ndim, int core, std::initializer_list<int> bcs, int bc_max) {
+  if (ndim < core || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "%s: ndim %d not in [%d,%d]", name, ndim, core, XG_MAX_NDIM);
+  for (int b : bcs)
+    if (b < XG_BC_PERIODIC || b > bc_max) return fail(XG_ERR_INVALID, "%s: boundary mode %d not in [%d,%d]", name, b, XG_BC_PERIODIC, bc_max);
+  return 0;
+}
+
+// extents (`core` = 2: (Y, X), 3: (Z, Y, X); the leading dims flattened into `outer`), the lane width -- `aligned`: every
+// field pointer is 16-byte aligned -- and the task geometry.  `planes_by_outer`: a kernel argument is indexed by the 32-bit
+// outer index.  An empty array is XG_OK with `empty` set.
+int fused_plan(FusedPlan* p, const char* name, const int64_t* shape, int ndim, int core, bool aligned,
+                      bool planes_by_outer, void* stream) {
+  memset(p, 0, sizeof(*p));
+  p->name = name;
+  p->nz = (core == 3) ? shape[ndim - 3] : 1;
+  p->ny = shape[ndim - 2];
+  p->nx = shape[ndim - 1];
+  p->outer = 1;
+  for (int d = 0; d < ndim - core; ++d) p->outer *= shape[d];
+  p->empty = p->outer == 0 || p->nz == 0 || p->ny == 0 || p->nx == 0;
+  if (p->empty) return XG_OK;
+  if (planes_by_outer && p->outer > 0xffffffffll)
+    return fail(XG_ERR_UNSUPPORTED, "%s: more than 2^32 %s", name, core == 3 ? "(Z,Y,X) volumes" : "(Y,X) planes");
+  p->V = (aligned && p->nx % NV == 0) ? NV : 1;
+  p->ntile = (u64)((p->nx + (int64_t)WAVE * p->V - 1) / ((int64_t)WAVE * p->V));
+  p->nseg = (u64)((p->ny + FSEG - 1) / FSEG);
+  p->per_outer = p->ntile * p->nseg;
+  p->fnt = make_fastdiv(p->ntile);
+  p->fns = make_fastdiv(p->nseg);
+  p->zb = make_zband(false, 0, 0, 1);
+  p->outer_step = MAX_ITEMS / p->per_outer;  // (0 for an extent that fused_launch refuses)
+  p->nts = tune().nt_store;
+  p->st = (hipStream_t)stream;
+  return XG_OK;
+}
+
+// band-major order when the planes are `shared` by every outer index (2-D metrics under a (Z, Y, X) field) -- level-major
+// they come from the fabric again for every level (the gradient: 0.56 of 8 TB/s): bands of `rows` rows, all `zgroups` level
+// groups (the outer indices; K7 / K7b: groups of ZK levels) of a band in ONE launch
+void fused_band(FusedPlan* p, bool shared, u32 rows, u64 zgroups) {
+  if (!shared || !tune().zband || p->outer < 2) return;
+  const u32 segs = (rows + FSEG - 1) / FSEG;
+  const u64 padded = ((p->nseg + segs - 1) / segs) * segs * zgroups * p->ntile;
+  if (padded > MAX_ITEMS) return;
+  p->zb = make_zband(true, zgroups, p->nseg, segs);
+  if (!p->zb.on) return;
+  p->band_waves = padded;
+  p->outer_step = (u64)p->outer;  // one launch over all levels
+}
+
+// the launches: `go(o0, nouter, nblk, grid)` starts the kernel for outer indices o0 .. o0 + nouter - 1 with nblk blocks of
+// work on a grid rounded up to the 8 XCD bands.  (More than one launch takes more than 2^31 wave-tasks.)
+template <class Go>
+int fused_launch(const FusedPlan& p, Go&& go) {
+  if (p.per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the %s kernel", p.name);
+  for (int64_t o0 = 0; o0 < p.outer; o0 += (int64_t)p.outer_step) {
+    const u32 nouter = (u32)((p.outer - o0 < (int64_t)p.outer_step) ? p.outer - o0 : (int64_t)p.outer_step);
+    const u64 waves = p.zb.on ? p.band_waves : (u64)nouter * p.per_outer;
+    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
+    const int rc = check_grid((u64)nblk + 8);
+    if (rc) return rc;
+    go(o0, nouter, nblk, ((nblk + 7) / 8) * 8);
+  }
+  XG_LAUNCH_CHECK();
+  return XG_OK;
+}
+
 #endif  // !XG_INT
 
 }  // namespace
@@ -1403,107 +1472,46 @@ int XG_FN(xg_binary)(int op, const real* a, const int64_t* a_strides, const real
 }
 
 #ifndef XG_INT
-// may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
-// every outer index?  (lanes start at multiples of NV along X)
-static bool plane_vec_ok(const real* m, const AreaIdx& ai, int64_t sy, int64_t sx) {
-  if (!m || sx != 1 || sy % NV != 0 || !aligned16(m)) return false;
-  for (int d = 0; d < ai.n; ++d)
-    if (ai.stride[d] % NV != 0) return false;
-  return true;
-}
-
 static int curl_div_impl(bool div, const real* u, const real* v, const real* area, const int64_t* area_strides,
                          real* out, const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y,
                          void* stream, const real* halo_x = nullptr, const real* halo_y = nullptr) {
+  const char* name = div ? "divergence" : "vorticity";
   if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
+  int rc;
+  if ((rc = fused_dims(name, ndim, 2, {bc_x, bc_y}, XG_BC_HALO))) return rc;
   if (area && !area_strides) return fail(XG_ERR_INVALID, "area without strides");
-  if (bc_x < XG_BC_PERIODIC || bc_x > XG_BC_HALO || bc_y < XG_BC_PERIODIC || bc_y > XG_BC_HALO)
-    return fail(XG_ERR_INVALID, "vorticity / divergence need a boundary mode on both axes");
   if ((bc_x == XG_BC_HALO && !halo_x) || (bc_y == XG_BC_HALO && !halo_y))
     return fail(XG_ERR_INVALID, "XG_BC_HALO without the halo buffer of that axis");
-  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
-  int64_t outer = 1;
-  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
-  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
-  // area: (Y, X) strides + one stride per leading dim (0 = broadcast); adjacent leading dims are merged
-  int64_t a_sy = 0, a_sx = 0;
-  bool area_bcast_all = true;
+  FusedPlan p;
+  const bool al = aligned16(u) && aligned16(v) && aligned16(out) && (bc_y != XG_BC_HALO || aligned16(halo_y));
+  if ((rc = fused_plan(&p, name, shape, ndim, 2, al, area != nullptr, stream)) || p.empty) return rc;
   AreaIdx ai;
-  memset(&ai, 0, sizeof(ai));
-  for (int d = 0; d < XG_MAX_NDIM; ++d) ai.fd[d] = make_fastdiv(1);
-  if (area) {
-    a_sy = area_strides[ndim - 2];
-    a_sx = area_strides[ndim - 1];
-    for (int d = 0; d < ndim - 2; ++d) {
-      if (shape[d] == 1) continue;
-      const int64_t st = area_strides[d];
-      if (st != 0) area_bcast_all = false;
-      if (ai.n > 0 && ai.stride[ai.n - 1] == st * shape[d]) {  // merges with the previous (slower) dim
-        ai.fd[ai.n - 1] = make_fastdiv((u64)ai.fd[ai.n - 1].d * (u64)shape[d]);
-        ai.stride[ai.n - 1] = st;
-        continue;
-      }
-      ai.fd[ai.n] = make_fastdiv((u64)shape[d]);
-      ai.stride[ai.n] = st;
-      ++ai.n;
-    }
-    if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Y,X) planes");
-  }
-  const int V = (aligned16(u) && aligned16(v) && aligned16(out) && nx % NV == 0 &&
-                 (bc_y != XG_BC_HALO || aligned16(halo_y))) ? NV : 1;
-  constexpr int SEG = XG_FUSED_SEG;
-  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
-  const u64 nseg_rows = (u64)((ny + SEG - 1) / SEG);
-  hipStream_t st = (hipStream_t)stream;
-  const bool nts = tune().nt_store;
+  int64_t a_sy, a_sx;
+  if ((rc = area_index(area, area_strides, shape, ndim, &ai, &a_sy, &a_sx))) return rc;
   // bit 0: v rows non-temporal (neighbour by lane shuffle), bit 1: inner u rows, bit 2: the area rows are aligned vectors
-  const int vnt = (tune().nt_load ? (tune().vec_nt & 3) : 0) | ((V > 1 && plane_vec_ok(area, ai, a_sy, a_sx)) ? 4 : 0);
-  const u64 nseg = nseg_rows;
-  const u64 per_outer = ntile * nseg;
-  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the vorticity kernel");
-  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
-  const u64 outer_per = MAX_ITEMS / per_outer;
+  const int vnt = vec_nt_bits(3) | ((p.V > 1 && plane_vec_ok(area, ai, a_sy, a_sx)) ? 4 : 0);
+  // levels per wave-task sharing the area rows: z-banded launches with the default vector lanes and stores only
+  int zk = (p.V > 1 && p.nts) ? tune().vec_zk : 1;
+  zk = zk >= 4 ? 4 : (zk >= 2 ? 2 : 1);
   // band height: the area rows of a band must survive in the XCD's 4 MB L2 while TWO fields and the output of all its
   // levels stream by.  16 rows: PMC reads 1.06x the algorithmic bytes (the halo u row of every band and level is the
   // 6 %); 24 rows 1.17x, 32 rows 1.26x -- the area is then re-read from the fabric once per level group -- at the same
   // speed within 1 % on an otherwise idle device (profiles/history/r03g_*, r03h_*)
-  const u32 zbr = (u32)(tune().vec_zb_rows > 1 ? tune().vec_zb_rows : 16);
-  const u32 ZB_SEGS = (zbr + SEG - 1) / SEG;
-  ZBand zb = make_zband(false, 0, 0, 1);
-  u64 outer_step = outer_per;
-  // levels per wave-task sharing the area rows: z-banded launches with the default vector lanes and stores only
-  int zk = (V > 1 && nts) ? tune().vec_zk : 1;
-  zk = zk >= 4 ? 4 : (zk >= 2 ? 2 : 1);
-  u64 zgroups = (u64)outer;
-  if (area && area_bcast_all && tune().zband && outer >= 2) {
-    const u64 padded_segs = ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS;
-    zgroups = ((u64)outer + zk - 1) / zk;
-    if (padded_segs * zgroups * ntile <= MAX_ITEMS) {
-      zb = make_zband(true, zgroups, nseg, ZB_SEGS);
-      if (zb.on) outer_step = (u64)outer;  // one launch over all levels
-    }
-  }
-  if (!zb.on) zk = 1;
-  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_step) {
-    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_step) ? outer - o0 : (int64_t)outer_step);
-    const u64 units = zb.on ? ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * zgroups * ntile : (u64)nouter * per_outer;
-    const u32 nblk = (u32)((units + WPB - 1) / WPB);
-    const u32 grid = ((nblk + 7) / 8) * 8;
-#define XG_GZ(V_, A_, NTS, ZK_) do { if (div) hipLaunchKernelGGL((k_divergence<V_, A_, NTS, SEG, ZK_>), dim3(grid), dim3(BLOCK), 0, st, u, v, area, out, o0, nouter, nblk, ny, nx, fnt, fns, zb, bc_x, fill_x, bc_y, fill_y, ai, a_sy, a_sx, halo_x, halo_y, vnt); \
-                                else hipLaunchKernelGGL((k_vorticity<V_, A_, NTS, SEG, ZK_>), dim3(grid), dim3(BLOCK), 0, st, u, v, area, out, o0, nouter, nblk, ny, nx, fnt, fns, zb, bc_x, fill_x, bc_y, fill_y, ai, a_sy, a_sx, halo_x, halo_y, vnt); } while (0)
+  fused_band(&p, area && planes_shared(area, ai), band_rows(), ((u64)p.outer + zk - 1) / zk);
+  if (!p.zb.on) zk = 1;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GZ(V_, A_, NTS, ZK_) do { if (div) hipLaunchKernelGGL((k_divergence<V_, A_, NTS, FSEG, ZK_>), dim3(grid), dim3(BLOCK), 0, p.st, u, v, area, out, o0, nouter, nblk, p.ny, p.nx, p.fnt, p.fns, p.zb, bc_x, fill_x, bc_y, fill_y, ai, a_sy, a_sx, halo_x, halo_y, vnt); \
+                                else hipLaunchKernelGGL((k_vorticity<V_, A_, NTS, FSEG, ZK_>), dim3(grid), dim3(BLOCK), 0, p.st, u, v, area, out, o0, nouter, nblk, p.ny, p.nx, p.fnt, p.fns, p.zb, bc_x, fill_x, bc_y, fill_y, ai, a_sy, a_sx, halo_x, halo_y, vnt); } while (0)
 #define XG_GO(V_, A_, NTS) XG_GZ(V_, A_, NTS, 1)
-#define XG_A(V_, A_) do { if (nts) XG_GO(V_, A_, true); else XG_GO(V_, A_, false); } while (0)
+#define XG_A(V_, A_) do { if (p.nts) XG_GO(V_, A_, true); else XG_GO(V_, A_, false); } while (0)
     if (zk == 4) XG_GZ(NV, true, true, 4);
     else if (zk == 2) XG_GZ(NV, true, true, 2);
-    else if (V > 1) { if (area) XG_A(NV, true); else XG_A(NV, false); }
+    else if (p.V > 1) { if (area) XG_A(NV, true); else XG_A(NV, false); }
     else { if (area) XG_A(1, true); else XG_A(1, false); }
 #undef XG_A
 #undef XG_GO
 #undef XG_GZ
-  }
-  XG_LAUNCH_CHECK();
-  return XG_OK;
+  });
 }
 
 int XG_FN(xg_vorticity)(const real* u, const real* v, const real* area, const int64_t* area_strides, real* out,
@@ -1530,101 +1538,40 @@ int XG_FN(xg_divergence_halo)(const real* u, const real* v, const real* halo_x, 
   return curl_div_impl(true, u, v, area, area_strides, out, shape, ndim, bc_x, fill_x, bc_y, fill_y, stream, halo_x, halo_y);
 }
 
-// `core`: the trailing dims that are not leading dims (2: (Y, X); K7e's volume: 3, (Z, Y, X))
-static int area_index(const real* m, const int64_t* strides, const int64_t* shape, int ndim, AreaIdx* ai, int64_t* sy,
-                      int64_t* sx, int core = 2) {
-  memset(ai, 0, sizeof(*ai));
-  for (int d = 0; d < XG_MAX_NDIM; ++d) ai->fd[d] = make_fastdiv(1);
-  *sy = *sx = 0;
-  if (!m) return 0;
-  if (!strides) return fail(XG_ERR_INVALID, "metric without strides");
-  *sy = strides[ndim - 2];
-  *sx = strides[ndim - 1];
-  for (int d = 0; d < ndim - core; ++d) {
-    if (shape[d] == 1) continue;
-    const int64_t st = strides[d];
-    if (ai->n > 0 && ai->stride[ai->n - 1] == st * shape[d]) {
-      ai->fd[ai->n - 1] = make_fastdiv((u64)ai->fd[ai->n - 1].d * (u64)shape[d]);
-      ai->stride[ai->n - 1] = st;
-      continue;
-    }
-    ai->fd[ai->n] = make_fastdiv((u64)shape[d]);
-    ai->stride[ai->n] = st;
-    ++ai->n;
-  }
-  return 0;
-}
-
 static int pair2d_impl(int mode, const real* a, const real* u, const real* v, real* out_x, real* out_y,
                        const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, const real* mx,
                        const int64_t* mx_strides, const real* my, const int64_t* my_strides, void* stream,
                        const real* halo_x = nullptr, const real* halo_y = nullptr) {
+  const char* name = mode ? "flux" : "gradient";
   if (!a || !out_x || !out_y || !shape || (mode == 1 && (!u || !v))) return fail(XG_ERR_INVALID, "NULL array argument");
   if ((bc_x == XG_BC_HALO && !halo_x) || (bc_y == XG_BC_HALO && !halo_y)) return fail(XG_ERR_INVALID, "halo mode without a halo array");
-  const int bc_max = (halo_x || halo_y) ? XG_BC_HALO : XG_BC_EXTEND;
-  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
-  if (bc_x < XG_BC_PERIODIC || bc_x > bc_max || bc_y < XG_BC_PERIODIC || bc_y > bc_max)
-    return fail(XG_ERR_INVALID, "gradient / flux need a boundary mode on both axes");
-  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
-  int64_t outer = 1;
-  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
-  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
-  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Y,X) planes");
-  AreaIdx aix, aiy;
-  int64_t mx_sy, mx_sx, my_sy, my_sx;
   int rc;
-  if ((rc = area_index(mx, mx_strides, shape, ndim, &aix, &mx_sy, &mx_sx))) return rc;
-  if ((rc = area_index(my, my_strides, shape, ndim, &aiy, &my_sy, &my_sx))) return rc;
-  bool al = aligned16(a) && aligned16(out_x) && aligned16(out_y) && nx % NV == 0;
+  if ((rc = fused_dims(name, ndim, 2, {bc_x, bc_y}, (halo_x || halo_y) ? XG_BC_HALO : XG_BC_EXTEND))) return rc;
+  bool al = aligned16(a) && aligned16(out_x) && aligned16(out_y);
   if (mode == 1) al = al && aligned16(u) && aligned16(v);
   if (bc_y == XG_BC_HALO) al = al && aligned16(halo_y);
-  const int V = al ? NV : 1;
-  constexpr int SEG = XG_FUSED_SEG;
-  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
-  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
-  const u64 per_outer = ntile * nseg;
-  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the fused two-output kernel");
-  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
-  const u64 outer_per = MAX_ITEMS / per_outer;
-  hipStream_t st = (hipStream_t)stream;
-  const bool nts = tune().nt_store;
-  const int vnt = tune().nt_load ? (tune().vec_nt & 1) : 0;  // bit 0: field rows non-temporal + the left neighbour by DPP
-  // gradient with metrics that every outer index shares (dxC(Y,X), dyC(Y,X) under a (Z,Y,X) field): band-major order, or
-  // both planes come from the fabric again for every level (0.56 of 8 TB/s level-major).  Two metrics: 8-row bands (rule 13)
-  ZBand zb = make_zband(false, 0, 0, 1);
-  u64 outer_step = outer_per;
-  // rows per band: twice `vec_zb_rows` (32) with one metric plane, `vec_zb_rows` (16) with two -- round 4, PMC per band
-  // height (profiles/history/r04b_ab_bands_grad.log): two metrics 8 -> 16 rows reads 5.97 -> 5.65 GB (traffic 1.041 -> 1.021x), 32
+  FusedPlan p;
+  if ((rc = fused_plan(&p, name, shape, ndim, 2, al, true, stream)) || p.empty) return rc;
+  AreaIdx aix, aiy;
+  int64_t mx_sy, mx_sx, my_sy, my_sx;
+  if ((rc = area_index(mx, mx_strides, shape, ndim, &aix, &mx_sy, &mx_sx))) return rc;
+  if ((rc = area_index(my, my_strides, shape, ndim, &aiy, &my_sy, &my_sx))) return rc;
+  const int vnt = vec_nt_bits(1);  // bit 0: field rows non-temporal + the left neighbour by DPP
+  // gradient with metrics that every outer index shares (dxC(Y,X), dyC(Y,X) under a (Z,Y,X) field).  Rows per band: twice
+  // `vec_zb_rows` (32) with one metric plane, `vec_zb_rows` (16) with two -- round 4, PMC per band height
+  // (profiles/history/r04b_ab_bands_grad.log): two metrics 8 -> 16 rows reads 5.97 -> 5.65 GB (traffic 1.041 -> 1.021x), 32
   // rows 5.61 GB, all at the same speed; the two `nt`-stored outputs leave the L2 room the one-output kernels do not have
   // (their cliff sits between 8 and 16 rows for two metrics, r04b_ab_bands_met.log)
-  const u32 gzb = (u32)(tune().vec_zb_rows > 1 ? tune().vec_zb_rows : 16);
-  const u32 ZB_SEGS = (u32)((((mx && my) ? gzb : 2 * gzb) + SEG - 1) / SEG);
-  auto shared = [](const real* m, const AreaIdx& ai) {  // absent, or broadcast along every leading dim
-    for (int d = 0; m && d < ai.n; ++d)
-      if (ai.stride[d] != 0) return false;
-    return true;
-  };
-  if (mode == 0 && (mx || my) && shared(mx, aix) && shared(my, aiy) && tune().zband && outer >= 2) {
-    const u64 padded = ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile;
-    if (padded <= MAX_ITEMS) {
-      zb = make_zband(true, (u64)outer, nseg, ZB_SEGS);
-      if (zb.on) outer_step = (u64)outer;
-    }
-  }
-  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_step) {
-    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_step) ? outer - o0 : (int64_t)outer_step);
-    const u64 waves = zb.on ? ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile : (u64)nouter * per_outer;
-    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
-    const u32 grid = ((nblk + 7) / 8) * 8;
-#define XG_GO(V_, M_, NTS) hipLaunchKernelGGL((k_pair2d<V_, M_, NTS, SEG>), dim3(grid), dim3(BLOCK), 0, st, a, u, v, out_x, out_y, o0, nouter, nblk, ny, nx, fnt, fns, bc_x, fill_x, bc_y, fill_y, mx, aix, mx_sy, mx_sx, my, aiy, my_sy, my_sx, halo_x, halo_y, zb, vnt)
-#define XG_M(V_, M_) do { if (nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
-    if (V > 1) { if (mode) XG_M(NV, 1); else XG_M(NV, 0); }
+  fused_band(&p, mode == 0 && (mx || my) && planes_shared(mx, aix) && planes_shared(my, aiy),
+             (mx && my) ? band_rows() : 2 * band_rows(), (u64)p.outer);
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, NTS) hipLaunchKernelGGL((k_pair2d<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, a, u, v, out_x, out_y, o0, nouter, nblk, p.ny, p.nx, p.fnt, p.fns, bc_x, fill_x, bc_y, fill_y, mx, aix, mx_sy, mx_sx, my, aiy, my_sy, my_sx, halo_x, halo_y, p.zb, vnt)
+#define XG_M(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
+    if (p.V > 1) { if (mode) XG_M(NV, 1); else XG_M(NV, 0); }
     else { if (mode) XG_M(1, 1); else XG_M(1, 0); }
 #undef XG_M
 #undef XG_GO
-  }
-  XG_LAUNCH_CHECK();
-  return XG_OK;
+  });
 }
 
 int XG_FN(xg_gradient)(const real* a, real* out_x, real* out_y, const int64_t* shape, int ndim, int bc_x, real fill_x,
@@ -1658,18 +1605,16 @@ int XG_FN(xg_flux_halo)(const real* u, const real* v, const real* t, const real*
 static int div2d_impl(int mode, const real* t, const real* u, const real* v, const real* const met[4],
                       const int64_t* const met_strides[4], const real* area, const int64_t* area_strides, real* out,
                       const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, void* stream) {
+  const char* name = mode ? "flux divergence" : "laplacian";
   if (!t || !out || !shape || (mode == 1 && (!u || !v))) return fail(XG_ERR_INVALID, "NULL array argument");
-  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
-  if (bc_x < XG_BC_PERIODIC || bc_x > XG_BC_EXTEND || bc_y < XG_BC_PERIODIC || bc_y > XG_BC_EXTEND)
-    return fail(XG_ERR_INVALID, "flux divergence / laplacian need a periodic, fill or extend boundary on both axes");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 2, {bc_x, bc_y}, XG_BC_EXTEND))) return rc;
   const int nmet = met ? (met[0] != nullptr) + (met[1] != nullptr) + (met[2] != nullptr) + (met[3] != nullptr) : 0;
   if (nmet != 0 && nmet != 4) return fail(XG_ERR_INVALID, "laplacian: the four metrics dxC, dyC, dyG, dxG, or none");
-  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
-  int64_t outer = 1;
-  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
-  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
-  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Y,X) planes");
-  int rc;
+  bool al = aligned16(t) && aligned16(out);
+  if (mode == 1) al = al && aligned16(u) && aligned16(v);
+  FusedPlan p;
+  if ((rc = fused_plan(&p, name, shape, ndim, 2, al, true, stream)) || p.empty) return rc;
   AreaIdx ai;
   int64_t a_sy, a_sx;
   if ((rc = area_index(area, area_strides, shape, ndim, &ai, &a_sy, &a_sx))) return rc;
@@ -1679,61 +1624,27 @@ static int div2d_impl(int mode, const real* t, const real* u, const real* v, con
     mt.p[k] = nmet ? met[k] : nullptr;
     if ((rc = area_index(mt.p[k], nmet ? met_strides[k] : nullptr, shape, ndim, &mt.ai[k], &mt.sy[k], &mt.sx[k]))) return rc;
   }
-  bool al = aligned16(t) && aligned16(out) && nx % NV == 0;
-  if (mode == 1) al = al && aligned16(u) && aligned16(v);
-  const int V = al ? NV : 1;
-  constexpr int SEG = XG_FUSED_SEG;  // (4 rows: the laplacian 12 % slower, the flux divergence 0.7 % faster -- EXPERIMENTS.md)
-  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
-  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
-  const u64 per_outer = ntile * nseg;
-  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the fused second-order kernel");
-  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
-  const u64 outer_per = MAX_ITEMS / per_outer;
-  hipStream_t st = (hipStream_t)stream;
-  const bool nts = tune().nt_store;
   // bit 0: inner T rows non-temporal + the neighbours by DPP (K7c's scheme), bit 2: the area rows are aligned vectors
-  int vnt = (tune().nt_load ? (tune().vec_nt & 1) : 0) | ((V > 1 && plane_vec_ok(area, ai, a_sy, a_sx)) ? 4 : 0);
+  int vnt = vec_nt_bits(1) | ((p.V > 1 && plane_vec_ok(area, ai, a_sy, a_sx)) ? 4 : 0);
   if (nmet) {  // bit 3: the four metric planes are aligned vectors as well
-    bool mv = V > 1;
+    bool mv = p.V > 1;
     for (int k = 0; k < 4; ++k) mv = mv && plane_vec_ok(mt.p[k], mt.ai[k], mt.sy[k], mt.sx[k]);
     vnt |= mv ? 8 : 0;
   }
-  // planes shared by every outer index (2-D metrics under a (Z, Y, X) field): band-major order, K7b's 16 rows per band for the
-  // area alone, 8 with the five planes of the weighted laplacian (K7c: the more planes, the lower the band)
-  auto shared = [](const real* m, const AreaIdx& a_) {
-    for (int d = 0; m && d < a_.n; ++d)
-      if (a_.stride[d] != 0) return false;
-    return true;
-  };
-  bool all_shared = (area || nmet) && shared(area, ai);
-  for (int k = 0; k < 4; ++k) all_shared = all_shared && shared(mt.p[k], mt.ai[k]);
-  const u32 zbr = (u32)(tune().vec_zb_rows > 1 ? tune().vec_zb_rows : 16);
-  const u32 ZB_SEGS = (u32)(((nmet ? (zbr + 1) / 2 : zbr) + SEG - 1) / SEG);
-  ZBand zb = make_zband(false, 0, 0, 1);
-  u64 outer_step = outer_per;
-  if (all_shared && tune().zband && outer >= 2) {
-    const u64 padded = ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile;
-    if (padded <= MAX_ITEMS) {
-      zb = make_zband(true, (u64)outer, nseg, ZB_SEGS);
-      if (zb.on) outer_step = (u64)outer;
-    }
-  }
-  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_step) {
-    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_step) ? outer - o0 : (int64_t)outer_step);
-    const u64 waves = zb.on ? ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile : (u64)nouter * per_outer;
-    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
-    if ((rc = check_grid((u64)nblk + 8))) return rc;
-    const u32 grid = ((nblk + 7) / 8) * 8;
-#define XG_GO(V_, M_, A_, NTS) do { hipLaunchKernelGGL((k_div2d<V_, M_, A_, NTS, SEG>), dim3(grid), dim3(BLOCK), 0, st, t, u, v, area, out, o0, nouter, nblk, ny, nx, fnt, fns, zb, bc_x, fill_x, bc_y, fill_y, ai, a_sy, a_sx, mt, vnt); } while (0)
-#define XG_A(V_, M_) do { if (area) { if (nts) XG_GO(V_, M_, true, true); else XG_GO(V_, M_, true, false); } \
-                          else { if (nts) XG_GO(V_, M_, false, true); else XG_GO(V_, M_, false, false); } } while (0)
-    if (V > 1) { if (mode) XG_A(NV, 1); else XG_A(NV, 0); }
+  // K7b's 16 rows per band for the area alone, 8 with the five planes of the weighted laplacian (K7c: the more planes, the
+  // lower the band)
+  bool all_shared = (area || nmet) && planes_shared(area, ai);
+  for (int k = 0; k < 4; ++k) all_shared = all_shared && planes_shared(mt.p[k], mt.ai[k]);
+  fused_band(&p, all_shared, nmet ? (band_rows() + 1) / 2 : band_rows(), (u64)p.outer);
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, A_, NTS) do { hipLaunchKernelGGL((k_div2d<V_, M_, A_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, t, u, v, area, out, o0, nouter, nblk, p.ny, p.nx, p.fnt, p.fns, p.zb, bc_x, fill_x, bc_y, fill_y, ai, a_sy, a_sx, mt, vnt); } while (0)
+#define XG_A(V_, M_) do { if (area) { if (p.nts) XG_GO(V_, M_, true, true); else XG_GO(V_, M_, true, false); } \
+                          else { if (p.nts) XG_GO(V_, M_, false, true); else XG_GO(V_, M_, false, false); } } while (0)
+    if (p.V > 1) { if (mode) XG_A(NV, 1); else XG_A(NV, 0); }
     else { if (mode) XG_A(1, 1); else XG_A(1, 0); }
 #undef XG_A
 #undef XG_GO
-  }
-  XG_LAUNCH_CHECK();
-  return XG_OK;
+  });
 }
 
 int XG_FN(xg_flux_divergence)(const real* u, const real* v, const real* t, const real* area, const int64_t* area_strides,
@@ -1757,60 +1668,33 @@ int XG_FN(xg_flux_divergence3d)(const real* u, const real* v, const real* w, con
                                 const int64_t* vol_strides, const real* vol2, const int64_t* vol2_strides, real* out,
                                 const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
                                 real fill_z, void* stream) {
+  const char* name = "3-D flux divergence";
   if (!u || !v || !w || !t || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
-  for (int b : {bc_x, bc_y, bc_z})
-    if (b < XG_BC_PERIODIC || b > XG_BC_EXTEND)
-      return fail(XG_ERR_INVALID, "3-D flux divergence needs a periodic, fill or extend boundary on all three axes");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
   if (vol2 && !vol) return fail(XG_ERR_INVALID, "3-D flux divergence: a second volume factor without the first");
   if ((vol && !vol_strides) || (vol2 && !vol2_strides)) return fail(XG_ERR_INVALID, "metric without strides");
-  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1];
-  int64_t outer = 1;
-  for (int d = 0; d < ndim - 3; ++d) outer *= shape[d];
-  if (outer == 0 || nz == 0 || ny == 0 || nx == 0) return XG_OK;
-  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Z,Y,X) volumes");
-  int rc;
+  FusedPlan p;
+  const bool al = aligned16(t) && aligned16(u) && aligned16(v) && aligned16(w) && aligned16(out);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
   VolIdx vi[2];
-  const real* vp[2] = {vol, vol2};
-  const int64_t* vs[2] = {vol_strides, vol2_strides};
-  for (int k = 0; k < 2; ++k) {
-    memset(&vi[k], 0, sizeof(VolIdx));
-    vi[k].p = vp[k];
-    if ((rc = area_index(vp[k], vs[k], shape, ndim, &vi[k].ai, &vi[k].sy, &vi[k].sx, 3))) return rc;
-    vi[k].sz = vp[k] ? vs[k][ndim - 3] : 0;
-  }
-  const int V = (aligned16(t) && aligned16(u) && aligned16(v) && aligned16(w) && aligned16(out) && nx % NV == 0) ? NV : 1;
-  constexpr int SEG = XG_FUSED_SEG;
-  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
-  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
-  const u64 per_outer = ntile * nseg;
-  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the 3-D flux divergence kernel");
-  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
-  const u64 outer_per = MAX_ITEMS / per_outer;
-  hipStream_t st = (hipStream_t)stream;
-  const bool nts = tune().nt_store;
+  if ((rc = vol_index(&vi[0], vol, vol_strides, shape, ndim))) return rc;
+  if ((rc = vol_index(&vi[1], vol2, vol2_strides, shape, ndim))) return rc;
   // bit 0: the lane neighbours by DPP (K7d), bits 2 / 3: the rows of volume factor 0 / 1 are aligned vectors
-  int vnt = tune().nt_load ? (tune().vec_nt & 1) : 0;
+  int vnt = vec_nt_bits(1);
   for (int k = 0; k < 2; ++k)
-    if (V > 1 && vi[k].sz % NV == 0 && plane_vec_ok(vi[k].p, vi[k].ai, vi[k].sy, vi[k].sx)) vnt |= 4 << k;
+    if (p.V > 1 && vi[k].sz % NV == 0 && plane_vec_ok(vi[k].p, vi[k].ai, vi[k].sy, vi[k].sx)) vnt |= 4 << k;
   const int nvol = (vol != nullptr) + (vol2 != nullptr);
-  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_per) {
-    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_per) ? outer - o0 : (int64_t)outer_per);
-    const u64 waves = (u64)nouter * per_outer;
-    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
-    if ((rc = check_grid((u64)nblk + 8))) return rc;
-    const u32 grid = ((nblk + 7) / 8) * 8;
-#define XG_GO(V_, N_, NTS) do { hipLaunchKernelGGL((k_div3d<V_, N_, NTS, SEG>), dim3(grid), dim3(BLOCK), 0, st, t, u, v, w, out, o0, nouter, nblk, nz, ny, nx, fnt, fns, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, vi[0], vi[1], vnt); } while (0)
-#define XG_N(V_, N_) do { if (nts) XG_GO(V_, N_, true); else XG_GO(V_, N_, false); } while (0)
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, N_, NTS) do { hipLaunchKernelGGL((k_div3d<V_, N_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, t, u, v, w, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, vi[0], vi[1], vnt); } while (0)
+#define XG_N(V_, N_) do { if (p.nts) XG_GO(V_, N_, true); else XG_GO(V_, N_, false); } while (0)
 #define XG_V(V_) do { if (nvol == 2) XG_N(V_, 2); else if (nvol == 1) XG_N(V_, 1); else XG_N(V_, 0); } while (0)
-    if (V > 1) XG_V(NV);
+    if (p.V > 1) XG_V(NV);
     else XG_V(1);
 #undef XG_V
 #undef XG_N
 #undef XG_GO
-  }
-  XG_LAUNCH_CHECK();
-  return XG_OK;
+  });
 }
 
 // K7f's launcher: (lead, Z, Y, X) fields, five optional broadcast metrics (face weights of u and of v, two factors each,
@@ -1823,111 +1707,63 @@ int XG_FN(xg_vertical_velocity)(const real* u, const real* v, const real* mu, co
                                 const int64_t* mv2_strides, const real* area, const int64_t* area_strides, real* out,
                                 const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
                                 real fill_z, int reverse, void* stream) {
+  const char* name = "vertical velocity";
   if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
-  for (int b : {bc_x, bc_y})
-    if (b < XG_BC_PERIODIC || b > XG_BC_EXTEND)
-      return fail(XG_ERR_INVALID, "vertical velocity needs a periodic, fill or extend boundary on X and Y");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y}, XG_BC_EXTEND))) return rc;
   if (!reverse && bc_z != XG_BC_FILL && bc_z != XG_BC_EXTEND)
     return fail(XG_ERR_UNSUPPORTED, "vertical velocity summed upward pads Z with fill or extend (periodic needs the column total first)");
   if ((mu != nullptr) != (mv != nullptr)) return fail(XG_ERR_INVALID, "vertical velocity: face weights for both u and v, or for neither");
   if ((mu2 && !mu) || (mv2 && !mv)) return fail(XG_ERR_INVALID, "vertical velocity: a second face-weight factor without the first");
-  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1];
-  int64_t outer = 1;
-  for (int d = 0; d < ndim - 3; ++d) outer *= shape[d];
-  if (outer == 0 || nz == 0 || ny == 0 || nx == 0) return XG_OK;
-  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Z,Y,X) volumes");
-  int rc;
+  FusedPlan p;
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, aligned16(u) && aligned16(v) && aligned16(out), true, stream)) || p.empty) return rc;
   VolIdx mi[5];  // u: a, b; v: a, b; area
   const real* mp[5] = {mu, mu2, mv, mv2, area};
   const int64_t* ms[5] = {mu_strides, mu2_strides, mv_strides, mv2_strides, area_strides};
-  for (int k = 0; k < 5; ++k) {
-    if (mp[k] && !ms[k]) return fail(XG_ERR_INVALID, "metric without strides");
-    memset(&mi[k], 0, sizeof(VolIdx));
-    mi[k].p = mp[k];
-    if ((rc = area_index(mp[k], ms[k], shape, ndim, &mi[k].ai, &mi[k].sy, &mi[k].sx, 3))) return rc;
-    mi[k].sz = mp[k] ? ms[k][ndim - 3] : 0;
-  }
+  for (int k = 0; k < 5; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
   for (int k : {1, 3})
     if (mp[k] && (mi[k].sy != 0 || mi[k].sx != 0))
       return fail(XG_ERR_UNSUPPORTED, "vertical velocity: the second face-weight factor varies along Z (and leading dims) only");
-  const int V = (aligned16(u) && aligned16(v) && aligned16(out) && nx % NV == 0) ? NV : 1;
-  constexpr int SEG = XG_FUSED_SEG;
   constexpr int U = XG_WCONT_WINDOW;
-  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
-  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
-  const u64 per_outer = ntile * nseg;
-  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the vertical velocity kernel");
-  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
-  const u64 outer_per = MAX_ITEMS / per_outer;
-  hipStream_t st = (hipStream_t)stream;
-  const bool nts = tune().nt_store;
   // bit 0: the lane neighbour by DPP (K7d), bits 2 / 3 / 4: the rows of u's factor a / v's factor a / the area are aligned vectors
-  int vnt = tune().nt_load ? (tune().vec_nt & 1) : 0;
+  int vnt = vec_nt_bits(1);
   const int vec_of[3] = {0, 2, 4};
   for (int k = 0; k < 3; ++k) {
     const VolIdx& m = mi[vec_of[k]];
-    if (V > 1 && m.p && m.sz % NV == 0 && plane_vec_ok(m.p, m.ai, m.sy, m.sx)) vnt |= 4 << k;
+    if (p.V > 1 && m.p && m.sz % NV == 0 && plane_vec_ok(m.p, m.ai, m.sy, m.sx)) vnt |= 4 << k;
   }
   const bool fw = mu != nullptr, ar = area != nullptr;
-  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_per) {
-    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_per) ? outer - o0 : (int64_t)outer_per);
-    const u64 waves = (u64)nouter * per_outer;
-    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
-    if ((rc = check_grid((u64)nblk + 8))) return rc;
-    const u32 grid = ((nblk + 7) / 8) * 8;
-#define XG_GO(V_, F_, A_, NTS) do { hipLaunchKernelGGL((k_wcont<V_, F_, A_, NTS, SEG, U>), dim3(grid), dim3(BLOCK), 0, st, u, v, out, o0, nouter, nblk, nz, ny, nx, fnt, fns, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, reverse ? 1 : 0, mi[0], mi[1], mi[2], mi[3], mi[4], vnt); } while (0)
-#define XG_N(V_, F_, A_) do { if (nts) XG_GO(V_, F_, A_, true); else XG_GO(V_, F_, A_, false); } while (0)
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, F_, A_, NTS) do { hipLaunchKernelGGL((k_wcont<V_, F_, A_, NTS, FSEG, U>), dim3(grid), dim3(BLOCK), 0, p.st, u, v, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, reverse ? 1 : 0, mi[0], mi[1], mi[2], mi[3], mi[4], vnt); } while (0)
+#define XG_N(V_, F_, A_) do { if (p.nts) XG_GO(V_, F_, A_, true); else XG_GO(V_, F_, A_, false); } while (0)
 #define XG_A(V_, F_) do { if (ar) XG_N(V_, F_, true); else XG_N(V_, F_, false); } while (0)
 #define XG_V(V_) do { if (fw) XG_A(V_, true); else XG_A(V_, false); } while (0)
-    if (V > 1) XG_V(NV);
+    if (p.V > 1) XG_V(NV);
     else XG_V(1);
 #undef XG_V
 #undef XG_A
 #undef XG_N
 #undef XG_GO
-  }
-  XG_LAUNCH_CHECK();
-  return XG_OK;
+  });
 }
 
 // K7g's launcher
 int XG_FN(xg_kinetic_energy)(const real* u, const real* v, real* out, const int64_t* shape, int ndim, int bc_x, real fill_x,
                              int bc_y, real fill_y, void* stream) {
+  const char* name = "kinetic energy";
   if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
-  if (bc_x < XG_BC_PERIODIC || bc_x > XG_BC_EXTEND || bc_y < XG_BC_PERIODIC || bc_y > XG_BC_EXTEND)
-    return fail(XG_ERR_INVALID, "kinetic energy needs a periodic, fill or extend boundary on both axes");
-  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
-  int64_t outer = 1;
-  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
-  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
-  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Y,X) planes");
-  const int V = (aligned16(u) && aligned16(v) && aligned16(out) && nx % NV == 0) ? NV : 1;
-  constexpr int SEG = XG_FUSED_SEG;
-  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
-  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
-  const u64 per_outer = ntile * nseg;
-  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the kinetic energy kernel");
-  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
-  const u64 outer_per = MAX_ITEMS / per_outer;
-  hipStream_t st = (hipStream_t)stream;
-  const bool nts = tune().nt_store;
-  const int vnt = tune().nt_load ? (tune().vec_nt & 1) : 0;  // bit 0: the right neighbour by DPP (K7d)
   int rc;
-  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_per) {
-    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_per) ? outer - o0 : (int64_t)outer_per);
-    const u64 waves = (u64)nouter * per_outer;
-    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
-    if ((rc = check_grid((u64)nblk + 8))) return rc;
-    const u32 grid = ((nblk + 7) / 8) * 8;
-#define XG_GO(V_, NTS) do { hipLaunchKernelGGL((k_kinetic<V_, NTS, SEG>), dim3(grid), dim3(BLOCK), 0, st, u, v, out, o0, nouter, nblk, ny, nx, fnt, fns, bc_x, fill_x, bc_y, fill_y, vnt); } while (0)
-    if (V > 1) { if (nts) XG_GO(NV, true); else XG_GO(NV, false); }
-    else { if (nts) XG_GO(1, true); else XG_GO(1, false); }
+  if ((rc = fused_dims(name, ndim, 2, {bc_x, bc_y}, XG_BC_EXTEND))) return rc;
+  FusedPlan p;
+  if ((rc = fused_plan(&p, name, shape, ndim, 2, aligned16(u) && aligned16(v) && aligned16(out), true, stream)) || p.empty) return rc;
+  const int vnt = vec_nt_bits(1);  // bit 0: the right neighbour by DPP (K7d)
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, NTS) do { hipLaunchKernelGGL((k_kinetic<V_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, u, v, out, o0, nouter, nblk, p.ny, p.nx, p.fnt, p.fns, bc_x, fill_x, bc_y, fill_y, vnt); } while (0)
+    if (p.V > 1) { if (p.nts) XG_GO(NV, true); else XG_GO(NV, false); }
+    else { if (p.nts) XG_GO(1, true); else XG_GO(1, false); }
 #undef XG_GO
-  }
-  XG_LAUNCH_CHECK();
-  return XG_OK;
+  });
 }
 
 // K7h's launcher: the three metrics all or none; the coriolis plane on its own
@@ -1935,18 +1771,15 @@ int XG_FN(xg_momentum_advection)(const real* u, const real* v, const real* corio
                                  const real* rAz, const int64_t* rAz_strides, const real* dxC, const int64_t* dxC_strides,
                                  const real* dyC, const int64_t* dyC_strides, real* out_u, real* out_v,
                                  const int64_t* shape, int ndim, int bc_x, real fill_x, int bc_y, real fill_y, void* stream) {
+  const char* name = "momentum advection";
   if (!u || !v || !out_u || !out_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
-  if (bc_x < XG_BC_PERIODIC || bc_x > XG_BC_EXTEND || bc_y < XG_BC_PERIODIC || bc_y > XG_BC_EXTEND)
-    return fail(XG_ERR_INVALID, "momentum advection needs a periodic, fill or extend boundary on both axes");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 2, {bc_x, bc_y}, XG_BC_EXTEND))) return rc;
   const int nmet = (rAz != nullptr) + (dxC != nullptr) + (dyC != nullptr);
   if (nmet != 0 && nmet != 3) return fail(XG_ERR_INVALID, "momentum advection: the three metrics rAz, dxC, dyC, or none");
-  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
-  int64_t outer = 1;
-  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
-  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
-  if (outer > 0xffffffffll) return fail(XG_ERR_UNSUPPORTED, "more than 2^32 (Y,X) planes");
-  int rc;
+  FusedPlan p;
+  const bool al = aligned16(u) && aligned16(v) && aligned16(out_u) && aligned16(out_v);
+  if ((rc = fused_plan(&p, name, shape, ndim, 2, al, true, stream)) || p.empty) return rc;
   Div2dMet mt;
   memset(&mt, 0, sizeof(mt));
   const real* mp[4] = {rAz, coriolis, dxC, dyC};
@@ -1955,61 +1788,32 @@ int XG_FN(xg_momentum_advection)(const real* u, const real* v, const real* corio
     mt.p[k] = mp[k];
     if ((rc = area_index(mp[k], ms[k], shape, ndim, &mt.ai[k], &mt.sy[k], &mt.sx[k]))) return rc;
   }
-  const int V = (aligned16(u) && aligned16(v) && aligned16(out_u) && aligned16(out_v) && nx % NV == 0) ? NV : 1;
-  constexpr int SEG = XG_FUSED_SEG;
-  const u64 ntile = (u64)((nx + (int64_t)WAVE * V - 1) / ((int64_t)WAVE * V));
-  const u64 nseg = (u64)((ny + SEG - 1) / SEG);
-  const u64 per_outer = ntile * nseg;
-  if (per_outer > MAX_ITEMS) return fail(XG_ERR_UNSUPPORTED, "extent too large for the momentum advection kernel");
-  const FastDiv fnt = make_fastdiv(ntile), fns = make_fastdiv(nseg);
-  const u64 outer_per = MAX_ITEMS / per_outer;
-  hipStream_t st = (hipStream_t)stream;
-  const bool nts = tune().nt_store;
   // bit 0: the lane neighbours by DPP (K7d), bit 3: every plane that is there is an aligned vector in every row
-  int vnt = tune().nt_load ? (tune().vec_nt & 1) : 0;
+  int vnt = vec_nt_bits(1);
   const bool met = nmet != 0, cor = coriolis != nullptr;
+  bool all_shared = met || cor;
   if (met || cor) {
-    bool mv = V > 1;
-    for (int k = 0; k < 4; ++k)
+    bool mv = p.V > 1;
+    for (int k = 0; k < 4; ++k) {
       if (mt.p[k]) mv = mv && plane_vec_ok(mt.p[k], mt.ai[k], mt.sy[k], mt.sx[k]);
+      all_shared = all_shared && planes_shared(mt.p[k], mt.ai[k]);
+    }
     vnt |= mv ? 8 : 0;
   }
-  // planes shared by every outer index (2-D metrics under a (Z, Y, X) field): band-major order, 8-row bands as the weighted
-  // laplacian's five planes (K7d)
-  bool all_shared = met || cor;
-  for (int k = 0; k < 4; ++k)
-    for (int d = 0; mt.p[k] && d < mt.ai[k].n; ++d)
-      if (mt.ai[k].stride[d] != 0) all_shared = false;
-  const u32 zbr = (u32)(tune().vec_zb_rows > 1 ? tune().vec_zb_rows : 16);
-  const u32 ZB_SEGS = (u32)(((zbr + 1) / 2 + SEG - 1) / SEG);
-  ZBand zb = make_zband(false, 0, 0, 1);
-  u64 outer_step = outer_per;
-  if (all_shared && tune().zband && outer >= 2) {
-    const u64 padded = ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile;
-    if (padded <= MAX_ITEMS) {
-      zb = make_zband(true, (u64)outer, nseg, ZB_SEGS);
-      if (zb.on) outer_step = (u64)outer;
-    }
-  }
-  for (int64_t o0 = 0; o0 < outer; o0 += (int64_t)outer_step) {
-    const u32 nouter = (u32)((outer - o0 < (int64_t)outer_step) ? outer - o0 : (int64_t)outer_step);
-    const u64 waves = zb.on ? ((nseg + ZB_SEGS - 1) / ZB_SEGS) * ZB_SEGS * (u64)outer * ntile : (u64)nouter * per_outer;
-    const u32 nblk = (u32)((waves + WPB - 1) / WPB);
-    if ((rc = check_grid((u64)nblk + 8))) return rc;
-    const u32 grid = ((nblk + 7) / 8) * 8;
-#define XG_GO(V_, M_, C_, NTS) do { hipLaunchKernelGGL((k_momadv<V_, M_, C_, NTS, SEG>), dim3(grid), dim3(BLOCK), 0, st, u, v, out_u, out_v, o0, nouter, nblk, ny, nx, fnt, fns, zb, bc_x, fill_x, bc_y, fill_y, mt, vnt); } while (0)
-#define XG_N(V_, M_, C_) do { if (nts) XG_GO(V_, M_, C_, true); else XG_GO(V_, M_, C_, false); } while (0)
+  // 8-row bands as the weighted laplacian's five planes (K7d)
+  fused_band(&p, all_shared, (band_rows() + 1) / 2, (u64)p.outer);
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, C_, NTS) do { hipLaunchKernelGGL((k_momadv<V_, M_, C_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, u, v, out_u, out_v, o0, nouter, nblk, p.ny, p.nx, p.fnt, p.fns, p.zb, bc_x, fill_x, bc_y, fill_y, mt, vnt); } while (0)
+#define XG_N(V_, M_, C_) do { if (p.nts) XG_GO(V_, M_, C_, true); else XG_GO(V_, M_, C_, false); } while (0)
 #define XG_C(V_, M_) do { if (cor) XG_N(V_, M_, true); else XG_N(V_, M_, false); } while (0)
 #define XG_V(V_) do { if (met) XG_C(V_, true); else XG_C(V_, false); } while (0)
-    if (V > 1) XG_V(NV);
+    if (p.V > 1) XG_V(NV);
     else XG_V(1);
 #undef XG_V
 #undef XG_C
 #undef XG_N
 #undef XG_GO
-  }
-  XG_LAUNCH_CHECK();
-  return XG_OK;
+  });
 }
 
 #endif  // !XG_INT
