@@ -42,6 +42,7 @@
  *                      docs/ufunc_examples.md) and the finite-volume del2, two-step chains in one pass
  *   xg_flux_divergence3d_f64  the same with the vertical flux w * interp(T, Z), divided by the cell volume
  *   xg_vertical_velocity_f64  w from continuity: -cumsum(divergence(u, v), Z) / area, one pass
+ *   xg_hydrostatic_pressure_gradient_f64  gradient(interp(cumint(b, Z), Z)): the pressure-gradient force, one pass
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -390,6 +391,23 @@ int xg_vertical_velocity_f64(const double* u, const double* v, const double* mu,
                              const double* mv2, const int64_t* mv2_strides, const double* area,
                              const int64_t* area_strides, double* out, const int64_t* shape, int ndim, int bc_x,
                              double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, int reverse, void* stream);
+/* The horizontal gradient of the hydrostatic pressure, one pass over arrays of identical `shape` (.., Z, Y, X): b (buoyancy,
+ * or g rho / rho0) at the centre, out_x at (Z:c, Y:c, X:left), out_y at (Z:c, Y:left, X:c).  It replaces the chain
+ *   p  = nancumsum of b * w along Z, center -> outer   xg_cumsum1d_f64 with skipna: a NaN product counts as 0, levels added
+ *                                                      in sequence from index 0 (w NULL: b itself); p has nz + 1 levels
+ *   pc = (p[k] + p[k+1]) / 2                           xg_stencil1d_f64 interp, outer -> center, no pad
+ *   out_x = (pc[i] - pc[i-1]) / dxC,  out_y = (pc[j] - pc[j-1]) / dyC      xg_gradient_f64 (dxC / dyC NULL: no division)
+ * p[0] is the Z pad (XG_BC_FILL: fill_z, XG_BC_EXTEND: p[1]) and p[k] = t[0] + .. + t[k-1] with t = b * w, the first sum
+ * t[0] itself.  XG_BC_PERIODIC along Z needs the column total first and is refused (XG_ERR_UNSUPPORTED): run the chain.
+ * The gradient pads pc below the first row and left of the first column -- periodic: pc at the wrapped index, extend: at
+ * the clamped index, fill: fill_x / fill_y itself.  The form for a model whose Z index grows downward from the surface.
+ * Argument order: the field, then (pointer, strides) of the Z weight, of dxC and of dyC, then the two outputs, shape, ndim
+ * and the boundary codes (XG_BC_PERIODIC, XG_BC_FILL, XG_BC_EXTEND; XG_BC_HALO is not accepted) with their fill values for
+ * X, Y and Z.  Every metric uses broadcast strides (0 = broadcast) against `shape`. */
+int xg_hydrostatic_pressure_gradient_f64(const double* b, const double* w, const int64_t* w_strides, const double* dxC,
+                                         const int64_t* dxC_strides, const double* dyC, const int64_t* dyC_strides,
+                                         double* out_x, double* out_y, const int64_t* shape, int ndim, int bc_x,
+                                         double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
 
 /* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
 /* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).
@@ -530,6 +548,10 @@ int xg_vertical_velocity_f32(const float* u, const float* v, const float* mu, co
                              const float* mv2, const int64_t* mv2_strides, const float* area,
                              const int64_t* area_strides, float* out, const int64_t* shape, int ndim, int bc_x,
                              float fill_x, int bc_y, float fill_y, int bc_z, float fill_z, int reverse, void* stream);
+int xg_hydrostatic_pressure_gradient_f32(const float* b, const float* w, const int64_t* w_strides, const float* dxC,
+                                         const int64_t* dxC_strides, const float* dyC, const int64_t* dyC_strides,
+                                         float* out_x, float* out_y, const int64_t* shape, int ndim, int bc_x,
+                                         float fill_x, int bc_y, float fill_y, int bc_z, float fill_z, void* stream);
 int xg_kinetic_energy_f32(const float* u, const float* v, float* out, const int64_t* shape, int ndim, int bc_x,
                           float fill_x, int bc_y, float fill_y, void* stream);
 int xg_momentum_advection_f32(const float* u, const float* v, const float* coriolis, const int64_t* coriolis_strides,

@@ -100,6 +100,7 @@ def main():
         "lapT": (lambda: D.laplacian(T, "periodic", "extend", 0.0, 0.0, dx, dx2, dx2, dx, dx), 16 + 16 / nz),  # del2: its five metrics from two planes
         "adv3": (lambda: D.flux_divergence_3d(U, V, W, T, dx, dz, "periodic", "extend", "extend"), 40 + 8 / nz),  # 3-D flux divergence / (rA * drF)
         "wcont": (lambda: D.vertical_velocity(U, V, None, None, None, None, dx, "periodic", "extend", "fill"), 24 + 8 / nz),  # w from continuity / rA
+        "pgrad": (lambda: D.hydrostatic_pressure_gradient(T, dz, dx, dx2, "periodic", "extend", "fill"), 24 + 16 / nz),  # pressure-gradient force: drF, dxC, dyC
         "keUV": (lambda: D.kinetic_energy(U, V, "periodic", "extend"), 24),  # 0.5 * (interp(u*u, X) + interp(v*v, Y))
         "madv": (lambda: D.momentum_advection(U, V, dx2, dx, dx2, dx, "periodic", "extend"), 32 + 16 / nz),  # vector-invariant advection + Coriolis: its four planes from two
     }

@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection against their chains), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient against their chains; 5pg: the last pair alone), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -76,6 +76,49 @@ def timeit_interleaved(fa, fb, reps):
     ta = sorted(ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(reps))
     tb = sorted(ev[2 * i + 1].elapsed_time(ev[2 * i + 2]) for i in range(reps))
     return ta[len(ta) // 2], tb[len(tb) // 2]
+
+
+def timeit_rounds(fa, fb, reps):
+    """`fa` and `fb` timed in turns as timeit_interleaved does, every round kept: ([ms of fa], [ms of fb])"""
+    fa()
+    fb()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * reps + 1)]
+    ev[0].record()
+    for i in range(reps):
+        fa()
+        ev[2 * i + 1].record()
+        fb()
+        ev[2 * i + 2].record()
+    torch.cuda.synchronize()
+    return ([ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(reps)],
+            [ev[2 * i + 1].elapsed_time(ev[2 * i + 2]) for i in range(reps)])
+
+
+def run_pressure_gradient(reps, nz=90, n=4320):
+    """hydrostatic_pressure_gradient in one pass against its chain of three launches (cumint to the outer position, interp,
+    gradient) on the MITgcm grid (drF, dxC, dyC; periodic / extend / fill), timed in turns, every paired round reported"""
+    grid = mitgcm_grid(nz, n, n)
+    B = DataArray(D.synthetic((nz, n, n), 56), ("Z", "YC", "XC"))
+    cells = nz * n * n
+
+    def chain():
+        pc = grid.interp(grid.cumint(B, "Z", to="outer"), "Z")
+        return grid.gradient(pc, metric_weighted=True)
+
+    gx, gy = grid.hydrostatic_pressure_gradient(B)
+    wx, wy = chain()
+    ok = bool(torch.equal(gx.data, wx.data) and torch.equal(gy.data, wy.data))
+    del gx, gy, wx, wy
+    torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(lambda: grid.hydrostatic_pressure_gradient(B), chain, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    rec(5, "hydrostatic_pressure_gradient fused gradient(interp(cumint(b, Z), Z)) / (dxC, dyC), periodic/extend/fill: 1 read + 2 writes", med(tf), cells, 24 + 16 / nz)
+    rec(5, "hydrostatic_pressure_gradient as its chain (3 launches), fused-equivalent bytes", med(tc), cells, 24 + 16 / nz)
+    print(json.dumps({"config": 5, "check": "fused hydrostatic_pressure_gradient == chain bit for bit at full size", "ok": ok,
+                      "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
+                      "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
 
 
 def rec(cfg, name, ms, cells, bpc):
@@ -707,6 +750,10 @@ def main():
         okm = bool(torch.equal(gu.data, wu.data) and torch.equal(gv.data, wv.data))
         print(json.dumps({"config": 5, "check": "fused momentum_advection == chain bit for bit at full size", "ok": okm,
                           "speedup": round(t_c / t_f, 2)}), flush=True)
+        del U, V, F5
+        torch.cuda.empty_cache()
+    if cfgs & {"5x", "5pg"}:
+        run_pressure_gradient(a.reps)
     ranks.close()
 
 

@@ -545,6 +545,68 @@ int wcont(const R* u, const R* v, const R* const met[5], const int64_t* const ms
   return XG_OK;
 }
 
+// the hydrostatic pressure gradient of the header, stage by stage over one (Z, Y, X) volume at a time: the pressure at the
+// nz + 1 interfaces, its mean at the cell centres, then the two differences of that field with their own pads.
+// met[] = {Z weight, dxC, dyC}
+template <typename R>
+int pgrad(const R* b, const R* const met[3], const int64_t* const ms[3], R* out_x, R* out_y, const int64_t* shape, int ndim,
+          int bc_x, R fill_x, int bc_y, R fill_y, int bc_z, R fill_z) {
+  if (!b || !out_x || !out_y || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  for (int c : {bc_x, bc_y, bc_z})
+    if (c < XG_BC_PERIODIC || c > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", c);
+  if (bc_z != XG_BC_FILL && bc_z != XG_BC_EXTEND)
+    return fail(XG_ERR_UNSUPPORTED, "hydrostatic pressure gradient pads Z with fill or extend");
+  for (int k = 0; k < 3; ++k)
+    if (met[k] && !ms[k]) return fail(XG_ERR_INVALID, "metric without strides");
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx;
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 3; ++d) outer *= shape[d];
+  if (outer == 0 || nz == 0 || plane == 0) return XG_OK;
+  std::vector<R> p((size_t)((nz + 1) * plane)), pc((size_t)(nz * plane));
+  for (int64_t o = 0; o < outer; ++o) {
+    int64_t rem = o, moff[3] = {0, 0, 0};  // the lead index decomposed for the broadcast strides
+    for (int d = ndim - 4; d >= 0; --d) {
+      const int64_t i = rem % shape[d];
+      rem /= shape[d];
+      for (int k = 0; k < 3; ++k)
+        if (met[k]) moff[k] += i * ms[k][d];
+    }
+    auto m = [&](int k, int64_t z, int64_t j, int64_t i) {
+      return met[k][moff[k] + z * ms[k][ndim - 3] + j * ms[k][ndim - 2] + i * ms[k][ndim - 1]];
+    };
+    const R* pb = b + o * nz * plane;
+    // (1) the interfaces: p[z + 1] = the nan-sum of b * w through level z, p[0] the pad
+    for (int64_t z = 0; z < nz; ++z)
+      for (int64_t c = 0; c < plane; ++c) {
+        R t = met[0] ? pb[z * plane + c] * m(0, z, c / nx, c % nx) : pb[z * plane + c];
+        if (t != t) t = R(0);
+        p[(z + 1) * plane + c] = z == 0 ? t : p[z * plane + c] + t;
+      }
+    for (int64_t c = 0; c < plane; ++c) p[c] = bc_z == XG_BC_FILL ? fill_z : p[plane + c];
+    // (2) the centres
+    for (int64_t z = 0; z < nz; ++z)
+      for (int64_t c = 0; c < plane; ++c) pc[z * plane + c] = (p[z * plane + c] + p[(z + 1) * plane + c]) / R(2);
+    // (3) the differences towards the left points
+    for (int64_t z = 0; z < nz; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const R* q = pc.data() + z * plane;
+          const R here = q[j * nx + i];
+          const R left = i > 0 ? q[j * nx + i - 1]
+                               : (bc_x == XG_BC_FILL ? fill_x : q[j * nx + (bc_x == XG_BC_PERIODIC ? nx - 1 : 0)]);
+          const R below = j > 0 ? q[(j - 1) * nx + i]
+                                : (bc_y == XG_BC_FILL ? fill_y : q[(bc_y == XG_BC_PERIODIC ? ny - 1 : 0) * nx + i]);
+          R gx = here - left, gy = here - below;
+          if (met[1]) gx = gx / m(1, z, j, i);
+          if (met[2]) gy = gy / m(2, z, j, i);
+          out_x[(o * nz + z) * plane + j * nx + i] = gx;
+          out_y[(o * nz + z) * plane + j * nx + i] = gy;
+        }
+  }
+  return XG_OK;
+}
+
 // kinetic energy (ke_only) and the vector-invariant momentum advection of the header: the stages of the chain one after
 // the other over whole planes, each read through `get`, which pads a plane by one cell on one axis at a time (periodic:
 // the plane's own value at the wrapped index, extend: at the clamped index, fill: the fill value of that axis).
@@ -841,6 +903,14 @@ int xg_event_destroy(void* ev) { free(ev); return XG_OK; }
     const R* const met[5] = {mu, mu2, mv, mv2, area};                                                                 \
     const int64_t* const ms[5] = {mus, mu2s, mvs, mv2s, as};                                                          \
     return wcont<R>(u, v, met, ms, out, shape, ndim, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, reverse);             \
+  }                                                                                                                   \
+  int xg_hydrostatic_pressure_gradient_##SFX(const R* b, const R* w, const int64_t* ws, const R* dxC,                 \
+                                             const int64_t* dxCs, const R* dyC, const int64_t* dyCs, R* out_x,         \
+                                             R* out_y, const int64_t* shape, int ndim, int bc_x, R fill_x, int bc_y,   \
+                                             R fill_y, int bc_z, R fill_z, void*) {                                    \
+    const R* const met[3] = {w, dxC, dyC};                                                                            \
+    const int64_t* const ms[3] = {ws, dxCs, dyCs};                                                                    \
+    return pgrad<R>(b, met, ms, out_x, out_y, shape, ndim, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z);                \
   }                                                                                                                   \
   int xg_kinetic_energy_##SFX(const R* u, const R* v, R* out, const int64_t* shape, int ndim, int bc_x, R fill_x,     \
                               int bc_y, R fill_y, void*) {                                                            \

@@ -1237,6 +1237,203 @@ __global__ __launch_bounds__(BLOCK) void k_momadv(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7i: the horizontal gradient of the hydrostatic pressure in ONE pass over (lead, Z, Y, X), one field in, two out:
+//   t[k]  = nan0(b[k] * w[k])                     the weighted buoyancy, a NaN product counts as 0 (the scans' nancumsum)
+//   p[0]  = Z pad (fill: fill_z, extend: p[1]),   p[k+1] = t[0] + .. + t[k], added in sequence (the first sum is t[0] itself)
+//   pc[k] = (p[k] + p[k+1]) / 2                   outer -> center, no pad
+//   gx = (pc[i] - pc[i-1]) [/ dxC],  gy = (pc[j] - pc[j-1]) [/ dyC]      K7c's gradient, its X / Y boundaries
+// i.e. cumint (center -> outer) -> interp -> gradient.  K7f's decomposition: a wave owns one (lead, Y segment, X tile) column
+// and marches Z forward with the running sums in registers, so b is read once and gx, gy written once: 24 B/cell in float64
+// against about 56 for the chain.  pc of the row below the segment comes from that row's own running sum, marched in the same
+// wave (1 + 1/SEG reads of b, the extra row an L2 hit: it is the segment before's last row); pc left of the lane's vector
+// comes from the lane before it, which formed it with the same arithmetic (DPP, K7c's move) -- only the tile's first lane
+// (and every lane of the narrow form) marches that column's sum itself.  Fill / extend at row 0 / column 0 need neither.
+// The loads form K7f's rolling window of levels ahead of the sums.  The Z weight is one wave-uniform load per level when it
+// varies along Z (and leading dims) only, else its rows are read with the level; the dxC / dyC rows stay in registers
+// unless they vary along Z.
+// ------------------------------------------------------------------------------------------
+template <typename T, int SEG>
+struct PgLevel {  // what one level of a column brings: SEG rows of b with the element left of the lane, the row below them
+  T bb[SEG], bel;
+  real bl[SEG];
+};
+
+// one cell's step: the product, the next running sum (kept in `acc`), the mean of the two sums around the level
+template <typename A>
+__device__ __forceinline__ A pg_cell(A& acc, A prod, bool started, bool zfill, real fill_z) {
+  const A t = nan0(prod);
+  const A nxt = started ? acc + t : t;
+  const A prv = started ? acc : (zfill ? splat<A>(fill_z) : nxt);
+  acc = nxt;
+  return op2<XG_OP_INTERP>(prv, nxt);
+}
+
+template <int V, bool MET, bool NTS, int SEG, int U>
+__global__ __launch_bounds__(BLOCK) void k_pgrad(
+    const real* __restrict__ b, real* __restrict__ out_x, real* __restrict__ out_y, int64_t o0, u32 nouter, u32 nblk,
+    int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
+    real fill_z, VolIdx wz, VolIdx mx, VolIdx my, int ntl) {
+  typedef typename VecT<V>::type T;
+  typedef PgLevel<T, SEG> L;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  // X as K7c: the column left of the lane's vector (periodic: column nx - 1 left of column 0); `march_l`: this lane forms
+  // that column's pc itself -- not at a fill / extend edge, where the pad replaces it
+  const bool edge_l = (i0 == 0);
+  const bool per_x = bc_x == XG_BC_PERIODIC;
+  const int64_t lidx = edge_l ? (per_x ? nx - 1 : 0) : i0 - 1;
+  const bool shl = V > 1 && (ntl & 1);
+  const bool own_l = !shl || (threadIdx.x & 63) == 0 || edge_l;
+  const bool march_l = own_l && !(edge_l && !per_x);
+  // Y: the row below the segment (periodic: row ny - 1 below row 0); wave-uniform
+  const bool edge_b = (j0 == 0);
+  const bool march_b = !(edge_b && bc_y != XG_BC_PERIODIC);
+  const int64_t jb = edge_b ? (march_b ? ny - 1 : 0) : j0 - 1;
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+  const real* pb = b + col;
+
+  auto fetch = [&](int64_t k) -> L {
+    L x;
+    const real* pk = pb + k * plane;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.bb[s_] = *reinterpret_cast<const T*>(pk + ro[s_] + i0);
+      x.bl[s_] = march_l ? pk[ro[s_] + lidx] : real(0);
+    }
+    x.bel = march_b ? *reinterpret_cast<const T*>(pk + jb * nx + i0) : splat<T>(real(0));
+    return x;
+  };
+
+  // the Z weight: `wflat` (it varies along Z and leading dims only) is one wave-uniform load per level
+  const bool wflat = wz.sy == 0 && wz.sx == 0;
+  const int64_t wzo = wz.p ? area_outer_off(wz.ai, o) : 0;
+  // dxC / dyC rows: in registers, loaded again per level only when the plane varies along Z
+  T dxr[SEG], dyr[SEG];
+  int64_t mxo = 0, myo = 0;
+  if (MET) {
+    if (mx.p) {
+      mxo = area_outer_off(mx.ai, o) + j0 * mx.sy + i0 * mx.sx;
+      load_rows<T, SEG>(dxr, mx.p, mxo, mx.sy, mx.sx, nrow, (ntl & 8) != 0);
+    }
+    if (my.p) {
+      myo = area_outer_off(my.ai, o) + j0 * my.sy + i0 * my.sx;
+      load_rows<T, SEG>(dyr, my.p, myo, my.sy, my.sx, nrow, (ntl & 16) != 0);
+    }
+  }
+
+  T p[SEG], pbel = splat<T>(real(0));  // the running sums p[k]: the segment's rows, the row below, the column to the left
+  real pl[SEG];
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    p[s_] = splat<T>(real(0));
+    pl[s_] = real(0);
+  }
+  const bool zfill = bc_z == XG_BC_FILL;
+  bool started = false;
+  real* px = out_x + col + j0 * nx + i0;
+  real* py = out_y + col + j0 * nx + i0;
+
+  auto step = [&](int64_t k, const L& x) {
+    T tc[SEG], tb = x.bel;
+    real tl[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      tc[s_] = x.bb[s_];
+      tl[s_] = x.bl[s_];
+    }
+    if (wz.p) {
+      const int64_t wk = wzo + k * wz.sz;
+      if (wflat) {
+        const real zw = wz.p[wk];
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) {
+          tc[s_] = tc[s_] * splat<T>(zw);
+          tl[s_] = tl[s_] * zw;
+        }
+        tb = tb * splat<T>(zw);
+      } else {
+        T wr[SEG], wb[1];
+        real wl[SEG];
+        load_rows<T, SEG>(wr, wz.p, wk + j0 * wz.sy + i0 * wz.sx, wz.sy, wz.sx, nrow, (ntl & 4) != 0);
+        load_rows<T, 1>(wb, wz.p, wk + jb * wz.sy + i0 * wz.sx, wz.sy, wz.sx, 1, (ntl & 4) != 0);
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_)
+          wl[s_] = march_l ? wz.p[wk + (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * wz.sy + lidx * wz.sx] : real(0);
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) {
+          tc[s_] = tc[s_] * wr[s_];
+          tl[s_] = tl[s_] * wl[s_];
+        }
+        tb = tb * wb[0];
+      }
+    }
+    if (MET && k > 0) {
+      if (mx.p && mx.sz != 0) load_rows<T, SEG>(dxr, mx.p, mxo + k * mx.sz, mx.sy, mx.sx, nrow, (ntl & 8) != 0);
+      if (my.p && my.sz != 0) load_rows<T, SEG>(dyr, my.p, myo + k * my.sz, my.sy, my.sx, nrow, (ntl & 16) != 0);
+    }
+    T pc[SEG];
+    real pcl[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      pc[s_] = pg_cell(p[s_], tc[s_], started, zfill, fill_z);
+      pcl[s_] = pg_cell(pl[s_], tl[s_], started, zfill, fill_z);
+    }
+    const T pcb = pg_cell(pbel, tb, started, zfill, fill_z);
+    started = true;
+    if (shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real left = from_lane_below(vec_last(pc[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+        if (!own_l) pcl[s_] = left;
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        real left = pcl[s_];
+        if (edge_l && !per_x) left = (bc_x == XG_BC_FILL) ? fill_x : vec_first(pc[s_]);
+        T below = (s_ == 0) ? pcb : pc[(s_ > 0) ? s_ - 1 : 0];
+        if (s_ == 0 && !march_b) below = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : pc[0];
+        T gx = dvdx_of(pc[s_], left);
+        T gy = pc[s_] - below;
+        if (MET) {
+          if (mx.p) gx = gx / dxr[s_];
+          if (my.p) gy = gy / dyr[s_];
+        }
+        stg_s<T, NTS>(px + k * plane + s_ * nx, gx);
+        stg_s<T, NTS>(py + k * plane + s_ * nx, gy);
+      }
+    }
+  };
+
+  // the rolling window (K7f's): every consumed level is replaced by the load of the level U steps ahead
+  L win[U];
+#pragma unroll
+  for (int q = 0; q < U; ++q)
+    if (q < nz) win[q] = fetch(q);
+  int64_t k = 0;
+  for (; k + 2 * U <= nz; k += U) {
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const L x = win[q];
+      win[q] = fetch(k + U + q);
+      step(k + q, x);
+    }
+  }
+  for (; k < nz; k += U) {  // the last one or two windows: refills and consumes guarded (wave-uniform tests)
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const L x = win[q];
+      if (k + U + q < nz) win[q] = fetch(k + U + q);
+      if (k + q < nz) step(k + q, x);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -1811,6 +2008,45 @@ int XG_FN(xg_momentum_advection)(const real* u, const real* v, const real* corio
     else XG_V(1);
 #undef XG_V
 #undef XG_C
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+// K7i's launcher: (lead, Z, Y, X) fields, three optional broadcast metrics (the Z weight, dxC, dyC), one wave per column
+#ifndef XG_PGRAD_WINDOW
+#define XG_PGRAD_WINDOW XG_WCONT_WINDOW  // levels in flight ahead of the running sums
+#endif
+int XG_FN(xg_hydrostatic_pressure_gradient)(const real* b, const real* w, const int64_t* w_strides, const real* dxC,
+                                            const int64_t* dxC_strides, const real* dyC, const int64_t* dyC_strides,
+                                            real* out_x, real* out_y, const int64_t* shape, int ndim, int bc_x, real fill_x,
+                                            int bc_y, real fill_y, int bc_z, real fill_z, void* stream) {
+  const char* name = "hydrostatic pressure gradient";
+  if (!b || !out_x || !out_y || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (bc_z != XG_BC_FILL && bc_z != XG_BC_EXTEND)
+    return fail(XG_ERR_UNSUPPORTED, "hydrostatic pressure gradient pads Z with fill or extend (periodic needs the column total first)");
+  FusedPlan p;
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, aligned16(b) && aligned16(out_x) && aligned16(out_y), true, stream)) || p.empty) return rc;
+  VolIdx mi[3];  // the Z weight, dxC, dyC
+  const real* mp[3] = {w, dxC, dyC};
+  const int64_t* ms[3] = {w_strides, dxC_strides, dyC_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  constexpr int U = XG_PGRAD_WINDOW;
+  // bit 0: the lane neighbour by DPP (K7c), bits 2 / 3 / 4: the rows of the Z weight / dxC / dyC are aligned vectors
+  int vnt = vec_nt_bits(1);
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool met = dxC != nullptr || dyC != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_pgrad<V_, M_, NTS, FSEG, U>), dim3(grid), dim3(BLOCK), 0, p.st, b, out_x, out_y, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt); } while (0)
+#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
 #undef XG_N
 #undef XG_GO
   });

@@ -1266,6 +1266,33 @@ def vertical_velocity(u, v, mu, mu2, mv, mv2, area, bc_x: str, bc_y: str, bc_z: 
     return out
 
 
+def hydrostatic_pressure_gradient(b, w, dxC, dyC, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0, fill_y: float = 0.0,
+                                  fill_z: float = 0.0):
+    """Fused gradient of the hydrostatic pressure in one pass (xg_hydrostatic_pressure_gradient_f64): the nancumsum of
+    b * w along Z from the centre to the outer position (the Z pad at level 0), its mean at the centre, and that field's
+    differences towards the left points along X and Y, divided by `dxC` / `dyC` (None = no division; `w` None = b itself).
+    Returns (gx, gy)."""
+    lib = _MEM.lib()
+    dt, sfx = _common(b, w, dxC, dyC)
+    b = asdevice(b, dt)
+    shape = list(b.shape)
+    mets = [_prep_metric(m, dt) for m in (w, dxC, dyC)]
+    out_x = _empty(shape, dtype=dt, device=b.device)
+    out_y = _empty(shape, dtype=dt, device=b.device)
+    if out_x.numel() == 0:
+        return out_x, out_y
+    margs = []
+    for m, what in zip(mets, ("Z weight", "dxC", "dyC")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
+    _check(
+        getattr(lib, "xg_hydrostatic_pressure_gradient_" + sfx)(b.data_ptr(), *margs, out_x.data_ptr(), out_y.data_ptr(),
+                                                                _hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x),
+                                                                _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z),
+                                                                _stream())
+    )
+    return out_x, out_y
+
+
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""

@@ -1574,6 +1574,87 @@ class Grid:
         res = res._replace(data=_dev.tohost(out) if host else out)
         return to_xarray(res) if was_xr else res
 
+    def hydrostatic_pressure_gradient(self, b, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", padding=None,
+                                      fill_value=None, metric_weighted: bool = True):
+        """Horizontal gradient of the hydrostatic pressure (the pressure-gradient force of the hydrostatic momentum
+        equations, and what geostrophic and thermal-wind velocities are formed from) in ONE pass: the buoyancy `b` (or
+        g * rho / rho0) is read once and the two components written once (24 B/cell in float64, against about 56 for the
+        chain); the running sum of a column stays in registers.  Returns `(gx, gy)`.
+
+        b at (Z:center, Y:center, X:center); gx at (Z:center, Y:center, X:left), gy at (Z:center, Y:left, X:center), where
+        `momentum_advection` puts its tendencies.  The Z axis needs an `outer` position (MITgcm's Zp1).  Bit-identical,
+        dims, coords and names included, to the chain
+
+            kw = dict(padding=padding, fill_value=fill_value)
+            p = grid.cumint(b, z_axis, to="outer", **kw)      # (Z:outer, Y, X): p[0] = Z pad, p[k] = sum_{m<k} b[m] * w[m]
+            pc = grid.interp(p, z_axis, **kw)                 # outer -> center, no pad: (p[k] + p[k+1]) / 2
+            gx, gy = grid.gradient(pc, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+
+        The sum runs forward from index 0 -- the form for a model whose Z index grows downward from the surface -- and
+        p[0] is the Z pad: `fill_value` under `fill`, p[1] under `extend`.  It is `Grid.cumsum`'s nancumsum taken in
+        sequence: a NaN product b * w counts as 0, and the first sum is the product itself.  The vertical weight (what
+        `get_metric(b, (z_axis,))` returns: drF(Z), or a registered (Z, Y, X) thickness) is always applied;
+        `metric_weighted` goes to the gradient only.  The gradient pads pc below and left of the first cell -- periodic:
+        pc at the wrapped index, extend: at the clamped index, fill: `fill_value` itself.
+
+        The chain itself runs (the same calls in the same order) for integer, float16 or mixed dtypes, for (Z, Y, X) not
+        last, for chunked host arrays, for periodic Z (the pad is the column total) or a missing boundary (the chain
+        raises), for a single column (ny * nx == 1), for a metric with dims the field lacks, and on grids with face
+        connections or a fold along any of the three axes."""
+        arg = b
+        b, was_xr = self._wrap_in(b)
+        axes = (self.axes[z_axis], self.axes[y_axis], self.axes[x_axis])
+        got = tuple(ax._get_position_name(b) for ax in axes)
+        if (tuple(p for p, _ in got) != ("center", "center", "center") or "outer" not in axes[0].coords
+                or "left" not in axes[1].coords or "left" not in axes[2].coords):
+            raise NotImplementedError("fused hydrostatic pressure gradient needs b at (Z:center, Y:center, X:center), left "
+                                      "points on X and Y and an outer position on Z")
+        (_, tz), (_, ty), (_, tx) = got
+        zo, yl, xl = axes[0].coords["outer"], axes[1].coords["left"], axes[2].coords["left"]
+        lead = b.dims[:-3]
+        p_dims, dims_x, dims_y = lead + (zo, ty, tx), lead + (tz, ty, xl), lead + (tz, yl, tx)
+        plan = None
+        weight = mx = my = None
+        if b.dims == lead + (tz, ty, tx) and not gridops.complex_topology(self, z_axis) and b.shape[-2] * b.shape[-1] != 1:
+            try:
+                weight = self._resident(self.get_metric(b, (z_axis,), _layout=b.dims), b.data)
+                if metric_weighted:
+                    mx = self._resident(self.get_metric(_DimsOnly(dims_x), (x_axis,)), b.data)
+                    my = self._resident(self.get_metric(_DimsOnly(dims_y), (y_axis,)), b.data)
+            except (KeyError, ValueError):
+                weight = None  # (the chain raises it where the chain looks the metric up)
+            if weight is not None and all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data))
+                                          for m, dims in ((weight, b.dims), (mx, dims_x), (my, dims_y))):
+                plan = self._second_order_plan([b], x_axis, y_axis, padding, fill_value,
+                                               [m for m in (weight, mx, my) if m is not None])
+            if plan is not None:
+                bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
+                fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
+                # periodic: the pad is the column total; no boundary: the chain raises
+                plan = None if bc[z_axis] not in ("fill", "extend") else \
+                    plan + (bc[z_axis], 0.0 if fval[z_axis] is None else float(fval[z_axis]))  # (as cumsum: -0.0 stays)
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            p = self.cumint(arg, z_axis, to="outer", **kw)
+            pc = self.interp(p, z_axis, **kw)
+            return self.gradient(pc, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+        bcx, bcy, fvx, fvy, bcz, fvz = plan
+        host = not _is_tensor(b.data)
+        ox, oy = _dev.hydrostatic_pressure_gradient(b.data, _aligned_view(weight, b.dims),
+                                                    None if mx is None else _aligned_view(mx, dims_x),
+                                                    None if my is None else _aligned_view(my, dims_y),
+                                                    bcx, bcy, bcz, fvx, fvy, fvz)
+        # dims, coords and names as the chain's, step by step over placeholders: the cumulative integral (named after the
+        # product with the weight, padded by one level), its mean at the centre, the two differences
+        p_shape = tuple(b.shape[:-3]) + (b.shape[-3] + 1,) + tuple(b.shape[-2:])
+        p = _reattach_coords([DataArray(_placeholder(p_shape), p_dims, name=_name_after(b.name, weight))], self,
+                             {z_axis: (1, 0)}, {zo}, [b])[0]
+        pc = _reattach_coords([DataArray(_placeholder(b.shape), b.dims, name=p.name)], self, None, {tz}, [p])[0]
+        gx, gy = self._labels_of_step(pc, dims_x, xl), self._labels_of_step(pc, dims_y, yl)
+        gx = gx._replace(data=_dev.tohost(ox) if host else ox)
+        gy = gy._replace(data=_dev.tohost(oy) if host else oy)
+        return (to_xarray(gx), to_xarray(gy)) if was_xr else (gx, gy)
+
     # ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---------------------
     def _c_grid_vector(self, u, v, x_axis, y_axis, what):
         """dims of a C-grid vector's points: (lead, at u, at v, centre, vorticity point); raises when u / v sit elsewhere"""
