@@ -43,6 +43,7 @@
  *   xg_flux_divergence3d_f64  the same with the vertical flux w * interp(T, Z), divided by the cell volume
  *   xg_vertical_velocity_f64  w from continuity: -cumsum(divergence(u, v), Z) / area, one pass
  *   xg_hydrostatic_pressure_gradient_f64  gradient(interp(cumint(b, Z), Z)): the pressure-gradient force, one pass
+ *   xg_vertical_momentum_advection_f64  -interp(interp(w, X / Y) * diff(u / v, Z), Z): w du/dz and w dv/dz, one pass
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -408,6 +409,25 @@ int xg_hydrostatic_pressure_gradient_f64(const double* b, const double* w, const
                                          const int64_t* dxC_strides, const double* dyC, const int64_t* dyC_strides,
                                          double* out_x, double* out_y, const int64_t* shape, int ndim, int bc_x,
                                          double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
+/* The vertical advection of horizontal momentum (w du/dz, w dv/dz in index space), one pass over arrays of identical `shape`
+ * (.., Z, Y, X): u at (Z:c, Y:c, X:left), v at (Z:c, Y:left, X:c), w at (Z:left, Y:c, X:c); out_u at u's points, out_v at
+ * v's.  It replaces the chain
+ *   wu = (w[i-1] + w[i]) / 2,  wv = (w[j-1] + w[j]) / 2        xg_stencil1d_f64 interp, center -> left along X / Y
+ *   du = u[k] - u[k-1],        dv = v[k] - v[k-1]              xg_stencil1d_f64 diff, center -> left along Z
+ *   pu = wu * du,              pv = wv * dv                    xg_binary_f64
+ *   out_u = -((pu[k] + pu[k+1]) / 2) [/ mu],  out_v = -((pv[k] + pv[k+1]) / 2) [/ mv]     interp left -> center along Z,
+ *                                                              the negation, the division (mu / mv NULL: no division)
+ * Every stage pads where the chain pads: w left of the first column and below the first row, u and v above level 0, the
+ * products pu, pv beyond level nz - 1 -- periodic: the stage's own value at the wrapped index, extend: at the clamped index,
+ * fill: fill_x / fill_y / fill_z itself (a filled product is fill_z, not a product formed from it).  All three boundary
+ * codes are served on every axis (XG_BC_HALO is not accepted).
+ * Argument order: the three fields, then (pointer, strides) of the metric of out_u and of out_v, the two outputs, shape, ndim
+ * and the boundary codes with their fill values for X, Y and Z.  Every metric uses broadcast strides (0 = broadcast) against
+ * `shape`. */
+int xg_vertical_momentum_advection_f64(const double* u, const double* v, const double* w, const double* mu,
+                                       const int64_t* mu_strides, const double* mv, const int64_t* mv_strides,
+                                       double* out_u, double* out_v, const int64_t* shape, int ndim, int bc_x,
+                                       double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
 
 /* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
 /* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).
@@ -552,6 +572,10 @@ int xg_hydrostatic_pressure_gradient_f32(const float* b, const float* w, const i
                                          const int64_t* dxC_strides, const float* dyC, const int64_t* dyC_strides,
                                          float* out_x, float* out_y, const int64_t* shape, int ndim, int bc_x,
                                          float fill_x, int bc_y, float fill_y, int bc_z, float fill_z, void* stream);
+int xg_vertical_momentum_advection_f32(const float* u, const float* v, const float* w, const float* mu,
+                                       const int64_t* mu_strides, const float* mv, const int64_t* mv_strides,
+                                       float* out_u, float* out_v, const int64_t* shape, int ndim, int bc_x, float fill_x,
+                                       int bc_y, float fill_y, int bc_z, float fill_z, void* stream);
 int xg_kinetic_energy_f32(const float* u, const float* v, float* out, const int64_t* shape, int ndim, int bc_x,
                           float fill_x, int bc_y, float fill_y, void* stream);
 int xg_momentum_advection_f32(const float* u, const float* v, const float* coriolis, const int64_t* coriolis_strides,

@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient against their chains; 5pg: the last pair alone), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection against their chains; 5pg, 5vm: the last two pairs, each alone), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -116,6 +116,37 @@ def run_pressure_gradient(reps, nz=90, n=4320):
     rec(5, "hydrostatic_pressure_gradient fused gradient(interp(cumint(b, Z), Z)) / (dxC, dyC), periodic/extend/fill: 1 read + 2 writes", med(tf), cells, 24 + 16 / nz)
     rec(5, "hydrostatic_pressure_gradient as its chain (3 launches), fused-equivalent bytes", med(tc), cells, 24 + 16 / nz)
     print(json.dumps({"config": 5, "check": "fused hydrostatic_pressure_gradient == chain bit for bit at full size", "ok": ok,
+                      "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
+                      "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_vertical_momentum_advection(reps, nz=90, n=4320):
+    """vertical_momentum_advection in one pass against its chain of twelve launches (two interps of w, two diffs along Z, two
+    products, two interps along Z, two negations, two divisions by drF) on the MITgcm grid (periodic / extend / fill), timed
+    in turns, every paired round reported"""
+    grid = mitgcm_grid(nz, n, n)
+    U = DataArray(D.synthetic((nz, n, n), 57), ("Z", "YC", "XG"))
+    V = DataArray(D.synthetic((nz, n, n), 58), ("Z", "YG", "XC"))
+    W = DataArray(D.synthetic((nz, n, n), 59), ("Zl", "YC", "XC"))
+    cells = nz * n * n
+
+    def chain():
+        wu, wv = grid.interp(W, "X"), grid.interp(W, "Y")
+        du, dv = grid.diff(U, "Z"), grid.diff(V, "Z")
+        gu, gv = -grid.interp(wu * du, "Z"), -grid.interp(wv * dv, "Z")
+        return gu / grid.get_metric(gu, ("Z",)), gv / grid.get_metric(gv, ("Z",))
+
+    gu, gv = grid.vertical_momentum_advection(U, V, W)
+    wu, wv = chain()
+    ok = bool(torch.equal(gu.data, wu.data) and torch.equal(gv.data, wv.data))
+    del gu, gv, wu, wv
+    torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(lambda: grid.vertical_momentum_advection(U, V, W), chain, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    rec(5, "vertical_momentum_advection fused -interp(interp(w, X / Y) * diff(u / v, Z), Z) / drF, periodic/extend/fill: 3 reads + 2 writes", med(tf), cells, 40)
+    rec(5, "vertical_momentum_advection as its chain (12 launches), fused-equivalent bytes", med(tc), cells, 40)
+    print(json.dumps({"config": 5, "check": "fused vertical_momentum_advection == chain bit for bit at full size", "ok": ok,
                       "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
                       "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
@@ -754,6 +785,8 @@ def main():
         torch.cuda.empty_cache()
     if cfgs & {"5x", "5pg"}:
         run_pressure_gradient(a.reps)
+    if cfgs & {"5x", "5vm"}:
+        run_vertical_momentum_advection(a.reps)
     ranks.close()
 
 

@@ -607,6 +607,83 @@ int pgrad(const R* b, const R* const met[3], const int64_t* const ms[3], R* out_
   return XG_OK;
 }
 
+// the vertical advection of horizontal momentum of the header as five plain passes over one (Z, Y, X) volume at a time:
+// w at u's and v's columns, the Z differences of u and v, the products, their means at the centre, the sign and the metrics.
+// Each pass pads its own axis by one cell through `padded`.
+// met[] = {the metric of out_u, of out_v}
+template <typename R>
+int vmomadv(const R* u, const R* v, const R* w, const R* const met[2], const int64_t* const ms[2], R* out_u, R* out_v,
+            const int64_t* shape, int ndim, int bc_x, R fill_x, int bc_y, R fill_y, int bc_z, R fill_z) {
+  if (!u || !v || !w || !out_u || !out_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  for (int c : {bc_x, bc_y, bc_z})
+    if (c < XG_BC_PERIODIC || c > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", c);
+  for (int k = 0; k < 2; ++k)
+    if (met[k] && !ms[k]) return fail(XG_ERR_INVALID, "metric without strides");
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx, vol = nz * plane;
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 3; ++d) outer *= shape[d];
+  if (outer == 0 || vol == 0) return XG_OK;
+  // the padded index of a one-axis read: a cell of the axis, or -1 for "the fill value"
+  auto padded = [](int64_t i, int64_t n, int bc) -> int64_t {
+    if (i >= 0 && i < n) return i;
+    if (bc == XG_BC_FILL) return -1;
+    if (bc == XG_BC_PERIODIC) return i < 0 ? n - 1 : 0;
+    return i < 0 ? 0 : n - 1;
+  };
+  std::vector<R> wu((size_t)vol), wv((size_t)vol), du((size_t)vol), dv((size_t)vol);
+  R* const out[2] = {out_u, out_v};
+  for (int64_t o = 0; o < outer; ++o) {
+    int64_t rem = o, moff[2] = {0, 0};  // the lead index decomposed for the broadcast strides
+    for (int d = ndim - 4; d >= 0; --d) {
+      const int64_t i = rem % shape[d];
+      rem /= shape[d];
+      for (int k = 0; k < 2; ++k)
+        if (met[k]) moff[k] += i * ms[k][d];
+    }
+    const R *pu = u + o * vol, *pv = v + o * vol, *pw = w + o * vol;
+    // (1) w between a cell and the one left of it / below it: (w[i-1] + w[i]) / 2, (w[j-1] + w[j]) / 2
+    for (int64_t z = 0; z < nz; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t c = z * plane + j * nx + i, il = padded(i - 1, nx, bc_x), jb = padded(j - 1, ny, bc_y);
+          const R left = il < 0 ? fill_x : pw[z * plane + j * nx + il];
+          const R below = jb < 0 ? fill_y : pw[z * plane + jb * nx + i];
+          wu[c] = (left + pw[c]) / R(2);
+          wv[c] = (below + pw[c]) / R(2);
+        }
+    // (2) u and v minus the level above them
+    for (int64_t z = 0; z < nz; ++z) {
+      const int64_t za = padded(z - 1, nz, bc_z);
+      for (int64_t c = 0; c < plane; ++c) {
+        du[z * plane + c] = pu[z * plane + c] - (za < 0 ? fill_z : pu[za * plane + c]);
+        dv[z * plane + c] = pv[z * plane + c] - (za < 0 ? fill_z : pv[za * plane + c]);
+      }
+    }
+    // (3) the products, in place
+    for (int64_t c = 0; c < vol; ++c) {
+      wu[c] = wu[c] * du[c];
+      wv[c] = wv[c] * dv[c];
+    }
+    // (4) their means at the centre: level z and the level after it, (5) the sign and the metric
+    for (int which = 0; which < 2; ++which) {
+      const std::vector<R>& p = which ? wv : wu;
+      for (int64_t z = 0; z < nz; ++z) {
+        const int64_t zn = padded(z + 1, nz, bc_z);
+        for (int64_t j = 0; j < ny; ++j)
+          for (int64_t i = 0; i < nx; ++i) {
+            const int64_t c = j * nx + i;
+            R g = -((p[z * plane + c] + (zn < 0 ? fill_z : p[zn * plane + c])) / R(2));
+            if (met[which])
+              g = g / met[which][moff[which] + z * ms[which][ndim - 3] + j * ms[which][ndim - 2] + i * ms[which][ndim - 1]];
+            out[which][o * vol + z * plane + c] = g;
+          }
+      }
+    }
+  }
+  return XG_OK;
+}
+
 // kinetic energy (ke_only) and the vector-invariant momentum advection of the header: the stages of the chain one after
 // the other over whole planes, each read through `get`, which pads a plane by one cell on one axis at a time (periodic:
 // the plane's own value at the wrapped index, extend: at the clamped index, fill: the fill value of that axis).
@@ -911,6 +988,14 @@ int xg_event_destroy(void* ev) { free(ev); return XG_OK; }
     const R* const met[3] = {w, dxC, dyC};                                                                            \
     const int64_t* const ms[3] = {ws, dxCs, dyCs};                                                                    \
     return pgrad<R>(b, met, ms, out_x, out_y, shape, ndim, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z);                \
+  }                                                                                                                   \
+  int xg_vertical_momentum_advection_##SFX(const R* u, const R* v, const R* w, const R* mu, const int64_t* mus,       \
+                                           const R* mv, const int64_t* mvs, R* out_u, R* out_v, const int64_t* shape, \
+                                           int ndim, int bc_x, R fill_x, int bc_y, R fill_y, int bc_z, R fill_z,      \
+                                           void*) {                                                                    \
+    const R* const met[2] = {mu, mv};                                                                                 \
+    const int64_t* const ms[2] = {mus, mvs};                                                                          \
+    return vmomadv<R>(u, v, w, met, ms, out_u, out_v, shape, ndim, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z);        \
   }                                                                                                                   \
   int xg_kinetic_energy_##SFX(const R* u, const R* v, R* out, const int64_t* shape, int ndim, int bc_x, R fill_x,     \
                               int bc_y, R fill_y, void*) {                                                            \

@@ -1434,6 +1434,158 @@ __global__ __launch_bounds__(BLOCK) void k_pgrad(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7j: the vertical advection of horizontal momentum in ONE pass over (lead, Z, Y, X), three fields in, two out:
+//   pu[k] = interp_x(w[k]) * (u[k] - u[k-1]),   pv[k] = interp_y(w[k]) * (v[k] - v[k-1])      at (Z:left), over u's / v's column
+//   gu[k] = -((pu[k] + pu[k+1]) / 2) [/ mu],    gv[k] = -((pv[k] + pv[k+1]) / 2) [/ mv]
+// i.e. interp (X / Y, center -> left) and diff (Z, center -> left), their product, interp (Z, left -> center), the negation,
+// the division.  Every stage pads where the chain pads: w left of the first column and below the first row, u and v above
+// level 0 (periodic: level nz-1, extend: level 0, fill: fill_z), the PRODUCTS beyond level nz-1 (periodic: pu[0], extend:
+// pu[nz-1], fill: fill_z itself).  K7e's decomposition: a wave owns one (lead, Y segment, X tile) column and marches
+// k = 0 .. nz-1 with u[k], v[k], pu[k] and pv[k] in registers; the rows of level k+1 are read at level k and form pu[k+1].
+// u, v and w are read once and gu, gv written once: 40 B/cell in float64.  w of the row below the segment is one more row per level (an L2 hit:
+// the segment before's last row); w left of the lane's vector comes from the lane before it by DPP, the tile's first lane
+// and the row's edge load or pad their own.  No running sum: all three Z boundaries are served.  The metrics (the Z metric
+// at u's / v's points) are one broadcast array per output; rows that do not vary along Z are loaded once per wave.
+// ------------------------------------------------------------------------------------------
+template <typename T, int SEG>
+struct VmLevel {  // what one level of a column brings: SEG rows of u, v and w, the w row below them, w left of the lane
+  T uu[SEG], vv[SEG], ww[SEG], wb;
+  real wl[SEG];
+};
+
+template <int V, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_vmomadv(
+    const real* __restrict__ u, const real* __restrict__ v, const real* __restrict__ w, real* __restrict__ out_u,
+    real* __restrict__ out_v, int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile,
+    FastDiv nseg, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mu, VolIdx mv, int ntl) {
+  typedef typename VecT<V>::type T;
+  typedef VmLevel<T, SEG> L;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  // X as K7e's T: w left of the lane's vector (periodic: column nx - 1, extend: column 0 itself); Y: the row below the
+  // segment (periodic: row ny - 1 below row 0, extend: row 0 itself); a fill edge loads the clamped cell and replaces it
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);
+  const bool fill_l = e.edge_l && bc_x == XG_BC_FILL;
+  const bool fill_b = j0 == 0 && bc_y == XG_BC_FILL;
+  const int64_t rb = (j0 > 0 ? j0 - 1 : ((bc_y == XG_BC_PERIODIC) ? ny - 1 : 0)) * nx;
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+
+  auto fetch = [&](int64_t k) -> L {
+    L x;
+    const int64_t lv = col + k * plane;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.uu[s_] = *reinterpret_cast<const T*>(u + lv + ro[s_] + i0);
+      x.vv[s_] = *reinterpret_cast<const T*>(v + lv + ro[s_] + i0);
+      x.ww[s_] = *reinterpret_cast<const T*>(w + lv + ro[s_] + i0);
+      x.wl[s_] = e.own_l ? w[lv + ro[s_] + e.lidx] : real(0);
+    }
+    x.wb = *reinterpret_cast<const T*>(w + lv + rb + i0);
+    return x;
+  };
+  // the two products of a level from its rows and the level above's u and v
+  auto products = [&](const L& x, const T (&up)[SEG], const T (&vp)[SEG], T (&pu)[SEG], T (&pv)[SEG]) {
+    real wl[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) wl[s_] = x.wl[s_];
+    if (e.shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real left = from_lane_below(vec_last(x.ww[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+        if (!e.own_l) wl[s_] = left;
+      }
+    }
+    const T wb = fill_b ? splat<T>(fill_y) : x.wb;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      const real left = fill_l ? fill_x : wl[s_];
+      pu[s_] = interp_left_of(x.ww[s_], left) * op2<XG_OP_DIFF>(up[s_], x.uu[s_]);
+      pv[s_] = op2<XG_OP_INTERP>(s_ == 0 ? wb : x.ww[(s_ > 0) ? s_ - 1 : 0], x.ww[s_]) * op2<XG_OP_DIFF>(vp[s_], x.vv[s_]);
+    }
+  };
+
+  // the metric rows: in registers, loaded again per level only when the array varies along Z
+  T mur[SEG], mvr[SEG];
+  int64_t muo = 0, mvo = 0;
+  if (MET) {
+    if (mu.p) {
+      muo = area_outer_off(mu.ai, o) + j0 * mu.sy + i0 * mu.sx;
+      load_rows<T, SEG>(mur, mu.p, muo, mu.sy, mu.sx, nrow, (ntl & 4) != 0);
+    }
+    if (mv.p) {
+      mvo = area_outer_off(mv.ai, o) + j0 * mv.sy + i0 * mv.sx;
+      load_rows<T, SEG>(mvr, mv.p, mvo, mv.sy, mv.sx, nrow, (ntl & 8) != 0);
+    }
+  }
+
+  // level 0: pu[0], pv[0] from u and v padded above it; periodic Z keeps them for the pad beyond the last level
+  T uc[SEG], vc[SEG], puc[SEG], pvc[SEG], pu0[SEG], pv0[SEG];
+  {
+    const L x = fetch(0);
+    const int64_t ka = col + ((bc_z == XG_BC_PERIODIC) ? nz - 1 : 0) * plane;
+    T ua[SEG], va[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      ua[s_] = (bc_z == XG_BC_FILL) ? splat<T>(fill_z) : *reinterpret_cast<const T*>(u + ka + ro[s_] + i0);
+      va[s_] = (bc_z == XG_BC_FILL) ? splat<T>(fill_z) : *reinterpret_cast<const T*>(v + ka + ro[s_] + i0);
+    }
+    products(x, ua, va, puc, pvc);
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      uc[s_] = x.uu[s_];
+      vc[s_] = x.vv[s_];
+      pu0[s_] = puc[s_];
+      pv0[s_] = pvc[s_];
+    }
+  }
+  real* pgu = out_u + col + j0 * nx + i0;
+  real* pgv = out_v + col + j0 * nx + i0;
+  for (int64_t k = 0; k < nz; ++k) {
+    T pun[SEG], pvn[SEG];
+    if (k + 1 < nz) {
+      const L x = fetch(k + 1);
+      products(x, uc, vc, pun, pvn);
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        uc[s_] = x.uu[s_];
+        vc[s_] = x.vv[s_];
+      }
+    } else {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        pun[s_] = (bc_z == XG_BC_PERIODIC) ? pu0[s_] : ((bc_z == XG_BC_EXTEND) ? puc[s_] : splat<T>(fill_z));
+        pvn[s_] = (bc_z == XG_BC_PERIODIC) ? pv0[s_] : ((bc_z == XG_BC_EXTEND) ? pvc[s_] : splat<T>(fill_z));
+      }
+    }
+    if (MET && k > 0) {
+      if (mu.p && mu.sz != 0) load_rows<T, SEG>(mur, mu.p, muo + k * mu.sz, mu.sy, mu.sx, nrow, (ntl & 4) != 0);
+      if (mv.p && mv.sz != 0) load_rows<T, SEG>(mvr, mv.p, mvo + k * mv.sz, mv.sy, mv.sx, nrow, (ntl & 8) != 0);
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        T gu = -op2<XG_OP_INTERP>(puc[s_], pun[s_]);
+        T gv = -op2<XG_OP_INTERP>(pvc[s_], pvn[s_]);
+        if (MET) {
+          if (mu.p) gu = gu / mur[s_];
+          if (mv.p) gv = gv / mvr[s_];
+        }
+        stg_s<T, NTS>(pgu + k * plane + s_ * nx, gu);
+        stg_s<T, NTS>(pgv + k * plane + s_ * nx, gv);
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      puc[s_] = pun[s_];
+      pvc[s_] = pvn[s_];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -2042,6 +2194,41 @@ int XG_FN(xg_hydrostatic_pressure_gradient)(const real* b, const real* w, const 
   const bool met = dxC != nullptr || dyC != nullptr;
   return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
 #define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_pgrad<V_, M_, NTS, FSEG, U>), dim3(grid), dim3(BLOCK), 0, p.st, b, out_x, out_y, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt); } while (0)
+#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+// K7j's launcher: (lead, Z, Y, X) fields, two optional broadcast metrics (the Z metric at u's and at v's points), one wave
+// per column
+int XG_FN(xg_vertical_momentum_advection)(const real* u, const real* v, const real* w, const real* mu,
+                                          const int64_t* mu_strides, const real* mv, const int64_t* mv_strides,
+                                          real* out_u, real* out_v, const int64_t* shape, int ndim, int bc_x, real fill_x,
+                                          int bc_y, real fill_y, int bc_z, real fill_z, void* stream) {
+  const char* name = "vertical momentum advection";
+  if (!u || !v || !w || !out_u || !out_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  FusedPlan p;
+  const bool al = aligned16(u) && aligned16(v) && aligned16(w) && aligned16(out_u) && aligned16(out_v);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  VolIdx mi[2];  // the metric of gu, of gv
+  const real* mp[2] = {mu, mv};
+  const int64_t* ms[2] = {mu_strides, mv_strides};
+  for (int k = 0; k < 2; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  // bit 0: the lane neighbour by DPP (K7e), bits 2 / 3: the rows of the metric of gu / gv are aligned vectors
+  int vnt = vec_nt_bits(1);
+  for (int k = 0; k < 2; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool met = mu != nullptr || mv != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_vmomadv<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, u, v, w, out_u, out_v, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], vnt); } while (0)
 #define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
 #define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
     if (p.V > 1) XG_V(NV);

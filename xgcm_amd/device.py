@@ -1293,6 +1293,35 @@ def hydrostatic_pressure_gradient(b, w, dxC, dyC, bc_x: str, bc_y: str, bc_z: st
     return out_x, out_y
 
 
+def vertical_momentum_advection(u, v, w, mu, mv, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0, fill_y: float = 0.0,
+                                fill_z: float = 0.0):
+    """Fused vertical advection of horizontal momentum in one pass (xg_vertical_momentum_advection_f64): w between a cell
+    and the one left of / below it, times the difference of u / v to the level above, the mean of that product with the
+    next level's, negated and divided by `mu` / `mv` (None = no division).  Each stage pads as the chain does: w left of /
+    below the first cell, u and v above level 0, the products beyond the last level.  Returns (gu, gv)."""
+    lib = _MEM.lib()
+    dt, sfx = _common(u, v, w, mu, mv)
+    u, v, w = asdevice(u, dt), asdevice(v, dt), asdevice(w, dt)
+    if v.shape != u.shape or w.shape != u.shape:
+        raise ValueError("vertical_momentum_advection: u, v and w must have the same shape")
+    shape = list(u.shape)
+    mets = [_prep_metric(m, dt) for m in (mu, mv)]
+    out_u = _empty(shape, dtype=dt, device=u.device)
+    out_v = _empty(shape, dtype=dt, device=u.device)
+    if out_u.numel() == 0:
+        return out_u, out_v
+    margs = []
+    for m, what in zip(mets, ("metric of gu", "metric of gv")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
+    _check(
+        getattr(lib, "xg_vertical_momentum_advection_" + sfx)(u.data_ptr(), v.data_ptr(), w.data_ptr(), *margs,
+                                                              out_u.data_ptr(), out_v.data_ptr(), _hip.i64(shape),
+                                                              len(shape), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y],
+                                                              float(fill_y), _hip.BC[bc_z], float(fill_z), _stream())
+    )
+    return out_u, out_v
+
+
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""
