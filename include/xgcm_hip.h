@@ -44,6 +44,7 @@
  *   xg_vertical_velocity_f64  w from continuity: -cumsum(divergence(u, v), Z) / area, one pass
  *   xg_hydrostatic_pressure_gradient_f64  gradient(interp(cumint(b, Z), Z)): the pressure-gradient force, one pass
  *   xg_vertical_momentum_advection_f64  -interp(interp(w, X / Y) * diff(u / v, Z), Z): w du/dz and w dv/dz, one pass
+ *   xg_horizontal_viscosity_f64  gradient(divergence * nu_d) -/+ diff(vorticity * nu_z): the harmonic viscosity, one pass
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -457,6 +458,33 @@ int xg_momentum_advection_f64(const double* u, const double* v, const double* co
                               double* out_v, const int64_t* shape, int ndim, int bc_x, double fill_x, int bc_y,
                               double fill_y, void* stream);
 
+/* ---- the dissipation term: the vector-invariant harmonic viscosity, one pass ---- */
+/* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).
+ * xg_horizontal_viscosity replaces the chain of seven launches (nine with the coefficients)
+ *   D    = xg_divergence_f64(u, v, rA)  [* nu_d]                              centre
+ *   zeta = xg_vorticity_f64(u, v, rAz)  [* nu_z]                              (Y:left, X:left)
+ *   dx, dy = xg_gradient_f64(D, dxC, dyC)                                     at u's / v's points
+ *   zy = (zeta[j+1,i] - zeta[j,i]) [/ dyG],  zx = (zeta[j,i+1] - zeta[j,i]) [/ dxG]     xg_stencil1d_f64 diff, left -> center
+ *   out_u = dx - zy,  out_v = dy + zx
+ * bit for bit, every stage with the bc of its axis on the side the chain pads it: u right of the last column and v above
+ * the last row (D), v left of the first column and u below the first row (zeta), the PRODUCT D [* nu_d] left of the first
+ * column and below the first row, the PRODUCT zeta [* nu_z] above the last row and right of the last column.  Periodic:
+ * the STAGE's value at the wrapped index, extend: at the clamped index, fill: the fill value itself (never a quotient or
+ * a product formed from it).  fill_x / fill_y pad u, v and the product D * nu_d; zfill_x / zfill_y pad the product
+ * zeta * nu_z (the chain's one-axis differences keep the sign of a -0.0 fill that its two-axis operators drop, so a
+ * caller that mirrors the chain passes +0.0 and -0.0 here).  The six metrics rA, rAz, dxC, dyC, dyG (the Y metric at u's
+ * points), dxG (the X metric at v's points) come together or are all NULL (the plain differences); nu_d (at the centre)
+ * and nu_z (at the vorticity point) come together or are both NULL.  The eight planes use broadcast strides
+ * (0 = broadcast) against `shape`.  XG_BC_HALO is not accepted. */
+int xg_horizontal_viscosity_f64(const double* u, const double* v, const double* rA, const int64_t* rA_strides,
+                                const double* rAz, const int64_t* rAz_strides, const double* dxC,
+                                const int64_t* dxC_strides, const double* dyC, const int64_t* dyC_strides,
+                                const double* dyG, const int64_t* dyG_strides, const double* dxG,
+                                const int64_t* dxG_strides, const double* nu_d, const int64_t* nu_d_strides,
+                                const double* nu_z, const int64_t* nu_z_strides, double* out_u, double* out_v,
+                                const int64_t* shape, int ndim, int bc_x, double fill_x, double zfill_x, int bc_y,
+                                double fill_y, double zfill_y, void* stream);
+
 /* ---- the same two-point operator along the last TWO axes in one pass -------------------- */
 /* out = OP_second(pad(OP_first(pad(in)))) for (.., Y, X) arrays, order 0: X then Y, 1: Y then X;
  * replaces two sequential apply_as_grid_ufunc passes of Grid.interp/diff/min/max(da, [ax1, ax2])
@@ -583,6 +611,14 @@ int xg_momentum_advection_f32(const float* u, const float* v, const float* corio
                               const int64_t* dxC_strides, const float* dyC, const int64_t* dyC_strides, float* out_u,
                               float* out_v, const int64_t* shape, int ndim, int bc_x, float fill_x, int bc_y,
                               float fill_y, void* stream);
+int xg_horizontal_viscosity_f32(const float* u, const float* v, const float* rA, const int64_t* rA_strides,
+                                const float* rAz, const int64_t* rAz_strides, const float* dxC,
+                                const int64_t* dxC_strides, const float* dyC, const int64_t* dyC_strides,
+                                const float* dyG, const int64_t* dyG_strides, const float* dxG,
+                                const int64_t* dxG_strides, const float* nu_d, const int64_t* nu_d_strides,
+                                const float* nu_z, const int64_t* nu_z_strides, float* out_u, float* out_v,
+                                const int64_t* shape, int ndim, int bc_x, float fill_x, float zfill_x, int bc_y,
+                                float fill_y, float zfill_y, void* stream);
 int xg_stencil2d_f32(int op, const float* in, float* out, const int64_t* shape, int ndim, int order,
                      int padx_lo, int padx_hi, int bc_x, float fill_x, int pady_lo, int pady_hi,
                      int bc_y, float fill_y, void* stream);

@@ -104,6 +104,7 @@ def main():
         "vmadv": (lambda: D.vertical_momentum_advection(U, V, W, dz, dz, "periodic", "extend", "fill"), 40),  # w du/dz, w dv/dz: drF
         "keUV": (lambda: D.kinetic_energy(U, V, "periodic", "extend"), 24),  # 0.5 * (interp(u*u, X) + interp(v*v, Y))
         "madv": (lambda: D.momentum_advection(U, V, dx2, dx, dx2, dx, "periodic", "extend"), 32 + 16 / nz),  # vector-invariant advection + Coriolis: its four planes from two
+        "hvisc": (lambda: D.horizontal_viscosity(U, V, dx, dx2, dx, dx2, dx2, dx, dx2, dx, "periodic", "extend"), 32 + 16 / nz),  # harmonic viscosity: its six metrics and two coefficients from two planes
     }
     cases = a.cases.split(",")
     dx2_off = None
@@ -153,7 +154,7 @@ def main():
             R = int(c[5:])
             TR = D.synthetic((R, nz, ny, nx), 4)
             CASES[c] = ((lambda TR=TR: D.cumsum1d(TR, 1, 0, 1, 1, 0, "fill")), 16 * R)
-    if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "keUV", "madv")):
+    if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "keUV", "madv", "hvisc")):
         U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
     W = D.synthetic((nz, ny, nx), 54) if ("adv3" in cases or "vmadv" in cases) else None
     variants = []
@@ -183,7 +184,7 @@ def main():
                 T2 = D.synthetic((nz, ny, nx), 9, 0, 1000.0, 1000.0)
             if T3k:
                 T3 = D.synthetic((nz, ny, nx), 10, 0, 1000.0, 1000.0)
-            if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "keUV", "madv")):
+            if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "keUV", "madv", "hvisc")):
                 U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
             if "adv3" in cases or "vmadv" in cases:
                 W = D.synthetic((nz, ny, nx), 54)

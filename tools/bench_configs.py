@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection against their chains; 5pg, 5vm: the last two pairs, each alone), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity against their chains; 5pg, 5vm, 5hv: the last three pairs, each alone), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -147,6 +147,46 @@ def run_vertical_momentum_advection(reps, nz=90, n=4320):
     rec(5, "vertical_momentum_advection fused -interp(interp(w, X / Y) * diff(u / v, Z), Z) / drF, periodic/extend/fill: 3 reads + 2 writes", med(tf), cells, 40)
     rec(5, "vertical_momentum_advection as its chain (12 launches), fused-equivalent bytes", med(tc), cells, 40)
     print(json.dumps({"config": 5, "check": "fused vertical_momentum_advection == chain bit for bit at full size", "ok": ok,
+                      "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
+                      "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_horizontal_viscosity(reps, nz=90, n=4320):
+    """horizontal_viscosity in one pass against its chain of nine launches (divergence, vorticity, two products with the
+    coefficient planes, gradient, two derivatives of zeta, two combinations) with the six 2-D metric planes and both 2-D
+    coefficient planes (periodic / extend), timed in turns, every paired round reported"""
+    coords = {"XC": ("XC", np.arange(n) + 0.5), "XG": ("XG", np.arange(n) * 1.0), "YC": ("YC", np.arange(n) + 0.5),
+              "YG": ("YG", np.arange(n) * 1.0), "Z": ("Z", np.arange(nz) + 0.5)}
+    m = lambda seed, dims: DataArray(D.synthetic((n, n), seed, 0, 1000.0, 1000.0), dims)  # noqa: E731
+    ds = Dataset({"dxC": m(31, ("YC", "XG")), "dyC": m(32, ("YG", "XC")), "dyG": m(35, ("YC", "XG")), "dxG": m(36, ("YG", "XC")),
+                  "rA": m(37, ("YC", "XC")), "rAz": m(33, ("YG", "XG"))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"}},
+                padding={"X": "periodic", "Y": "extend"}, autoparse_metadata=False,
+                metrics={("X",): ["dxC", "dxG"], ("Y",): ["dyC", "dyG"], ("X", "Y"): ["rA", "rAz"]})
+    U = DataArray(D.synthetic((nz, n, n), 51), ("Z", "YC", "XG"))
+    V = DataArray(D.synthetic((nz, n, n), 52), ("Z", "YG", "XC"))
+    ND = DataArray(D.synthetic((n, n), 38, 0, 50.0, 100.0), ("YC", "XC"))
+    NZ = DataArray(D.synthetic((n, n), 39, 0, 50.0, 100.0), ("YG", "XG"))
+    cells = nz * n * n
+
+    def chain():
+        div = grid.divergence(U, V) * ND
+        zeta = grid.vorticity(U, V) * NZ
+        dx, dy = grid.gradient(div, metric_weighted=True)
+        return dx - grid.derivative(zeta, "Y"), dy + grid.derivative(zeta, "X")
+
+    gu, gv = grid.horizontal_viscosity(U, V, ND, NZ)
+    wu, wv = chain()
+    ok = bool(torch.equal(gu.data, wu.data) and torch.equal(gv.data, wv.data))
+    del gu, gv, wu, wv
+    torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(lambda: grid.horizontal_viscosity(U, V, ND, NZ), chain, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    bpc = 32 + 64 / nz
+    rec(5, "horizontal_viscosity fused (rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z), periodic/extend: 2 reads + 2 writes", med(tf), cells, bpc)
+    rec(5, "horizontal_viscosity as its chain (9 launches), fused-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": "fused horizontal_viscosity == chain bit for bit at full size", "ok": ok,
                       "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
                       "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
@@ -787,6 +827,8 @@ def main():
         run_pressure_gradient(a.reps)
     if cfgs & {"5x", "5vm"}:
         run_vertical_momentum_advection(a.reps)
+    if cfgs & {"5x", "5hv"}:
+        run_horizontal_viscosity(a.reps)
     ranks.close()
 
 

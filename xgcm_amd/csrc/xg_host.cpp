@@ -10,7 +10,7 @@
 // semantics, not against the kernels or the oracle.  It serves the 1-D operators of SURVEY.md section 8(a):
 // stencil (+ pre-gathered halos), cumsum, reduce, pad, the broadcasting binary op and the synthetic generator, plus the
 // fused divergence / vorticity / flux divergence (2-D and 3-D) / vertical velocity / laplacian / kinetic energy / momentum
-// advection; the other fused / topology / transform entry points exist
+// advection / horizontal viscosity; the other fused / topology / transform entry points exist
 // and return XG_ERR_UNSUPPORTED.
 //
 // Build: g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off  (no FMA contraction: same bit contract as the kernels)
@@ -763,6 +763,95 @@ int momentum(bool ke_only, const R* u, const R* v, const R* const met[4], const 
   return XG_OK;
 }
 
+// the harmonic viscosity of the header as five plain passes over one (Y, X) plane at a time, each into its own temporary:
+// D and zeta from the padded fields, their products with the coefficients, the four differences of the padded products,
+// the combination.  Each read beyond the plane goes through `pad1`, which pads ONE axis by one cell.
+// pl[] = {rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z}: the six metrics all or none, the two coefficients both or none
+template <typename R>
+int hvisc(const R* u, const R* v, const R* const pl[8], const int64_t* const ps[8], R* out_u, R* out_v, const int64_t* shape,
+          int ndim, int bc_x, R fill_x, R zfill_x, int bc_y, R fill_y, R zfill_y) {
+  if (!u || !v || !out_u || !out_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 2 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [2,%d]", ndim, XG_MAX_NDIM);
+  for (int b : {bc_x, bc_y})
+    if (b < XG_BC_PERIODIC || b > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", b);
+  int nmet = 0, nvis = 0;
+  for (int k = 0; k < 8; ++k) {
+    if (pl[k] && !ps[k]) return fail(XG_ERR_INVALID, "metric without strides");
+    (k < 6 ? nmet : nvis) += pl[k] != nullptr;
+  }
+  if (nmet != 0 && nmet != 6) return fail(XG_ERR_INVALID, "horizontal viscosity: the six metrics rA, rAz, dxC, dyC, dyG, dxG, or none");
+  if (nvis != 0 && nvis != 2) return fail(XG_ERR_INVALID, "horizontal viscosity: both coefficients nu_d, nu_z, or none");
+  const int64_t ny = shape[ndim - 2], nx = shape[ndim - 1];
+  int64_t outer = 1;
+  for (int d = 0; d < ndim - 2; ++d) outer *= shape[d];
+  if (outer == 0 || ny == 0 || nx == 0) return XG_OK;
+  const size_t n = (size_t)(ny * nx);
+  std::vector<R> div(n), zeta(n), dx(n), dy(n), zy(n), zx(n);
+  // cell k of an axis of n cells padded by one on each side: the cell itself, the wrapped / clamped one, or -1 = the fill
+  auto pad1 = [](int64_t k, int64_t n, int bc) -> int64_t {
+    if (k >= 0 && k < n) return k;
+    if (bc == XG_BC_FILL) return -1;
+    if (bc == XG_BC_PERIODIC) return k < 0 ? n - 1 : 0;
+    return k < 0 ? 0 : n - 1;
+  };
+  for (int64_t o = 0; o < outer; ++o) {
+    int64_t rem = o, moff[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the outer index decomposed for the broadcast strides
+    for (int d = ndim - 3; d >= 0; --d) {
+      const int64_t i = rem % shape[d];
+      rem /= shape[d];
+      for (int k = 0; k < 8; ++k)
+        if (pl[k]) moff[k] += i * ps[k][d];
+    }
+    auto m = [&](int k, int64_t j, int64_t i) { return pl[k][moff[k] + j * ps[k][ndim - 2] + i * ps[k][ndim - 1]]; };
+    const R* pu = u + o * ny * nx;
+    const R* pv = v + o * ny * nx;
+    auto along_x = [&](const R* a, int64_t j, int64_t i, R fill) { const int64_t q = pad1(i, nx, bc_x); return q < 0 ? fill : a[j * nx + q]; };
+    auto along_y = [&](const R* a, int64_t j, int64_t i, R fill) { const int64_t q = pad1(j, ny, bc_y); return q < 0 ? fill : a[q * nx + i]; };
+    // (1) the divergence at the centre, the vorticity at the corner
+    for (int64_t j = 0; j < ny; ++j)
+      for (int64_t i = 0; i < nx; ++i) {
+        const int64_t c = j * nx + i;
+        R d = (along_x(pu, j, i + 1, fill_x) - pu[c]) + (along_y(pv, j + 1, i, fill_y) - pv[c]);
+        R z = (pv[c] - along_x(pv, j, i - 1, fill_x)) - (pu[c] - along_y(pu, j - 1, i, fill_y));
+        if (nmet) {
+          d = d / m(0, j, i);
+          z = z / m(1, j, i);
+        }
+        div[c] = d;
+        zeta[c] = z;
+      }
+    // (2) times the coefficients, in place
+    if (nvis)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          div[j * nx + i] = div[j * nx + i] * m(6, j, i);
+          zeta[j * nx + i] = zeta[j * nx + i] * m(7, j, i);
+        }
+    // (3) the gradient of the first product (towards the cell left of / below it), (4) the differences of the second one
+    // (towards the corner above / right of it)
+    for (int64_t j = 0; j < ny; ++j)
+      for (int64_t i = 0; i < nx; ++i) {
+        const int64_t c = j * nx + i;
+        dx[c] = div[c] - along_x(div.data(), j, i - 1, fill_x);
+        dy[c] = div[c] - along_y(div.data(), j - 1, i, fill_y);
+        zy[c] = along_y(zeta.data(), j + 1, i, zfill_y) - zeta[c];
+        zx[c] = along_x(zeta.data(), j, i + 1, zfill_x) - zeta[c];
+        if (nmet) {
+          dx[c] = dx[c] / m(2, j, i);
+          dy[c] = dy[c] / m(3, j, i);
+          zy[c] = zy[c] / m(4, j, i);
+          zx[c] = zx[c] / m(5, j, i);
+        }
+      }
+    // (5) the two tendencies
+    for (size_t c = 0; c < n; ++c) {
+      out_u[(size_t)(o * ny * nx) + c] = dx[c] - zy[c];
+      out_v[(size_t)(o * ny * nx) + c] = dy[c] + zx[c];
+    }
+  }
+  return XG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1010,6 +1099,16 @@ int xg_event_destroy(void* ev) { free(ev); return XG_OK; }
     const R* const met[4] = {rAz, cor, dxC, dyC};                                                                     \
     const int64_t* const ms[4] = {rAzs, cors, dxCs, dyCs};                                                            \
     return momentum<R>(false, u, v, met, ms, out_u, out_v, shape, ndim, bc_x, fill_x, bc_y, fill_y);                  \
+  }                                                                                                                   \
+  int xg_horizontal_viscosity_##SFX(const R* u, const R* v, const R* rA, const int64_t* rAs, const R* rAz,             \
+                                    const int64_t* rAzs, const R* dxC, const int64_t* dxCs, const R* dyC,              \
+                                    const int64_t* dyCs, const R* dyG, const int64_t* dyGs, const R* dxG,              \
+                                    const int64_t* dxGs, const R* nud, const int64_t* nuds, const R* nuz,              \
+                                    const int64_t* nuzs, R* out_u, R* out_v, const int64_t* shape, int ndim, int bc_x, \
+                                    R fill_x, R zfill_x, int bc_y, R fill_y, R zfill_y, void*) {                       \
+    const R* const pl[8] = {rA, rAz, dxC, dyC, dyG, dxG, nud, nuz};                                                   \
+    const int64_t* const ps[8] = {rAs, rAzs, dxCs, dyCs, dyGs, dxGs, nuds, nuzs};                                     \
+    return hvisc<R>(u, v, pl, ps, out_u, out_v, shape, ndim, bc_x, fill_x, zfill_x, bc_y, fill_y, zfill_y);           \
   }                                                                                                                   \
   int xg_laplacian_##SFX(const R* a, const R* dxC, const int64_t* dxCs, const R* dyC, const int64_t* dyCs, const R* dyG, \
                          const int64_t* dyGs, const R* dxG, const int64_t* dxGs, const R* area, const int64_t* as,     \

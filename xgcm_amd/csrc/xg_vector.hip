@@ -1237,6 +1237,206 @@ __global__ __launch_bounds__(BLOCK) void k_momadv(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7k: the vector-invariant harmonic viscosity (MITgcm's mom_vi_hdissip, harmonic part) in ONE pass, two fields in, two out:
+//   D    = ((u[j,i+1] - u[j,i]) + (v[j+1,i] - v[j,i])) [/ rA]  [* nu_d]              centre                K7b
+//   zeta = ((v[j,i] - v[j,i-1]) - (u[j,i] - u[j-1,i])) [/ rAz] [* nu_z]              (Y:left, X:left)      K7
+//   gu   = (D[j,i] - D[j,i-1]) [/ dxC] - (zeta[j+1,i] - zeta[j,i]) [/ dyG]           at u's points
+//   gv   = (D[j,i] - D[j-1,i]) [/ dyC] + (zeta[j,i+1] - zeta[j,i]) [/ dxG]           at v's points
+// in the chain's operation order (-ffp-contract=off, the compiler's IEEE quotients).  K7h's patch: per wave-task (SEG rows,
+// one x-tile) a lane holds u and v at rows j0-1 .. j0+SEG, columns i0-1 .. i0+V -- the columns left and right of its vector
+// from the neighbouring lanes (DPP), lane 0 / lane 63 / the edge lanes load their own.  A periodic axis wraps the patch's
+// indices: every stage's periodic pad is then the stage's own value at the wrapped index.  At an extend / fill boundary the
+// raw patch carries the pads of the FIRST stages, here on both sides (u below row 0 and right of the last column, v left of
+// column 0 and above the last row: the clamped index or the fill value), and the two products override their own pads: D
+// below and left, zeta above and right -- extend: the product at the clamped index, fill: the fill value itself.  The pads
+// of zeta's products take their own fill pair (`zfill_x`, `zfill_y`): the chain's one-axis differences keep the sign of a
+// -0.0 fill, its two-axis operators do not.  Every intermediate is formed once per lane; the two outputs of a cell share
+// them.  32 B/cell in float64 (the six metric planes and 2-D coefficients stay in the L2) instead of ~150-200 for the chain.
+// ------------------------------------------------------------------------------------------
+struct HviscPlanes {        // the six metrics (all or none) and the two coefficients (both or none), broadcast strides
+  const real* p[8];         // rA (centre), rAz (Y:l, X:l), dxC (Y:c, X:l), dyC (Y:l, X:c), dyG (Y:c, X:l), dxG (Y:l, X:c),
+  AreaIdx ai[8];            // nu_d (centre), nu_z (Y:l, X:l)
+  int64_t sy[8], sx[8];
+};
+
+template <int V, bool MET, bool VIS, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_hvisc(
+    const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ out_u, real* __restrict__ out_v, int64_t o0,
+    u32 nouter, u32 nblk, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, ZBand zb, int bc_x, real fill_x, real zfill_x,
+    int bc_y, real fill_y, real zfill_y, HviscPlanes mt, int ntl) {
+  typedef typename VecT<V>::type T;
+  XG_WAVE_TASK(V, SEG, zb.on, zb, 1);  // (band-major: the plane rows of a band stay in the XCD's L2 for all outer indices)
+  const int64_t base = o * ny * nx;
+  const bool per_x = bc_x == XG_BC_PERIODIC, per_y = bc_y == XG_BC_PERIODIC;
+  const bool edge_l = (i0 == 0), edge_r = (i0 + V >= nx);
+  const bool bot = (j0 == 0);  // patch row -1 lies below the array
+  const int64_t lidx = edge_l ? (per_x ? nx - 1 : 0) : i0 - 1;
+  const int64_t ridx = edge_r ? (per_x ? 0 : nx - 1) : i0 + V;
+  const bool shl = V > 1 && (ntl & 1);
+  const bool own_l = !shl || (threadIdx.x & 63) == 0 || edge_l;
+  const bool own_r = !shl || (threadIdx.x & 63) == 63 || edge_r;
+  // patch row p (0 .. SEG+1) is array row j0 + p - 1, wrapped (periodic) or clamped; rows beyond ny (short tails) repeat
+  // row ny-1 and feed nothing that is stored
+  int64_t rw[SEG + 2];
+#pragma unroll
+  for (int p = 0; p < SEG + 2; ++p) {
+    const int64_t g = j0 + p - 1;
+    rw[p] = g < 0 ? (per_y ? ny - 1 : 0) : (g >= ny ? ((per_y && g == ny) ? 0 : ny - 1) : g);
+  }
+  // U[p][1 + k] / W[p][1 + k]: u / v at patch row p, column i0 + k; [0]: column i0 - 1, [V + 1]: column i0 + V
+  real U[SEG + 2][V + 2], W[SEG + 2][V + 2];
+  {
+    const real* pu = u + base;
+    const real* pv = v + base;
+#pragma unroll
+    for (int p = 0; p < SEG + 2; ++p) {
+      const T tu = *reinterpret_cast<const T*>(pu + rw[p] * nx + i0);
+      const T tv = *reinterpret_cast<const T*>(pv + rw[p] * nx + i0);
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        U[p][1 + k] = vec_at(tu, k);
+        W[p][1 + k] = vec_at(tv, k);
+      }
+      U[p][0] = own_l ? pu[rw[p] * nx + lidx] : real(0);
+      W[p][0] = own_l ? pv[rw[p] * nx + lidx] : real(0);
+      U[p][V + 1] = own_r ? pu[rw[p] * nx + ridx] : real(0);
+      W[p][V + 1] = own_r ? pv[rw[p] * nx + ridx] : real(0);
+    }
+  }
+  // the planes at the patch's points (wrapped / clamped like the fields: what a clamped index reads is overridden).
+  // At the centre, [p][c]: row j0 + p - 1, column i0 + c - 1; at the vorticity point, [p][c]: row j0 + p, column i0 + c
+  real RA[SEG + 1][V + 1], ND[SEG + 1][V + 1], RZ[SEG + 1][V + 1], NZ[SEG + 1][V + 1];
+  T DXC[SEG], DYC[SEG], DYG[SEG], DXG[SEG];
+  if (MET || VIS) {
+    int64_t mb[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) mb[k] = mt.p[k] ? area_outer_off(mt.ai[k], o) : 0;
+    const bool vec = (ntl & 8) != 0;
+    // `r0`: the patch row of dst[0]; `left`: the extra column is the one left of the vector (else the one right of it)
+    auto plane = [&](real (&dst)[SEG + 1][V + 1], int k, int r0, bool left) {
+      const real* m = mt.p[k];
+      const int64_t sy = mt.sy[k], sx = mt.sx[k];
+#pragma unroll
+      for (int p = 0; p < SEG + 1; ++p) {
+        const int64_t off = mb[k] + rw[p + r0] * sy;
+        const T row = vec ? *reinterpret_cast<const T*>(m + off + i0) : ldm<T>(m, off + i0 * sx, sx);
+#pragma unroll
+        for (int c = 0; c < V; ++c) dst[p][c + (left ? 1 : 0)] = vec_at(row, c);
+        dst[p][left ? 0 : V] = m[off + (left ? lidx : ridx) * sx];
+      }
+    };
+    auto rows = [&](T (&dst)[SEG], int k) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const int64_t off = mb[k] + rw[s_ + 1] * mt.sy[k];
+        dst[s_] = vec ? *reinterpret_cast<const T*>(mt.p[k] + off + i0) : ldm<T>(mt.p[k], off + i0 * mt.sx[k], mt.sx[k]);
+      }
+    };
+    if (MET) {
+      plane(RA, 0, 0, true);
+      plane(RZ, 1, 1, false);
+    }
+    if (VIS) {
+      plane(ND, 6, 0, true);
+      plane(NZ, 7, 1, false);
+    }
+    if (MET) {
+      rows(DXC, 2);
+      rows(DYC, 3);
+      rows(DYG, 4);
+      rows(DXG, 5);
+    }
+  }
+  if (shl) {
+#pragma unroll
+    for (int p = 0; p < SEG + 2; ++p) {
+      const real ul = from_lane_below(U[p][V]), wl = from_lane_below(W[p][V]);   // DPP wave_shr:1 (lane 0 is `own_l`)
+      const real ur = from_lane_above(U[p][1]), wr = from_lane_above(W[p][1]);   // DPP wave_shl:1 (lane 63 is `own_r`)
+      if (!own_l) { U[p][0] = ul; W[p][0] = wl; }
+      if (!own_r) { U[p][V + 1] = ur; W[p][V + 1] = wr; }
+    }
+  }
+  // the pads of the first stages at a fill boundary: u below row 0 and right of the last column, v left of column 0 and
+  // above the last row (where two of them meet, the value feeds only products that are pads themselves)
+  if (bot && bc_y == XG_BC_FILL) {
+#pragma unroll
+    for (int c = 0; c < V + 2; ++c) U[0][c] = fill_y;
+  }
+  if (bc_y == XG_BC_FILL) {
+#pragma unroll
+    for (int p = 1; p < SEG + 2; ++p) {
+      if (j0 + p - 1 == ny) {  // the row above the last one (wave-uniform)
+#pragma unroll
+        for (int c = 0; c < V + 2; ++c) W[p][c] = fill_y;
+      }
+    }
+  }
+  if (bc_x == XG_BC_FILL) {
+#pragma unroll
+    for (int p = 0; p < SEG + 2; ++p) {
+      if (edge_l) W[p][0] = fill_x;
+      if (edge_r) U[p][V + 1] = fill_x;
+    }
+  }
+  const bool ovr_x_hi = edge_r && !per_x, ovr_x_lo = edge_l && !per_x, ovr_y_lo = bot && !per_y;
+  const bool ext_x = bc_x == XG_BC_EXTEND, ext_y = bc_y == XG_BC_EXTEND;
+  // P = D [* nu_d] at rows j0-1 .. j0+SEG-1, columns i0-1 .. i0+V-1; Q = zeta [* nu_z] at rows j0 .. j0+SEG, columns
+  // i0 .. i0+V
+  real P[SEG + 1][V + 1], Q[SEG + 1][V + 1];
+#pragma unroll
+  for (int p = 0; p < SEG + 1; ++p) {
+#pragma unroll
+    for (int c = 0; c < V + 1; ++c) {
+      real d = (U[p][c + 1] - U[p][c]) + (W[p + 1][c] - W[p][c]);
+      if (MET) d = d / RA[p][c];
+      if (VIS) d = d * ND[p][c];
+      P[p][c] = d;
+      real z = (W[p + 1][c + 1] - W[p + 1][c]) - (U[p + 1][c + 1] - U[p][c + 1]);
+      if (MET) z = z / RZ[p][c];
+      if (VIS) z = z * NZ[p][c];
+      Q[p][c] = z;
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < SEG + 1; ++p) {
+    if (p > 0 && ovr_x_lo) P[p][0] = ext_x ? P[p][1] : fill_x;
+    if (ovr_x_hi) Q[p][V] = ext_x ? Q[p][V - 1] : zfill_x;
+    if (p > 0 && j0 + p == ny && !per_y) {  // the row above the last one (wave-uniform)
+#pragma unroll
+      for (int c = 0; c < V; ++c) Q[p][c] = ext_y ? Q[p - 1][c] : zfill_y;
+    }
+  }
+  if (ovr_y_lo) {
+#pragma unroll
+    for (int c = 1; c < V + 1; ++c) P[0][c] = ext_y ? P[1][c] : fill_y;
+  }
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    if (s_ < nrow) {
+      T gu, gv;
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        real dx = P[s_ + 1][c + 1] - P[s_ + 1][c];
+        real zy = Q[s_ + 1][c] - Q[s_][c];
+        real dy = P[s_ + 1][c + 1] - P[s_][c + 1];
+        real zx = Q[s_][c + 1] - Q[s_][c];
+        if (MET) {
+          dx = dx / vec_at(DXC[s_], c);
+          zy = zy / vec_at(DYG[s_], c);
+          dy = dy / vec_at(DYC[s_], c);
+          zx = zx / vec_at(DXG[s_], c);
+        }
+        vec_set(gu, c, dx - zy);
+        vec_set(gv, c, dy + zx);
+      }
+      const int64_t off = base + (j0 + s_) * nx + i0;
+      stg<T, NTS>(out_u + off, gu);  // (two outputs: plain `nt`, as K7h)
+      stg<T, NTS>(out_v + off, gv);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // K7i: the horizontal gradient of the hydrostatic pressure in ONE pass over (lead, Z, Y, X), one field in, two out:
 //   t[k]  = nan0(b[k] * w[k])                     the weighted buoyancy, a NaN product counts as 0 (the scans' nancumsum)
 //   p[0]  = Z pad (fill: fill_z, extend: p[1]),   p[k+1] = t[0] + .. + t[k], added in sequence (the first sum is t[0] itself)
@@ -2163,6 +2363,68 @@ int XG_FN(xg_momentum_advection)(const real* u, const real* v, const real* corio
 #undef XG_N
 #undef XG_GO
   });
+}
+
+// K7k's launcher: the six metrics all or none, the two coefficient planes both or none
+static int hvisc_impl(const real* u, const real* v, const real* const planes[8], const int64_t* const strides[8],
+                      real* out_u, real* out_v, const int64_t* shape, int ndim, int bc_x, real fill_x, real zfill_x,
+                      int bc_y, real fill_y, real zfill_y, void* stream) {
+  const char* name = "horizontal viscosity";
+  if (!u || !v || !out_u || !out_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 2, {bc_x, bc_y}, XG_BC_EXTEND))) return rc;
+  int nmet = 0, nvis = 0;
+  for (int k = 0; k < 8; ++k) (k < 6 ? nmet : nvis) += planes[k] != nullptr;
+  if (nmet != 0 && nmet != 6) return fail(XG_ERR_INVALID, "horizontal viscosity: the six metrics rA, rAz, dxC, dyC, dyG, dxG, or none");
+  if (nvis != 0 && nvis != 2) return fail(XG_ERR_INVALID, "horizontal viscosity: both coefficients nu_d, nu_z, or none");
+  FusedPlan p;
+  const bool al = aligned16(u) && aligned16(v) && aligned16(out_u) && aligned16(out_v);
+  if ((rc = fused_plan(&p, name, shape, ndim, 2, al, true, stream)) || p.empty) return rc;
+  HviscPlanes mt;
+  memset(&mt, 0, sizeof(mt));
+  for (int k = 0; k < 8; ++k) {
+    mt.p[k] = planes[k];
+    if ((rc = area_index(planes[k], strides[k], shape, ndim, &mt.ai[k], &mt.sy[k], &mt.sx[k]))) return rc;
+  }
+  // bit 0: the lane neighbours by DPP (K7d), bit 3: every plane that is there is an aligned vector in every row
+  int vnt = vec_nt_bits(1);
+  const bool met = nmet != 0, vis = nvis != 0;
+  bool all_shared = met || vis;
+  if (met || vis) {
+    bool mv = p.V > 1;
+    for (int k = 0; k < 8; ++k) {
+      if (mt.p[k]) mv = mv && plane_vec_ok(mt.p[k], mt.ai[k], mt.sy[k], mt.sx[k]);
+      all_shared = all_shared && planes_shared(mt.p[k], mt.ai[k]);
+    }
+    vnt |= mv ? 8 : 0;
+  }
+  // 8-row bands as K7h's four planes; 4 with all eight (K7c: the more planes, the lower the band)
+  fused_band(&p, all_shared, (met && vis) ? (band_rows() + 3) / 4 : (band_rows() + 1) / 2, (u64)p.outer);
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, C_, NTS) do { hipLaunchKernelGGL((k_hvisc<V_, M_, C_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, u, v, out_u, out_v, o0, nouter, nblk, p.ny, p.nx, p.fnt, p.fns, p.zb, bc_x, fill_x, zfill_x, bc_y, fill_y, zfill_y, mt, vnt); } while (0)
+#define XG_N(V_, M_, C_) do { if (p.nts) XG_GO(V_, M_, C_, true); else XG_GO(V_, M_, C_, false); } while (0)
+#define XG_C(V_, M_) do { if (vis) XG_N(V_, M_, true); else XG_N(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (met) XG_C(V_, true); else XG_C(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_C
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+int XG_FN(xg_horizontal_viscosity)(const real* u, const real* v, const real* rA, const int64_t* rA_strides, const real* rAz,
+                                   const int64_t* rAz_strides, const real* dxC, const int64_t* dxC_strides, const real* dyC,
+                                   const int64_t* dyC_strides, const real* dyG, const int64_t* dyG_strides, const real* dxG,
+                                   const int64_t* dxG_strides, const real* nu_d, const int64_t* nu_d_strides,
+                                   const real* nu_z, const int64_t* nu_z_strides, real* out_u, real* out_v,
+                                   const int64_t* shape, int ndim, int bc_x, real fill_x, real zfill_x, int bc_y,
+                                   real fill_y, real zfill_y, void* stream) {
+  const real* const planes[8] = {rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z};
+  const int64_t* const strides[8] = {rA_strides, rAz_strides, dxC_strides, dyC_strides, dyG_strides, dxG_strides,
+                                     nu_d_strides, nu_z_strides};
+  return hvisc_impl(u, v, planes, strides, out_u, out_v, shape, ndim, bc_x, fill_x, zfill_x, bc_y, fill_y, zfill_y, stream);
 }
 
 // K7i's launcher: (lead, Z, Y, X) fields, three optional broadcast metrics (the Z weight, dxC, dyC), one wave per column

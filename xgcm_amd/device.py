@@ -1367,6 +1367,36 @@ def momentum_advection(u, v, coriolis, rAz, dxC, dyC, bc_x: str, bc_y: str, fill
     return out_u, out_v
 
 
+def horizontal_viscosity(u, v, rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z, bc_x: str, bc_y: str, fill_x: float = 0.0,
+                         fill_y: float = 0.0, zfill_x: Optional[float] = None, zfill_y: Optional[float] = None):
+    """Fused vector-invariant harmonic viscosity in one pass (xg_horizontal_viscosity_f64): (gu, gv) with
+    gu = d(D * nu_d) / dx - d(zeta * nu_z) / dy, gv = d(D * nu_d) / dy + d(zeta * nu_z) / dx, D = divergence(u, v) / rA,
+    zeta = vorticity(u, v) / rAz.  The six metrics rA, rAz, dxC, dyC, dyG, dxG all given or all None; the two coefficients
+    both given or both None.  `zfill_x` / `zfill_y` pad the product zeta * nu_z (default: `fill_x` / `fill_y`)."""
+    lib = _MEM.lib()
+    dt, sfx = _common(u, v, rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z)
+    u, v = asdevice(u, dt), asdevice(v, dt)
+    if u.shape != v.shape:
+        raise ValueError("horizontal_viscosity: u and v must have the same shape")
+    shape = list(u.shape)
+    out_u = _empty(shape, dtype=dt, device=u.device)
+    out_v = _empty(shape, dtype=dt, device=u.device)
+    if out_u.numel() == 0:
+        return out_u, out_v
+    mets = [_prep_metric(m, dt) for m in (rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z)]
+    margs = []
+    for m, what in zip(mets, ("rA", "rAz", "dxC", "dyC", "dyG", "dxG", "nu_d", "nu_z")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
+    _check(
+        getattr(lib, "xg_horizontal_viscosity_" + sfx)(u.data_ptr(), v.data_ptr(), *margs, out_u.data_ptr(),
+                                                       out_v.data_ptr(), _hip.i64(shape), len(shape), _hip.BC[bc_x],
+                                                       float(fill_x), float(fill_x if zfill_x is None else zfill_x),
+                                                       _hip.BC[bc_y], float(fill_y),
+                                                       float(fill_y if zfill_y is None else zfill_y), _stream())
+    )
+    return out_u, out_v
+
+
 def laplacian(a, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, dxC=None, dyC=None, dyG=None,
               dxG=None, area=None) -> torch.Tensor:
     """Fused finite-volume del2 in one pass (xg_laplacian_f64): Fx = (a - a[x-1]) / dxC * dyG, Fy = (a - a[y-1]) / dyC

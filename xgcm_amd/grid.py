@@ -1901,6 +1901,113 @@ class Grid:
         gv = gv._replace(data=_dev.tohost(ov) if host else ov)
         return (to_xarray(gu), to_xarray(gv)) if was_xr else (gu, gv)
 
+    def horizontal_viscosity(self, u, v, viscosity_d=None, viscosity_z=None, x_axis: str = "X", y_axis: str = "Y",
+                             padding=None, fill_value=None, metric_weighted: bool = True):
+        """Vector-invariant harmonic viscosity, del2 u = d/dx(D) - d/dy(zeta) and del2 v = d/dy(D) + d/dx(zeta) with D the
+        horizontal divergence and zeta the relative vorticity (MITgcm's mom_vi_hdissip, harmonic part), in ONE pass: u and
+        v are read once and the two tendencies written once (32 B/cell in float64, against about 150-200 for the seven to
+        nine launches of the chain).  Returns `(gu, gv)`, gu at u's points, gv at v's.
+
+        u at (Y:center, X:left), v at (Y:left, X:center).  `viscosity_d` is a coefficient at the cell centre, where D
+        lives, `viscosity_z` one at the vorticity point (Y:left, X:left) -- the Smagorinsky / Leith form; each may have any
+        subset of its stage's dims (a full (lead, Y, X) field included).  A scalar viscosity is the caller's product of the
+        result, and `grid.horizontal_viscosity(*grid.horizontal_viscosity(u, v))` is the biharmonic operator.
+        Bit-identical, dims, coords and names included, to the chain
+
+            kw = dict(padding=padding, fill_value=fill_value)
+            div  = grid.divergence(u, v, x_axis, y_axis, metric_weighted=metric_weighted, **kw)   # centre
+            zeta = grid.vorticity(u, v, x_axis, y_axis, metric_weighted=metric_weighted, **kw)    # (Y:left, X:left)
+            if viscosity_d is not None: div  = div * viscosity_d
+            if viscosity_z is not None: zeta = zeta * viscosity_z
+            dx, dy = grid.gradient(div, x_axis, y_axis, metric_weighted=metric_weighted, **kw)    # centre -> left, at u's / v's points
+            op = grid.derivative if metric_weighted else grid.diff
+            zy = op(zeta, y_axis, **kw)                                                           # left -> centre along Y: at u's points
+            zx = op(zeta, x_axis, **kw)                                                           # left -> centre along X: at v's points
+            gu = dx - zy
+            gv = dy + zx
+
+        Pads: every stage pads with its axis's own boundary on the side the chain pads it -- u right of the last column
+        and v above the last row (D), v left of the first column and u below the first row (zeta), the PRODUCT D * nu_d
+        left of the first column and below the first row, the PRODUCT zeta * nu_z above the last row and right of the last
+        column.  Periodic: the stage's own value at the wrapped index; extend: at the clamped index; fill: `fill_value`
+        itself, never a quotient or a product formed from it.
+
+        Signed zeros: `divergence`, `vorticity` and `gradient` turn a -0.0 fill value into +0.0, the one-axis operators
+        of the last stage hand it on as it is.  The kernel takes a separate fill pair for the pads of zeta * nu_z, so a
+        -0.0 fill goes through the one pass too and leaves the chain's bit patterns.
+
+        Metrics: with `metric_weighted`, whatever `get_metric` returns at each stage's dims -- the (X, Y) metric at the
+        centre and at the vorticity point, the X metric at u's and the Y metric at v's points (the gradient), the Y metric
+        at u's and the X metric at v's points (the differences of zeta); the kernel takes all six or none.
+
+        The chain itself runs (the same calls in the same order) for integer, float16 or mixed dtypes (coefficients and
+        metrics included), for (Y, X) not last or fields of different shapes, for chunked inputs, coefficients or metrics,
+        for a coefficient or metric with dims its stage lacks, for exactly one of the two coefficients, for a metric
+        lookup that raises (the chain raises it), for a missing boundary on either axis (the chain raises), on grids with
+        face connections or a fold along either axis, and for anything else `_second_order_plan` declines."""
+        args = (u, v, viscosity_d, viscosity_z)
+        (u, xr1), (v, xr2), (nud, xr3), (nuz, xr4) = (self._wrap_in(a) for a in args)
+        was_xr = xr1 or xr2 or xr3 or xr4
+        lead, u_dims, v_dims, c_dims, z_dims = self._c_grid_vector(u, v, x_axis, y_axis, "horizontal viscosity")
+        plan = None
+        mets = {}
+        if (u.dims == u_dims and v.dims == v_dims and (nud is None) == (nuz is None)
+                and (nud is None or (isinstance(nud, DataArray) and isinstance(nuz, DataArray)))):
+            try:
+                if metric_weighted:
+                    for key, dims, axes, layout in (("rA", c_dims, (x_axis, y_axis), None), ("rAz", z_dims, (x_axis, y_axis), None),
+                                                    ("dxC", u_dims, (x_axis,), None), ("dyC", v_dims, (y_axis,), None),
+                                                    ("dyG", u_dims, (y_axis,), u_dims), ("dxG", v_dims, (x_axis,), v_dims)):
+                        mets[key] = (self._resident(self.get_metric(_DimsOnly(dims), axes, _layout=layout), u.data), dims)
+            except (KeyError, ValueError):
+                mets = None  # (the chain raises it where the chain looks the metric up)
+            if mets is not None:
+                if nud is not None:
+                    mets["nu_d"] = (self._resident(nud, u.data), c_dims)
+                    mets["nu_z"] = (self._resident(nuz, u.data), z_dims)
+                if all(set(m.dims) <= set(dims) and not _is_chunked(m.data) for m, dims in mets.values()):
+                    plan = self._second_order_plan([u, v], x_axis, y_axis, padding, fill_value, [m for m, _ in mets.values()])
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            u, v, viscosity_d, viscosity_z = args
+            div = self.divergence(u, v, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+            zeta = self.vorticity(u, v, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+            if viscosity_d is not None:
+                div = div * viscosity_d
+            if viscosity_z is not None:
+                zeta = zeta * viscosity_z
+            dx, dy = self.gradient(div, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+            op = self.derivative if metric_weighted else self.diff
+            zy = op(zeta, y_axis, **kw)
+            zx = op(zeta, x_axis, **kw)
+            gu = dx - zy
+            gv = dy + zx
+            return gu, gv
+        bcx, bcy, fvx, fvy = plan
+        # the one-axis operators of the last stage hand their fill value on as it is (None: 0.0): a -0.0 keeps its sign there
+        fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
+        zfx, zfy = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis))
+        host = not (_is_tensor(u.data) or _is_tensor(v.data))
+        views = {k: _aligned_view(m, dims) for k, (m, dims) in mets.items()}
+        ou, ov = _dev.horizontal_viscosity(u.data, v.data, *(views.get(k) for k in ("rA", "rAz", "dxC", "dyC", "dyG", "dxG",
+                                                                                     "nu_d", "nu_z")),
+                                           bcx, bcy, fvx, fvy, zfx, zfy)
+        # dims, coords and names as the chain's, step by step over placeholders
+        xl, yl, xc, yc = u_dims[-1], v_dims[-2], v_dims[-1], u_dims[-2]
+        div = _reattach_coords([DataArray(_placeholder(u.shape), c_dims)], self, None, {xc, yc}, [u, v])[0]
+        zeta = _reattach_coords([DataArray(_placeholder(u.shape), z_dims)], self, None, {xl, yl}, [u, v])[0]
+        if nud is not None:
+            div = self._labels_of_binary(div, mets["nu_d"][0])
+            zeta = self._labels_of_binary(zeta, mets["nu_z"][0])
+        dx, dy = self._labels_of_step(div, u_dims, xl), self._labels_of_step(div, v_dims, yl)
+        zy, zx = self._labels_of_step(zeta, u_dims, yc), self._labels_of_step(zeta, v_dims, xc)
+        if metric_weighted and zeta.name is not None:  # (`derivative` names its quotient, `gradient` does not)
+            zy = zy._replace(name=_name_after(zeta.name, mets["dyG"][0]))
+            zx = zx._replace(name=_name_after(zeta.name, mets["dxG"][0]))
+        gu = self._labels_of_binary(dx, zy)._replace(data=_dev.tohost(ou) if host else ou)
+        gv = self._labels_of_binary(dy, zx)._replace(data=_dev.tohost(ov) if host else ov)
+        return (to_xarray(gu), to_xarray(gv)) if was_xr else (gu, gv)
+
     def transform(self, da, axis, target, **kwargs):
         """Convert `da` to new 1-D coordinates along `axis` (linear / log / conservative; reference
         grid.py:1687-1777 -> transform.py:284-514), one HIP kernel launch per call."""
