@@ -5,7 +5,8 @@ xgcm/grid_ufunc.py:966-984).
 
 Host threads -- each on its own `xg_stream_create` stream, and in a second variant all on the SAME stream -- run plain
 and metric stencils, chained scans (`k_cumsum_chain`, whose hand-off workspace is per (device, stream) under a mutex),
-marching scans, weighted reductions, fused vorticity and a deliberately failing call, many times over.  Every result
+marching scans, weighted reductions, fused vorticity, one call each of the nine one-pass operators K7d - K7k (the 3-D ones
+on the array viewed as (1, Z, Y, X)) and a deliberately failing call, many times over.  Every result
 must equal the single-threaded result bit for bit, every thread must read back ITS OWN error text from
 `xg_last_error` (thread-local buffer), and `xg_chain_status` must stay clean (no hand-off gave up, nothing was redone).
 ctypes releases the GIL for the duration of every ABI call, so the calls genuinely overlap.
@@ -43,6 +44,18 @@ def _work(D, inputs, tid):
     out["integrate_z"] = D.reduce1d(a, 0, mz, True)
     out["average_y"] = D.reduce1d(a, 1, m2, "mean_valid")
     out["vorticity"] = D.vorticity(a, a, area, "fill", "fill", 0.0, 0.0)
+    # the one-pass operators K7d - K7k on the same array and metrics; the 3-D entries take it as (1, Z, Y, X)
+    pair = lambda name, r: out.update({name + "_u": r[0], name + "_v": r[1]})  # noqa: E731
+    out["flux_divergence"] = D.flux_divergence(a, a, a, area, "periodic", "extend", 1.5, -0.5)
+    out["laplacian"] = D.laplacian(a, "fill", "periodic", 1.5, -0.5, m2, area, area, m2, area)
+    out["kinetic_energy"] = D.kinetic_energy(a, a, "fill", "extend", 1.5, -0.5)
+    pair("momentum_advection", D.momentum_advection(a, a, m2, area, m2, area, "periodic", "fill", 1.5, -0.5))
+    pair("horizontal_viscosity", D.horizontal_viscosity(a, a, area, m2, m2, area, area, m2, m2, area, "extend", "periodic", 1.5, -0.5))
+    a4, z4, p4, q4 = a.view(1, *a.shape), mz.view(1, -1, 1, 1), area.view(1, *area.shape), m2.view(1, *m2.shape)
+    out["flux_divergence_3d"] = D.flux_divergence_3d(a4, a4, a4, a4, p4, z4, "periodic", "extend", "fill", 1.5, -0.5, 0.25)
+    out["vertical_velocity"] = D.vertical_velocity(a4, a4, q4, z4, p4, z4, p4, "extend", "periodic", "fill", 1.5, -0.5, 0.25)
+    pair("hydrostatic_pressure_gradient", D.hydrostatic_pressure_gradient(a4, z4, q4, p4, "periodic", "fill", "extend", 1.5, -0.5, 0.25))
+    pair("vertical_momentum_advection", D.vertical_momentum_advection(a4, a4, a4, z4, z4, "fill", "extend", "periodic", 1.5, -0.5, 0.25))
     return {k: v.clone() for k, v in out.items()}
 
 
