@@ -45,6 +45,8 @@
  *   xg_hydrostatic_pressure_gradient_f64  gradient(interp(cumint(b, Z), Z)): the pressure-gradient force, one pass
  *   xg_vertical_momentum_advection_f64  -interp(interp(w, X / Y) * diff(u / v, Z), Z): w du/dz and w dv/dz, one pass
  *   xg_horizontal_viscosity_f64  gradient(divergence * nu_d) -/+ diff(vorticity * nu_z): the harmonic viscosity, one pass
+ *   xg_vertical_diffusion  derivative(derivative(a, Z) * kappa, Z): vertical diffusion / viscosity, one pass (float64 and
+ *                      float32 through one entry: the element type is an argument)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -429,6 +431,23 @@ int xg_vertical_momentum_advection_f64(const double* u, const double* v, const d
                                        const int64_t* mu_strides, const double* mv, const int64_t* mv_strides,
                                        double* out_u, double* out_v, const int64_t* shape, int ndim, int bc_x,
                                        double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
+/* Vertical diffusion d/dz(kappa da/dz) of one field `a` of `shape` (.., Z, Y, X) at Z:center, one pass; `out` has the same
+ * shape.  `dtype` is the element type of every array: XG_T_F64 or XG_T_F32 (enum xg_dtype below); any other code is
+ * XG_ERR_INVALID.  It replaces the chain
+ *   g = a[k] - a[k-1]  [/ mf]        xg_stencil1d diff along Z, center -> left (outer = 0) or center -> outer (outer = 1)
+ *   f = g * kappa                    xg_binary (kappa NULL: f = g)
+ *   out = f[k+1] - f[k]  [/ mc]      xg_stencil1d diff along Z, left | outer -> center
+ * in this order of operations: f[k] = ((a[k] - a[k-1]) / mf[k]) * kappa[k], out[k] = (f[k+1] - f[k]) / mc[k].
+ * outer = 0: nz flux levels; a is padded above level 0 (periodic: a[nz-1], extend: a[0], fill: fill_z) and the FLUX beyond
+ * level nz-1 (periodic: f[0], extend: f[nz-1], fill: fill_z itself, not a flux formed from it).
+ * outer = 1: nz + 1 flux levels; a is padded on both sides and the flux needs no pad.
+ * kappa and mf (the metric of the flux) live at the flux levels: their strides are broadcast strides (0 = broadcast) against
+ * `shape` with nz (outer = 0) or nz + 1 (outer = 1) levels along Z; mc (the metric of the result) against `shape` itself.
+ * NULL kappa, mf or mc: absent.  bc_z: XG_BC_PERIODIC, XG_BC_FILL or XG_BC_EXTEND; fill_z is cast to the element type
+ * (-0.0 and NaN keep their bits). */
+int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* kappa_strides, const void* mf,
+                          const int64_t* mf_strides, const void* mc, const int64_t* mc_strides, void* out,
+                          const int64_t* shape, int ndim, int outer, int bc_z, double fill_z, void* stream);
 
 /* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
 /* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).

@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity against their chains; 5pg, 5vm, 5hv: the last three pairs, each alone), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion against their chains; 5pg, 5vm, 5hv, 5vd: the last four pairs, each alone), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -187,6 +187,39 @@ def run_horizontal_viscosity(reps, nz=90, n=4320):
     rec(5, "horizontal_viscosity fused (rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z), periodic/extend: 2 reads + 2 writes", med(tf), cells, bpc)
     rec(5, "horizontal_viscosity as its chain (9 launches), fused-equivalent bytes", med(tc), cells, bpc)
     print(json.dumps({"config": 5, "check": "fused horizontal_viscosity == chain bit for bit at full size", "ok": ok,
+                      "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
+                      "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_vertical_diffusion(reps, nz=90, n=4320):
+    """vertical_diffusion in one pass against its chain of three launches (derivative to Z:outer, the product with a 3-D
+    kappa, derivative back to the centre; drC(Zp1), drF(Z); `extend`: no flux through the top and the bottom), timed in
+    turns, every paired round reported"""
+    coords = {"XC": ("XC", np.arange(n) + 0.5), "XG": ("XG", np.arange(n) * 1.0), "YC": ("YC", np.arange(n) + 0.5),
+              "YG": ("YG", np.arange(n) * 1.0), "Z": ("Z", np.arange(nz) + 0.5), "Zp1": ("Zp1", np.arange(nz + 1) * 1.0)}
+    ds = Dataset({"drF": DataArray(D.synthetic((nz,), 33, 0, 1000.0, 1000.0), ("Z",)),
+                  "drC": DataArray(D.synthetic((nz + 1,), 34, 0, 1000.0, 1000.0), ("Zp1",))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                            "Z": {"center": "Z", "outer": "Zp1"}},
+                padding={"X": "periodic", "Y": "extend", "Z": "extend"}, metrics={("Z",): ["drF", "drC"]}, autoparse_metadata=False)
+    T = DataArray(D.synthetic((nz, n, n), 61), ("Z", "YC", "XC"))
+    K = DataArray(D.synthetic((nz + 1, n, n), 62, 0, 50.0, 100.0), ("Zp1", "YC", "XC"))
+    cells = nz * n * n
+
+    def chain():
+        return grid.derivative(grid.derivative(T, "Z", to="outer") * K, "Z")
+
+    got, want = grid.vertical_diffusion(T, K), chain()
+    ok = bool(torch.equal(got.data, want.data))
+    del got, want
+    torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(lambda: grid.vertical_diffusion(T, K), chain, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    bpc = 24 + 8 / nz   # a and out, nz + 1 levels of kappa
+    rec(5, "vertical_diffusion fused derivative(derivative(a, Z, to=outer) * kappa, Z), 3-D kappa, drC / drF, extend: 2 reads + 1 write", med(tf), cells, bpc)
+    rec(5, "vertical_diffusion as its chain (3 launches), fused-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": "fused vertical_diffusion == chain bit for bit at full size", "ok": ok,
                       "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
                       "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
@@ -829,6 +862,8 @@ def main():
         run_vertical_momentum_advection(a.reps)
     if cfgs & {"5x", "5hv"}:
         run_horizontal_viscosity(a.reps)
+    if cfgs & {"5x", "5vd"}:
+        run_vertical_diffusion(a.reps)
     ranks.close()
 
 

@@ -204,6 +204,9 @@ DTYPE = {"bool": 0, "int8": 1, "int16": 2, "int32": 3, "int64": 4, "uint8": 5, "
          "float32": 9, "float64": 10, "float16": 11}
 SIGNATURES["xg_copy_nd"] = (C.c_int, [_vp, _i64p, _vp, _i64p, _i64p, C.c_int, C.c_int, _vp])
 SIGNATURES["xg_convert"] = (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int, _vp])
+# one entry for float64 and float32 (the element type, a DTYPE code, comes first): no _f64 / _f32 twins
+SIGNATURES["xg_vertical_diffusion"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int,
+                                               C.c_int, C.c_double, _vp])
 
 SUFFIX = {"float64": "f64", "float32": "f32", "int64": "i64", "int32": "i32"}
 

@@ -684,6 +684,77 @@ int vmomadv(const R* u, const R* v, const R* w, const R* const met[2], const int
   return XG_OK;
 }
 
+// the vertical diffusion of the header as the three passes of its chain over one (Z, Y, X) volume at a time, each into a
+// temporary: the difference of `a` to the level above at the flux levels (nz of them, `outer`: nz + 1) over the flux'
+// metric, the product with kappa, the difference of the flux to the next level's over the result's metric.
+// arr[] = {kappa, the metric of the flux, the metric of the result}
+template <typename R>
+int vdiff(const R* a, const R* const arr[3], const int64_t* const st[3], R* out, const int64_t* shape, int ndim, int outer,
+          int bc_z, R fill_z) {
+  if (!a || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  if (bc_z < XG_BC_PERIODIC || bc_z > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", bc_z);
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "outer %d is neither 0 (left) nor 1", outer);
+  for (int k = 0; k < 3; ++k)
+    if (arr[k] && !st[k]) return fail(XG_ERR_INVALID, "metric without strides");
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx, vol = nz * plane;
+  const int64_t nf = nz + outer;  // flux levels
+  int64_t lead = 1;
+  for (int d = 0; d < ndim - 3; ++d) lead *= shape[d];
+  if (lead == 0 || vol == 0) return XG_OK;
+  std::vector<R> g((size_t)(nf * plane)), f((size_t)(nf * plane));
+  for (int64_t o = 0; o < lead; ++o) {
+    int64_t rem = o, off[3] = {0, 0, 0};  // the lead index decomposed for the broadcast strides
+    for (int d = ndim - 4; d >= 0; --d) {
+      const int64_t i = rem % shape[d];
+      rem /= shape[d];
+      for (int k = 0; k < 3; ++k)
+        if (arr[k]) off[k] += i * st[k][d];
+    }
+    auto at = [&](int k, int64_t z, int64_t j, int64_t i) -> R {
+      return arr[k][off[k] + z * st[k][ndim - 3] + j * st[k][ndim - 2] + i * st[k][ndim - 1]];
+    };
+    const R* pa = a + o * vol;
+    // level z of the padded field: a level of `a`, or its pad above level 0 / below level nz - 1
+    auto level = [&](int64_t z, int64_t c) -> R {
+      if (z >= 0 && z < nz) return pa[z * plane + c];
+      if (bc_z == XG_BC_FILL) return fill_z;
+      if (bc_z == XG_BC_PERIODIC) return pa[(z < 0 ? nz - 1 : 0) * plane + c];
+      return pa[(z < 0 ? 0 : nz - 1) * plane + c];
+    };
+    // (1) the gradient at the flux levels
+    for (int64_t z = 0; z < nf; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t c = j * nx + i;
+          R d = level(z, c) - level(z - 1, c);
+          if (arr[1]) d = d / at(1, z, j, i);
+          g[z * plane + c] = d;
+        }
+    // (2) the flux
+    for (int64_t z = 0; z < nf; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t c = z * plane + j * nx + i;
+          f[c] = arr[0] ? g[c] * at(0, z, j, i) : g[c];
+        }
+    // (3) its difference to the next level's; `left` pads the flux beyond its last level
+    for (int64_t z = 0; z < nz; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t c = j * nx + i;
+          R next;
+          if (z + 1 < nf) next = f[(z + 1) * plane + c];
+          else if (bc_z == XG_BC_FILL) next = fill_z;
+          else next = f[((bc_z == XG_BC_PERIODIC) ? 0 : nz - 1) * plane + c];
+          R d = next - f[z * plane + c];
+          if (arr[2]) d = d / at(2, z, j, i);
+          out[o * vol + z * plane + c] = d;
+        }
+  }
+  return XG_OK;
+}
+
 // kinetic energy (ke_only) and the vector-invariant momentum advection of the header: the stages of the chain one after
 // the other over whole planes, each read through `get`, which pads a plane by one cell on one axis at a time (periodic:
 // the plane's own value at the wrapped index, extend: at the clamped index, fill: the fill value of that axis).
@@ -1195,6 +1266,21 @@ static double half_to_double(uint16_t h) {
   else v = std::ldexp((double)(m | 0x400), e - 25);
   return (h & 0x8000) ? -v : v;
 }
+int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* ks, const void* mf, const int64_t* mfs,
+                          const void* mc, const int64_t* mcs, void* out, const int64_t* shape, int ndim, int outer, int bc_z,
+                          double fill_z, void*) {
+  const int64_t* const st[3] = {ks, mfs, mcs};
+  if (dtype == XG_T_F64) {
+    const double* const arr[3] = {(const double*)kappa, (const double*)mf, (const double*)mc};
+    return vdiff<double>((const double*)a, arr, st, (double*)out, shape, ndim, outer, bc_z, fill_z);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const arr[3] = {(const float*)kappa, (const float*)mf, (const float*)mc};
+    return vdiff<float>((const float*)a, arr, st, (float*)out, shape, ndim, outer, bc_z, (float)fill_z);
+  }
+  return fail(XG_ERR_INVALID, "vertical diffusion: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+
 int xg_convert(const void* src, int st, void* dst, int dt, uint64_t n, int via, double scale, int flags, void*) {
   if (st < XG_T_BOOL || st > XG_T_F16 || dt < XG_T_BOOL || dt > XG_T_F16) return fail(XG_ERR_INVALID, "unknown element type (%d -> %d)", st, dt);
   if (via < -1 || via > XG_T_U64) return fail(XG_ERR_INVALID, "via_type %d is not an integer type", via);

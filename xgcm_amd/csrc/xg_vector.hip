@@ -1786,6 +1786,126 @@ __global__ __launch_bounds__(BLOCK) void k_vmomadv(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7l: vertical diffusion d/dz(kappa da/dz) in ONE pass over (lead, Z, Y, X), one field in, one out:
+//   f[k]   = ((a[k] - a[k-1]) [/ mf[k]]) [* kappa[k]]        the diffusive flux between level k-1 and level k
+//   out[k] = (f[k+1] - f[k]) [/ mc[k]]
+// i.e. derivative (Z, center -> left | outer), the product with kappa, derivative (Z, left | outer -> center).  Pads as the
+// chain's.  `left` (nz flux levels): a above level 0 (periodic: a[nz-1], extend: a[0], fill: fill_z), then the FLUX beyond
+// level nz-1 (periodic: f[0], extend: f[nz-1], fill: fill_z itself).  `outer` (nz+1 flux levels; kappa and mf have nz+1
+// levels): a on both sides (periodic: a[nz-1] above, a[0] below; extend: a[0], a[nz-1]; fill: fill_z), the flux needs none.
+// K7e's decomposition without its X and Y neighbours: a wave owns one (lead, Y segment, X tile) column and marches
+// k = 0 .. nz-1 with a[k] and f[k] in registers; the rows of a[k+1], kappa[k+1] and mf[k+1] are read at level k and form
+// f[k+1].  a and kappa are read once and out written once: 24 B/cell in float64 (16 with a profile kappa(Z) or none).
+// kappa and the two metrics are one broadcast array each; rows that do not vary along Z are loaded once per wave.  Periodic
+// Z costs one more row read before the march (and, `outer`, one after it).
+// ------------------------------------------------------------------------------------------
+template <int V, bool KAP, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_vdiff(
+    const real* __restrict__ a, real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny,
+    int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int bc_z, real fill_z, VolIdx kp, VolIdx mf, VolIdx mc, int ntl) {
+  typedef typename VecT<V>::type T;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+  auto rows = [&](T (&x)[SEG], int64_t k) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) x[s_] = *reinterpret_cast<const T*>(a + col + k * plane + ro[s_] + i0);
+  };
+
+  // the rows of kappa and of the two metrics: in registers, loaded again per level only when the array varies along Z
+  T kr[SEG], mfr[SEG], mcr[SEG];
+  int64_t kpo = 0, mfo = 0, mco = 0;
+  if (KAP) {
+    kpo = area_outer_off(kp.ai, o) + j0 * kp.sy + i0 * kp.sx;
+    load_rows<T, SEG>(kr, kp.p, kpo, kp.sy, kp.sx, nrow, (ntl & 4) != 0);
+  }
+  if (MET) {
+    if (mf.p) {
+      mfo = area_outer_off(mf.ai, o) + j0 * mf.sy + i0 * mf.sx;
+      load_rows<T, SEG>(mfr, mf.p, mfo, mf.sy, mf.sx, nrow, (ntl & 8) != 0);
+    }
+    if (mc.p) {
+      mco = area_outer_off(mc.ai, o) + j0 * mc.sy + i0 * mc.sx;
+      load_rows<T, SEG>(mcr, mc.p, mco, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
+    }
+  }
+  // the flux between two levels from the rows of kappa and mf that are in registers
+  auto flux = [&](const T (&lo)[SEG], const T (&hi)[SEG], T (&f)[SEG]) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      T d = op2<XG_OP_DIFF>(lo[s_], hi[s_]);
+      if (MET) {
+        if (mf.p) d = d / mfr[s_];
+      }
+      if (KAP) d = d * kr[s_];
+      f[s_] = d;
+    }
+  };
+
+  // level 0: f[0] from a padded above it; `left` with periodic Z keeps it for the pad beyond the last level
+  T ac[SEG], fc[SEG], f0[SEG];
+  {
+    T aa[SEG];
+    rows(ac, 0);
+    if (bc_z == XG_BC_PERIODIC) rows(aa, nz - 1);
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (bc_z == XG_BC_FILL) aa[s_] = splat<T>(fill_z);
+      else if (bc_z == XG_BC_EXTEND) aa[s_] = ac[s_];
+    }
+    flux(aa, ac, fc);
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) f0[s_] = fc[s_];
+  }
+  real* po = out + col + j0 * nx + i0;
+  for (int64_t k = 0; k < nz; ++k) {
+    const bool more = k + 1 < nz;
+    T fn[SEG];
+    if (more || outer) {
+      // flux level k+1 exists: a[k+1] (`outer`, last level: the pad of a), then the rows of kappa and mf at k+1
+      T an[SEG];
+      if (more || bc_z == XG_BC_PERIODIC) rows(an, more ? k + 1 : 0);
+      if (!more) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) {
+          if (bc_z == XG_BC_FILL) an[s_] = splat<T>(fill_z);
+          else if (bc_z == XG_BC_EXTEND) an[s_] = ac[s_];
+        }
+      }
+      if (KAP && kp.sz != 0) load_rows<T, SEG>(kr, kp.p, kpo + (k + 1) * kp.sz, kp.sy, kp.sx, nrow, (ntl & 4) != 0);
+      if (MET) {
+        if (mf.p && mf.sz != 0) load_rows<T, SEG>(mfr, mf.p, mfo + (k + 1) * mf.sz, mf.sy, mf.sx, nrow, (ntl & 8) != 0);
+      }
+      flux(ac, an, fn);
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) ac[s_] = an[s_];
+    } else {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_)
+        fn[s_] = (bc_z == XG_BC_PERIODIC) ? f0[s_] : ((bc_z == XG_BC_EXTEND) ? fc[s_] : splat<T>(fill_z));
+    }
+    if (MET && k > 0) {
+      if (mc.p && mc.sz != 0) load_rows<T, SEG>(mcr, mc.p, mco + k * mc.sz, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        T z = op2<XG_OP_DIFF>(fc[s_], fn[s_]);
+        if (MET) {
+          if (mc.p) z = z / mcr[s_];
+        }
+        stg_s<T, NTS>(po + k * plane + s_ * nx, z);
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) fc[s_] = fn[s_];
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -2500,6 +2620,67 @@ int XG_FN(xg_vertical_momentum_advection)(const real* u, const real* v, const re
 #undef XG_GO
   });
 }
+
+// K7l's launcher: one (lead, Z, Y, X) field, kappa and the metric of the flux (both at the flux levels: nz of them, `outer`
+// nz + 1) and the metric of the result, each optional and with broadcast strides, one wave per column.  The ABI has ONE
+// entry for both element types (xg_vertical_diffusion, below); each float build defines its own implementation, hidden.
+__attribute__((visibility("hidden"))) int xg_internal_vdiff_f64(
+    const double* a, const double* kappa, const int64_t* kappa_strides, const double* mf, const int64_t* mf_strides,
+    const double* mc, const int64_t* mc_strides, double* out, const int64_t* shape, int ndim, int outer, int bc_z,
+    double fill_z, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_vdiff_f32(
+    const float* a, const float* kappa, const int64_t* kappa_strides, const float* mf, const int64_t* mf_strides,
+    const float* mc, const int64_t* mc_strides, float* out, const int64_t* shape, int ndim, int outer, int bc_z,
+    float fill_z, void* stream);
+
+int XG_FN(xg_internal_vdiff)(const real* a, const real* kappa, const int64_t* kappa_strides, const real* mf,
+                             const int64_t* mf_strides, const real* mc, const int64_t* mc_strides, real* out,
+                             const int64_t* shape, int ndim, int outer, int bc_z, real fill_z, void* stream) {
+  const char* name = "vertical diffusion";
+  if (!a || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  FusedPlan p;
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, aligned16(a) && aligned16(out), true, stream)) || p.empty) return rc;
+  VolIdx mi[3];  // kappa, the metric of the flux, the metric of the result
+  const real* mp[3] = {kappa, mf, mc};
+  const int64_t* ms[3] = {kappa_strides, mf_strides, mc_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  // bits 2 / 3 / 4: the rows of kappa / the flux metric / the result's metric are aligned vectors (no X neighbour: no bit 0)
+  int vnt = 0;
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool kap = kappa != nullptr, met = mf != nullptr || mc != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, K_, M_, NTS) do { hipLaunchKernelGGL((k_vdiff<V_, K_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, a, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_z, fill_z, mi[0], mi[1], mi[2], vnt); } while (0)
+#define XG_N(V_, K_, M_) do { if (p.nts) XG_GO(V_, K_, M_, true); else XG_GO(V_, K_, M_, false); } while (0)
+#define XG_M(V_, K_) do { if (met) XG_N(V_, K_, true); else XG_N(V_, K_, false); } while (0)
+#define XG_V(V_) do { if (kap) XG_M(V_, true); else XG_M(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_M
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument, the fill is cast to it here
+int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* kappa_strides, const void* mf,
+                          const int64_t* mf_strides, const void* mc, const int64_t* mc_strides, void* out,
+                          const int64_t* shape, int ndim, int outer, int bc_z, double fill_z, void* stream) {
+  if (dtype == XG_T_F64)
+    return xg_internal_vdiff_f64((const double*)a, (const double*)kappa, kappa_strides, (const double*)mf, mf_strides,
+                                 (const double*)mc, mc_strides, (double*)out, shape, ndim, outer, bc_z, fill_z, stream);
+  if (dtype == XG_T_F32)
+    return xg_internal_vdiff_f32((const float*)a, (const float*)kappa, kappa_strides, (const float*)mf, mf_strides,
+                                 (const float*)mc, mc_strides, (float*)out, shape, ndim, outer, bc_z, (float)fill_z, stream);
+  return fail(XG_ERR_INVALID, "vertical diffusion: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
 
 #endif  // !XG_INT
 

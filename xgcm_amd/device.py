@@ -1322,6 +1322,31 @@ def vertical_momentum_advection(u, v, w, mu, mv, bc_x: str, bc_y: str, bc_z: str
     return out_u, out_v
 
 
+def vertical_diffusion(a, kappa, mf, mc, outer: bool, bc_z: str, fill_z: float = 0.0) -> torch.Tensor:
+    """Fused vertical diffusion d/dz(kappa da/dz) in one pass (xg_vertical_diffusion): the difference of `a` to the level
+    above, divided by `mf` and multiplied by `kappa` (the flux), the difference of the flux to the next level's, divided by
+    `mc` (None = that step is absent).  `outer` False: the flux at Z:left -- `a` is padded above level 0, the flux beyond
+    the last level; True: at Z:outer -- `a` is padded on both sides, the flux has one level more and needs no pad.  `kappa`
+    and `mf` broadcast against the flux' shape, `mc` against `a`'s."""
+    lib = _MEM.lib()
+    dt, sfx = _common(a, kappa, mf, mc)
+    a = asdevice(a, dt)
+    if a.dim() < 3:
+        raise ValueError("vertical_diffusion: the field needs (Z, Y, X) as its last three dims")
+    shape = list(a.shape)
+    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
+    kappa, mf, mc = (_prep_metric(m, dt) for m in (kappa, mf, mc))
+    out = _empty(shape, dtype=dt, device=a.device)
+    if out.numel() == 0:
+        return out
+    margs = []
+    for m, against, what in ((kappa, fshape, "kappa"), (mf, fshape, "metric of the flux"), (mc, shape, "metric of the result")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
+    _check(lib.xg_vertical_diffusion(_hip.DTYPE["float32" if sfx == "f32" else "float64"], a.data_ptr(), *margs, out.data_ptr(),
+                                     _hip.i64(shape), len(shape), int(bool(outer)), _hip.BC[bc_z], float(fill_z), _stream()))
+    return out
+
+
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""

@@ -1764,6 +1764,97 @@ class Grid:
         gv = gv._replace(data=_dev.tohost(ov) if host else ov)
         return (to_xarray(gu), to_xarray(gv)) if was_xr else (gu, gv)
 
+    def vertical_diffusion(self, a, kappa=None, z_axis: str = "Z", to=None, padding=None, fill_value=None,
+                           metric_weighted: bool = True):
+        """Vertical mixing d/dz(kappa da/dz) -- the vertical diffusion of a tracer, the vertical viscosity of u or v -- in
+        ONE pass: `a` and `kappa` are read once and the result written once (24 B/cell in float64, 16 with a profile
+        kappa(Z) or none, against 56 for the three launches of the chain); the flux stays in registers.
+
+        `a` at Z:center with its Z dim third from last; the two dims after it are only rows and columns, so `a` may sit
+        at the centre, at u's or at v's points.  `kappa` at the flux position on Z, with dims among those of the flux (a
+        profile kappa(Z), a (Z, Y, X) field, a field with leading dims): it is read through broadcast strides, never
+        materialised.  `to`: the flux position, "left" or "outer" (None: "outer" when the Z axis has one, else "left").
+        Bit-identical, dims, coords and name included, to the chain
+
+            kw = dict(padding=padding, fill_value=fill_value)
+            g = grid.derivative(a, z_axis, to=to, **kw)    # center -> left | outer: (a[k] - a[k-1]) / drC
+            f = g * kappa                                  # the diffusive flux (kappa=None: f = g)
+            out = grid.derivative(f, z_axis, **kw)         # left | outer -> center: (f[k+1] - f[k]) / drF
+
+        (`metric_weighted=False`: `diff` in both places).  Pads where the chain pads.  "left": `a` above level 0
+        (periodic: a[nz-1], extend: a[0], fill: `fill_value`), then the FLUX beyond level nz-1 (periodic: f[0], extend:
+        f[nz-1], fill: `fill_value` itself, not a flux formed from it).  "outer": `a` on both sides; the flux has nz+1
+        levels and needs no pad -- with `extend` it is exactly zero at the top and at the bottom, the no-flux condition.
+
+        The metrics are whatever `get_metric` returns at the flux' and at `a`'s dims (drC / drF, or registered 3-D
+        thicknesses), one broadcast array each.
+
+        The chain itself runs (the same calls in the same order) for integer, float16 or mixed dtypes (a `kappa` of another
+        dtype included), for fewer than three dims or Z not third from last, for another `to` or a position the axis
+        lacks, for a `kappa` that is not at the flux position, has dims `a` lacks or is chunked, for chunked `a`, for a
+        metric that is chunked or has dims its stage lacks, for a metric lookup that raises (the chain raises it), for a Z
+        axis without a boundary, and with face connections or a fold along Z."""
+        args = (a, kappa)
+        (a, xr1), (kappa, xr2) = self._wrap_in(a), self._wrap_in(kappa)
+        was_xr = xr1 or xr2
+        zax = self.axes[z_axis]
+        if to is None:
+            to = "outer" if "outer" in zax.coords else "left"
+        plan = None
+        mf = mc = None
+        served = (isinstance(a, DataArray) and a.ndim >= 3 and to in ("left", "outer") and to in zax.coords
+                  and "center" in zax.coords and a.dims[-3] == zax.coords["center"]
+                  and sum(d in a.dims for d in zax.coords.values()) == 1
+                  and (kappa is None or isinstance(kappa, DataArray)) and not gridops.complex_topology(self, z_axis))
+        if served:
+            tz, zf = zax.coords["center"], zax.coords[to]
+            f_dims = a.dims[:-3] + (zf,) + a.dims[-2:]
+            f_shape = tuple(a.shape[:-3]) + (a.shape[-3] + (1 if to == "outer" else 0),) + tuple(a.shape[-2:])
+            dtype = _dt.np_dtype(a.data)
+            served = dtype in (_dt.FLOAT32, _dt.FLOAT64) and not _is_chunked(a.data)
+            if served and kappa is not None:
+                served = (set(kappa.dims) <= set(f_dims) and not _is_chunked(kappa.data) and _dt.np_dtype(kappa.data) == dtype
+                          and all(kappa.sizes[d] == f_shape[f_dims.index(d)] for d in kappa.dims))
+        if served:
+            try:
+                if metric_weighted:
+                    mf = self._resident(self.get_metric(_DimsOnly(f_dims, a.name), (z_axis,), _layout=f_dims), a.data)
+                    mc = self._resident(self.get_metric(_DimsOnly(a.dims, a.name), (z_axis,), _layout=a.dims), a.data)
+                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data) and _dt.np_dtype(m.data) == dtype)
+                             for m, dims in ((mf, f_dims), (mc, a.dims)))
+            except (KeyError, ValueError):
+                served = False  # (the chain raises it where the chain looks the metric up)
+        if served:
+            bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")[z_axis]
+            fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")[z_axis]
+            # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as it is
+            # (None: 0.0), so a -0.0 or a NaN keeps its bits
+            plan = None if bc is None else (bc, 0.0 if fval is None else float(fval))
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            a, kappa = args
+            step = self.derivative if metric_weighted else self.diff
+            g = step(a, z_axis, to=to, **kw)
+            f = g if kappa is None else g * kappa
+            return step(f, z_axis, **kw)
+        bcz, fvz = plan
+        host = not (_is_tensor(a.data) or (kappa is not None and _is_tensor(kappa.data)))
+        out = _dev.vertical_diffusion(a.data, None if kappa is None else _aligned_view(kappa, f_dims),
+                                      None if mf is None else _aligned_view(mf, f_dims),
+                                      None if mc is None else _aligned_view(mc, a.dims), to == "outer", bcz, fvz)
+        # dims, coords and name as the chain's, step by step over placeholders: the gradient at the flux levels (named
+        # after its quotient with the metric), the product with kappa, the difference back at the centre, its quotient
+        g = _reattach_coords([DataArray(_placeholder(f_shape), f_dims, name=a.name)], self, None, {zf}, [a])[0]
+        if mf is not None:
+            g = g._replace(name=_name_after(g.name, mf))
+        f = g if kappa is None else DataArray(_placeholder(f_shape), f_dims, coords=_binary_coords(g, kappa, f_dims),
+                                              name=_result_name(g, kappa))
+        res = _reattach_coords([DataArray(_placeholder(a.shape), a.dims, name=f.name)], self, None, {tz}, [f])[0]
+        if mc is not None:
+            res = res._replace(name=_name_after(res.name, mc))
+        res = res._replace(data=_dev.tohost(out) if host else out)
+        return to_xarray(res) if was_xr else res
+
     # ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---------------------
     def _c_grid_vector(self, u, v, x_axis, y_axis, what):
         """dims of a C-grid vector's points: (lead, at u, at v, centre, vorticity point); raises when u / v sit elsewhere"""
