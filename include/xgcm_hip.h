@@ -47,6 +47,7 @@
  *   xg_horizontal_viscosity_f64  gradient(divergence * nu_d) -/+ diff(vorticity * nu_z): the harmonic viscosity, one pass
  *   xg_vertical_diffusion  derivative(derivative(a, Z) * kappa, Z): vertical diffusion / viscosity, one pass (float64 and
  *                      float32 through one entry: the element type is an argument)
+ *   xg_implicit_vertical_diffusion  (I - dt d/dz(kappa d/dz)) x = a: a tridiagonal solve along Z, one pass (one entry likewise)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -448,6 +449,24 @@ int xg_vertical_momentum_advection_f64(const double* u, const double* v, const d
 int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* kappa_strides, const void* mf,
                           const int64_t* mf_strides, const void* mc, const int64_t* mc_strides, void* out,
                           const int64_t* shape, int ndim, int outer, int bc_z, double fill_z, void* stream);
+/* Implicit (backward-Euler) vertical diffusion: solves (I - dt D) x = a column by column, D = d/dz(kappa d/dz) with no flux
+ * through the top and the bottom -- the inverse of a -> a - dt * xg_vertical_diffusion(a, .., outer = 1, XG_BC_EXTEND) -- in one
+ * pass: a tridiagonal (Thomas) solve along Z of `shape` (.., Z, Y, X), contiguous; `out` and the workspace `work` have the
+ * same shape and element type as `a` (out != a).  `dtype`: XG_T_F64 or XG_T_F32; any other code is XG_ERR_INVALID.  Levels
+ * k = 0 .. nz-1, faces k = 1 .. nz-1 (face k between level k-1 and level k), every operation in the element type, dt cast to
+ * it once, no fused multiply-add, in this order:
+ *   w[k]  = dt * (kappa[k] [/ mf[k]])       (kappa NULL: 1)       lo[k] = w[k] [/ mc[k]]       up[k-1] = w[k] [/ mc[k-1]]
+ *   b = 1 [+ lo[k], k > 0] [+ up[k], k < nz-1]
+ *   m = b [- lo[k] * c[k-1], k > 0]    r = 1 / m    c[k] = up[k] * r    d[k] = (a[k] [+ lo[k] * d[k-1], k > 0]) * r
+ *   x[nz-1] = d[nz-1]    x[k] = d[k] + c[k] * x[k+1], k = nz-2 .. 0
+ * No pivoting: for kappa >= 0, dt >= 0 and positive metrics the matrix is an M-matrix (m >= 1, 0 <= c < 1).
+ * kappa and mf (the metric of the flux) are indexed by face: their strides are broadcast strides (0 = broadcast) against
+ * `shape` with nz (outer = 0, Z:left) or nz + 1 (outer = 1, Z:outer) levels along Z; faces 0 and nz are never read.  mc (the
+ * metric of the result) against `shape` itself.  NULL kappa, mf or mc: absent.  `work` holds c on return (scratch).
+ * XG_ERR_INVALID: a NULL a, out, work or shape, a plane without strides, outer not 0 or 1, dt negative, NaN or infinite. */
+int xg_implicit_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* kappa_strides, const void* mf,
+                                   const int64_t* mf_strides, const void* mc, const int64_t* mc_strides, void* work, void* out,
+                                   const int64_t* shape, int ndim, int outer, double dt, void* stream);
 
 /* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
 /* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).

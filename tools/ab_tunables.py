@@ -103,6 +103,7 @@ def main():
         "pgrad": (lambda: D.hydrostatic_pressure_gradient(T, dz, dx, dx2, "periodic", "extend", "fill"), 24 + 16 / nz),  # pressure-gradient force: drF, dxC, dyC
         "vmadv": (lambda: D.vertical_momentum_advection(U, V, W, dz, dz, "periodic", "extend", "fill"), 40),  # w du/dz, w dv/dz: drF
         "vdiff": (lambda: D.vertical_diffusion(T, W, dz, dz, False, "extend"), 24),  # d/dz(kappa dT/dz), flux at Z:left: a 3-D kappa, drC, drF
+        "vimpl": (lambda: D.implicit_vertical_diffusion(T, W, dz, dz, False, 3600.0), 56),  # (I - dt d/dz(kappa d/dz)) x = T, flux at Z:left: a 3-D kappa, drC, drF; d and c out and back
         "keUV": (lambda: D.kinetic_energy(U, V, "periodic", "extend"), 24),  # 0.5 * (interp(u*u, X) + interp(v*v, Y))
         "madv": (lambda: D.momentum_advection(U, V, dx2, dx, dx2, dx, "periodic", "extend"), 32 + 16 / nz),  # vector-invariant advection + Coriolis: its four planes from two
         "hvisc": (lambda: D.horizontal_viscosity(U, V, dx, dx2, dx, dx2, dx2, dx, dx2, dx, "periodic", "extend"), 32 + 16 / nz),  # harmonic viscosity: its six metrics and two coefficients from two planes
@@ -157,7 +158,7 @@ def main():
             CASES[c] = ((lambda TR=TR: D.cumsum1d(TR, 1, 0, 1, 1, 0, "fill")), 16 * R)
     if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "keUV", "madv", "hvisc")):
         U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
-    W = D.synthetic((nz, ny, nx), 54) if ("adv3" in cases or "vmadv" in cases or "vdiff" in cases) else None
+    W = D.synthetic((nz, ny, nx), 54) if ("adv3" in cases or "vmadv" in cases or "vdiff" in cases or "vimpl" in cases) else None
     variants = []
     for spec in a.variants.split(";"):
         kv = dict((k.strip(), int(v)) for k, v in (item.split("=") for item in spec.split(",") if item.strip()))
@@ -187,7 +188,7 @@ def main():
                 T3 = D.synthetic((nz, ny, nx), 10, 0, 1000.0, 1000.0)
             if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "keUV", "madv", "hvisc")):
                 U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
-            if "adv3" in cases or "vmadv" in cases or "vdiff" in cases:
+            if "adv3" in cases or "vmadv" in cases or "vdiff" in cases or "vimpl" in cases:
                 W = D.synthetic((nz, ny, nx), 54)
             for c in cases:
                 CASES[c][0]()

@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion against their chains; 5pg, 5vm, 5hv, 5vd: the last four pairs, each alone), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv: the last five pairs, each alone), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -223,6 +223,42 @@ def run_vertical_diffusion(reps, nz=90, n=4320):
                       "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
                       "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_implicit_vertical_diffusion(reps, nz=90, n=4320):
+    """implicit_vertical_diffusion in one pass (a forward and a backward sweep in one launch) against the level loop of
+    xgcm_amd/grid.py (a dozen plane-sized operations per level and sweep) on resident tensors: 3-D kappa at Z:outer,
+    drC(Zp1), drF(Z), timed in turns, every paired round reported"""
+    from xgcm_amd.grid import _implicit_vertical_diffusion_levels as levels
+
+    coords = {"XC": ("XC", np.arange(n) + 0.5), "XG": ("XG", np.arange(n) * 1.0), "YC": ("YC", np.arange(n) + 0.5),
+              "YG": ("YG", np.arange(n) * 1.0), "Z": ("Z", np.arange(nz) + 0.5), "Zp1": ("Zp1", np.arange(nz + 1) * 1.0)}
+    drf, drc = D.synthetic((nz,), 33, 0, 10.0, 10.0), D.synthetic((nz + 1,), 34, 0, 10.0, 10.0)
+    ds = Dataset({"drF": DataArray(drf, ("Z",)), "drC": DataArray(drc, ("Zp1",))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                            "Z": {"center": "Z", "outer": "Zp1"}},
+                padding={"X": "periodic", "Y": "extend", "Z": "extend"}, metrics={("Z",): ["drF", "drC"]}, autoparse_metadata=False)
+    T = DataArray(D.synthetic((nz, n, n), 61), ("Z", "YC", "XC"))
+    K = DataArray(D.synthetic((nz + 1, n, n), 62, 0, 0.1, 0.0), ("Zp1", "YC", "XC"))   # 0 .. 0.1 m2/s over 10 .. 20 m layers
+    dt = 3600.0                                                                        # coupling dt kappa / (drC drF) <= 3.6
+    cells = nz * n * n
+
+    def loop():
+        return levels(T.data, K.data, drc[:, None, None], drf[:, None, None], 0, dt)
+
+    got, want = grid.implicit_vertical_diffusion(T, K, dt=dt), loop()
+    ok = bool(torch.equal(got.data.view(torch.int64), want.view(torch.int64)))
+    del got, want
+    torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(lambda: grid.implicit_vertical_diffusion(T, K, dt=dt), loop, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    bpc = 56   # a, kappa, d out and back, c out and back, x (the 91st level of kappa is not counted)
+    rec(5, "implicit_vertical_diffusion one pass (Thomas solve along Z), 3-D kappa, drC / drF: a, kappa, d and c out and back, x", med(tf), cells, bpc)
+    rec(5, "implicit_vertical_diffusion as the level loop over planes, one-pass-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": "one-pass implicit_vertical_diffusion == level loop bit for bit at full size", "ok": ok,
+                      "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
+                      "rounds_ms_loop": [round(t, 3) for t in tc],
+                      "fused_below_loop_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
 
 
 def rec(cfg, name, ms, cells, bpc):
@@ -864,6 +900,8 @@ def main():
         run_horizontal_viscosity(a.reps)
     if cfgs & {"5x", "5vd"}:
         run_vertical_diffusion(a.reps)
+    if cfgs & {"5x", "5iv"}:
+        run_implicit_vertical_diffusion(a.reps)
     ranks.close()
 
 

@@ -207,6 +207,8 @@ SIGNATURES["xg_convert"] = (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_uint64, C.
 # one entry for float64 and float32 (the element type, a DTYPE code, comes first): no _f64 / _f32 twins
 SIGNATURES["xg_vertical_diffusion"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int,
                                                C.c_int, C.c_double, _vp])
+SIGNATURES["xg_implicit_vertical_diffusion"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _i64p,
+                                                        C.c_int, C.c_int, C.c_double, _vp])
 
 SUFFIX = {"float64": "f64", "float32": "f32", "int64": "i64", "int32": "i32"}
 

@@ -755,6 +755,72 @@ int vdiff(const R* a, const R* const arr[3], const int64_t* const st[3], R* out,
   return XG_OK;
 }
 
+// the implicit vertical diffusion of the header, level by level over one (Z, Y, X) volume at a time: the Thomas algorithm with
+// every cell of a level advanced before the next level is touched.  c goes into `work`, d into `out`; the backward loop
+// turns d into x.  arr[] = {kappa, the metric of the flux, the metric of the result}; faces 0 and nz are never read.
+template <typename R>
+int vimpl(const R* a, const R* const arr[3], const int64_t* const st[3], R* work, R* out, const int64_t* shape, int ndim,
+          int outer, R dt) {
+  if (!a || !out || !work || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "outer %d is neither 0 (left) nor 1", outer);
+  for (int k = 0; k < 3; ++k)
+    if (arr[k] && !st[k]) return fail(XG_ERR_INVALID, "a plane without strides");
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx, vol = nz * plane;
+  int64_t lead = 1;
+  for (int d = 0; d < ndim - 3; ++d) lead *= shape[d];
+  if (lead == 0 || vol == 0) return XG_OK;
+  const R one = R(1);
+  for (int64_t o = 0; o < lead; ++o) {
+    int64_t rem = o, off[3] = {0, 0, 0};  // the lead index decomposed for the broadcast strides
+    for (int d = ndim - 4; d >= 0; --d) {
+      const int64_t i = rem % shape[d];
+      rem /= shape[d];
+      for (int k = 0; k < 3; ++k)
+        if (arr[k]) off[k] += i * st[k][d];
+    }
+    auto at = [&](int k, int64_t z, int64_t j, int64_t i) -> R {
+      return arr[k][off[k] + z * st[k][ndim - 3] + j * st[k][ndim - 2] + i * st[k][ndim - 1]];
+    };
+    // dt * kappa / mf at face z (1 .. nz-1)
+    auto weight = [&](int64_t z, int64_t j, int64_t i) -> R {
+      R g = arr[0] ? at(0, z, j, i) : one;
+      if (arr[1]) g = g / at(1, z, j, i);
+      return dt * g;
+    };
+    const R* pa = a + o * vol;
+    R* pc = work + o * vol;
+    R* pd = out + o * vol;
+    for (int64_t z = 0; z < nz; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t c = z * plane + j * nx + i;
+          R b = one, lo = 0, up = 0;
+          if (z > 0) {
+            lo = weight(z, j, i);
+            if (arr[2]) lo = lo / at(2, z, j, i);
+            b = b + lo;
+          }
+          if (z + 1 < nz) {
+            up = weight(z + 1, j, i);
+            if (arr[2]) up = up / at(2, z, j, i);
+            b = b + up;
+          }
+          R m = b, d = pa[c];
+          if (z > 0) {
+            m = m - lo * pc[c - plane];
+            d = d + lo * pd[c - plane];
+          }
+          const R r = one / m;
+          if (z + 1 < nz) pc[c] = up * r;
+          pd[c] = d * r;
+        }
+    for (int64_t z = nz - 2; z >= 0; --z)
+      for (int64_t c = z * plane; c < (z + 1) * plane; ++c) pd[c] = pd[c] + pc[c] * pd[c + plane];
+  }
+  return XG_OK;
+}
+
 // kinetic energy (ke_only) and the vector-invariant momentum advection of the header: the stages of the chain one after
 // the other over whole planes, each read through `get`, which pads a plane by one cell on one axis at a time (periodic:
 // the plane's own value at the wrapped index, extend: at the clamped index, fill: the fill value of that axis).
@@ -1279,6 +1345,22 @@ int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int
     return vdiff<float>((const float*)a, arr, st, (float*)out, shape, ndim, outer, bc_z, (float)fill_z);
   }
   return fail(XG_ERR_INVALID, "vertical diffusion: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+
+int xg_implicit_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* ks, const void* mf,
+                                   const int64_t* mfs, const void* mc, const int64_t* mcs, void* work, void* out,
+                                   const int64_t* shape, int ndim, int outer, double dt, void*) {
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(XG_ERR_INVALID, "implicit vertical diffusion: dt %g is negative or not finite", dt);
+  const int64_t* const st[3] = {ks, mfs, mcs};
+  if (dtype == XG_T_F64) {
+    const double* const arr[3] = {(const double*)kappa, (const double*)mf, (const double*)mc};
+    return vimpl<double>((const double*)a, arr, st, (double*)work, (double*)out, shape, ndim, outer, dt);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const arr[3] = {(const float*)kappa, (const float*)mf, (const float*)mc};
+    return vimpl<float>((const float*)a, arr, st, (float*)work, (float*)out, shape, ndim, outer, (float)dt);
+  }
+  return fail(XG_ERR_INVALID, "implicit vertical diffusion: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 
 int xg_convert(const void* src, int st, void* dst, int dt, uint64_t n, int via, double scale, int flags, void*) {

@@ -1906,6 +1906,176 @@ __global__ __launch_bounds__(BLOCK) void k_vdiff(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7m: implicit (backward-Euler) vertical diffusion, (I - dt D) x = a with D = d/dz(kappa d/dz) under the no-flux condition
+// at the top and at the bottom, over (lead, Z, Y, X) in ONE launch: the Thomas algorithm per column, a forward and a backward
+// sweep over the same column.  Faces k = 1 .. nz-1 (face k between level k-1 and level k), in the field's type, no FMA:
+//   w[k]  = dt * (kappa[k] [/ mf[k]])                  (kappa absent: 1)
+//   lo[k] = w[k] [/ mc[k]],  up[k-1] = w[k] [/ mc[k-1]]
+//   b     = 1 [+ lo[k], k > 0] [+ up[k], k < nz-1]
+//   m     = b [- lo[k] * c[k-1]],  r = 1 / m,  c[k] = up[k] * r,  d[k] = (a[k] [+ lo[k] * d[k-1]]) * r       forward
+//   x[nz-1] = d[nz-1],  x[k] = d[k] + c[k] * x[k+1]                                                          backward
+// kappa and mf are indexed by face (nz or nz + 1 of them: faces 0 and nz are never read), mc by level; no pivoting (for
+// kappa, dt >= 0 and positive metrics m >= 1 and 0 <= c < 1).  K7l's geometry: a wave owns one (lead, Y segment, X tile)
+// column set.  The forward sweep marches k = 0 .. nz-1 with c[k-1], d[k-1] and w[k] in registers, stores d[k] into `out` and
+// c[k] into the workspace `cw` (the field's shape); the backward sweep marches k = nz-2 .. 0, reads both back and overwrites
+// out[k] with x[k].  The coefficients lo, up, b do not depend on the recurrence: those of level k+1 (and the loads behind
+// them) are formed BEFORE level k's dependent chain (a reciprocal, two products, a sum), as K7l reads level k+1 at level k;
+// the backward sweep reads level k-1 before it forms level k.
+// NO barrier, LDS exchange or atomic: every lane reads back exactly the elements it stored itself -- same lane, same level,
+// same rows, same columns -- and no other lane or wave touches them.  A store followed by a load of the same address in one
+// thread is a dependence of plain program order: the compiler keeps the order of the two accesses, and the hardware performs
+// one wave's vector memory accesses to one address in the order they were issued (the vector L1 writes through).  For the
+// same reason the stores of c and d are always plain (they are read again by the same wave); only the final store of x
+// obeys `nt_store`.
+// float64 with a 3-D kappa: a 8 + kappa 8 + d out and back 16 + c out and back 16 + x 8 = 56 B/cell (48 with a profile
+// kappa(Z) or none); the read-backs may come from the L2 / the Infinity Cache.
+// ------------------------------------------------------------------------------------------
+template <int V, bool KAP, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_vimpl(
+    const real* __restrict__ a, real* __restrict__ cw, real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk, int64_t nz,
+    int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, real dt, VolIdx kp, VolIdx mf, VolIdx mc, int ntl) {
+  typedef typename VecT<V>::type T;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row, which this lane owns too)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = col + (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx + i0;
+  const T one = splat<T>(real(1)), tdt = splat<T>(dt);
+
+  // the rows of kappa and of the two metrics: loaded per face / level only when the array varies along Z, else once (and
+  // not at all for a column of one level, which has no face)
+  T kr[SEG], mfr[SEG], mcr[SEG];
+  int64_t kpo = 0, mfo = 0, mco = 0;
+  if (KAP) {
+    kpo = area_outer_off(kp.ai, o) + j0 * kp.sy + i0 * kp.sx;
+    if (kp.sz == 0 && nz > 1) load_rows<T, SEG>(kr, kp.p, kpo, kp.sy, kp.sx, nrow, (ntl & 4) != 0);
+  }
+  if (MET) {
+    if (mf.p) {
+      mfo = area_outer_off(mf.ai, o) + j0 * mf.sy + i0 * mf.sx;
+      if (mf.sz == 0 && nz > 1) load_rows<T, SEG>(mfr, mf.p, mfo, mf.sy, mf.sx, nrow, (ntl & 8) != 0);
+    }
+    if (mc.p) {
+      mco = area_outer_off(mc.ai, o) + j0 * mc.sy + i0 * mc.sx;
+      if (mc.sz == 0 && nz > 1) load_rows<T, SEG>(mcr, mc.p, mco, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
+    }
+  }
+  // w = w[k + 1] on return from coef(k) (k < nz-1), which needs w = w[k] on entry (k > 0): the coefficients of level k
+  T w[SEG];
+  auto coef = [&](int64_t k, T (&a_)[SEG], T (&lo_)[SEG], T (&up_)[SEG], T (&b_)[SEG]) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) a_[s_] = *reinterpret_cast<const T*>(a + ro[s_] + k * plane);
+    if (MET && nz > 1) {
+      if (mc.p && mc.sz != 0) load_rows<T, SEG>(mcr, mc.p, mco + k * mc.sz, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) b_[s_] = one;
+    if (k > 0) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        T l = w[s_];
+        if (MET) {
+          if (mc.p) l = l / mcr[s_];
+        }
+        lo_[s_] = l;
+        b_[s_] = b_[s_] + l;
+      }
+    }
+    if (k + 1 < nz) {
+      // face k + 1
+      if (KAP && kp.sz != 0) load_rows<T, SEG>(kr, kp.p, kpo + (k + 1) * kp.sz, kp.sy, kp.sx, nrow, (ntl & 4) != 0);
+      if (MET) {
+        if (mf.p && mf.sz != 0) load_rows<T, SEG>(mfr, mf.p, mfo + (k + 1) * mf.sz, mf.sy, mf.sx, nrow, (ntl & 8) != 0);
+      }
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        T g = KAP ? kr[s_] : one;
+        if (MET) {
+          if (mf.p) g = g / mfr[s_];
+        }
+        w[s_] = tdt * g;
+        T u = w[s_];
+        if (MET) {
+          if (mc.p) u = u / mcr[s_];
+        }
+        up_[s_] = u;
+        b_[s_] = b_[s_] + u;
+      }
+    }
+  };
+
+  // ---- forward: d into out, c into cw; the last level's d is x itself ----
+  T ac[SEG], lo[SEG], up[SEG], b[SEG], cp[SEG], dp[SEG];
+  coef(0, ac, lo, up, b);
+  for (int64_t k = 0; k < nz; ++k) {
+    const bool more = k + 1 < nz;
+    T an[SEG], lon[SEG], upn[SEG], bn[SEG];
+    if (more) coef(k + 1, an, lon, upn, bn);
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      T m = b[s_], d = ac[s_];
+      if (k > 0) {
+        m = m - lo[s_] * cp[s_];
+        d = d + lo[s_] * dp[s_];
+      }
+      const T r = one / m;
+      d = d * r;
+      dp[s_] = d;
+      if (more) {
+        cp[s_] = up[s_] * r;
+        if (s_ < nrow) {
+          stg<T, false>(out + ro[s_] + k * plane, d);
+          stg<T, false>(cw + ro[s_] + k * plane, cp[s_]);
+        }
+      } else if (s_ < nrow) {
+        stg_s<T, NTS>(out + ro[s_] + k * plane, d);
+      }
+    }
+    if (more) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        ac[s_] = an[s_];
+        lo[s_] = lon[s_];
+        up[s_] = upn[s_];
+        b[s_] = bn[s_];
+      }
+    }
+  }
+  if (nz < 2) return;
+
+  // ---- backward: x[k] = d[k] + c[k] * x[k+1], what this lane stored read back one level ahead of its use ----
+  T dk[SEG], ck[SEG];
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    dk[s_] = *reinterpret_cast<const T*>(out + ro[s_] + (nz - 2) * plane);
+    ck[s_] = *reinterpret_cast<const T*>(cw + ro[s_] + (nz - 2) * plane);
+  }
+  for (int64_t k = nz - 2; k >= 0; --k) {
+    T dn[SEG], cn[SEG];
+    if (k > 0) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        dn[s_] = *reinterpret_cast<const T*>(out + ro[s_] + (k - 1) * plane);
+        cn[s_] = *reinterpret_cast<const T*>(cw + ro[s_] + (k - 1) * plane);
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      dp[s_] = dk[s_] + ck[s_] * dp[s_];
+      if (s_ < nrow) stg_s<T, NTS>(out + ro[s_] + k * plane, dp[s_]);
+    }
+    if (k > 0) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        dk[s_] = dn[s_];
+        ck[s_] = cn[s_];
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -2679,6 +2849,72 @@ int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int
     return xg_internal_vdiff_f32((const float*)a, (const float*)kappa, kappa_strides, (const float*)mf, mf_strides,
                                  (const float*)mc, mc_strides, (float*)out, shape, ndim, outer, bc_z, (float)fill_z, stream);
   return fail(XG_ERR_INVALID, "vertical diffusion: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+
+// K7m's launcher: K7l's arguments without a boundary (the solve is the no-flux one) and with a workspace of the field's shape
+// for the forward sweep's c.  `outer` only says how many faces kappa and mf have (nz or nz + 1): faces 1 .. nz-1 are read
+// either way, at the same strides.  One ABI entry for both element types (xg_implicit_vertical_diffusion, below).
+__attribute__((visibility("hidden"))) int xg_internal_vimpl_f64(
+    const double* a, const double* kappa, const int64_t* kappa_strides, const double* mf, const int64_t* mf_strides,
+    const double* mc, const int64_t* mc_strides, double* work, double* out, const int64_t* shape, int ndim, int outer,
+    double dt, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_vimpl_f32(
+    const float* a, const float* kappa, const int64_t* kappa_strides, const float* mf, const int64_t* mf_strides,
+    const float* mc, const int64_t* mc_strides, float* work, float* out, const int64_t* shape, int ndim, int outer,
+    float dt, void* stream);
+
+int XG_FN(xg_internal_vimpl)(const real* a, const real* kappa, const int64_t* kappa_strides, const real* mf,
+                             const int64_t* mf_strides, const real* mc, const int64_t* mc_strides, real* work, real* out,
+                             const int64_t* shape, int ndim, int outer, real dt, void* stream) {
+  const char* name = "implicit vertical diffusion";
+  if (!a || !out || !work || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  const real* mp[3] = {kappa, mf, mc};  // kappa, the metric of the flux, the metric of the result
+  const int64_t* ms[3] = {kappa_strides, mf_strides, mc_strides};
+  for (int k = 0; k < 3; ++k)
+    if (mp[k] && !ms[k]) return fail(XG_ERR_INVALID, "%s: a plane without strides", name);
+  FusedPlan p;
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, aligned16(a) && aligned16(out) && aligned16(work), true, stream)) || p.empty)
+    return rc;
+  VolIdx mi[3];
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  // bits 2 / 3 / 4: the rows of kappa / the flux metric / the result's metric are aligned vectors (no X neighbour: no bit 0)
+  int vnt = 0;
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool kap = kappa != nullptr, met = mf != nullptr || mc != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, K_, M_, NTS) do { hipLaunchKernelGGL((k_vimpl<V_, K_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, a, work, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, dt, mi[0], mi[1], mi[2], vnt); } while (0)
+#define XG_N(V_, K_, M_) do { if (p.nts) XG_GO(V_, K_, M_, true); else XG_GO(V_, K_, M_, false); } while (0)
+#define XG_M(V_, K_) do { if (met) XG_N(V_, K_, true); else XG_N(V_, K_, false); } while (0)
+#define XG_V(V_) do { if (kap) XG_M(V_, true); else XG_M(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_M
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument, dt is cast to it here, once
+int xg_implicit_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* kappa_strides, const void* mf,
+                                   const int64_t* mf_strides, const void* mc, const int64_t* mc_strides, void* work, void* out,
+                                   const int64_t* shape, int ndim, int outer, double dt, void* stream) {
+  if (!(dt >= 0.0) || !__builtin_isfinite(dt))
+    return fail(XG_ERR_INVALID, "implicit vertical diffusion: dt %g is negative or not finite", dt);
+  if (dtype == XG_T_F64)
+    return xg_internal_vimpl_f64((const double*)a, (const double*)kappa, kappa_strides, (const double*)mf, mf_strides,
+                                 (const double*)mc, mc_strides, (double*)work, (double*)out, shape, ndim, outer, dt, stream);
+  if (dtype == XG_T_F32)
+    return xg_internal_vimpl_f32((const float*)a, (const float*)kappa, kappa_strides, (const float*)mf, mf_strides,
+                                 (const float*)mc, mc_strides, (float*)work, (float*)out, shape, ndim, outer, (float)dt, stream);
+  return fail(XG_ERR_INVALID, "implicit vertical diffusion: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 #endif
 

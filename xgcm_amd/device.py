@@ -1347,6 +1347,33 @@ def vertical_diffusion(a, kappa, mf, mc, outer: bool, bc_z: str, fill_z: float =
     return out
 
 
+def implicit_vertical_diffusion(a, kappa, mf, mc, outer: bool, dt: float) -> torch.Tensor:
+    """Implicit vertical diffusion in one pass (xg_implicit_vertical_diffusion): solves (I - dt D) x = a column by column,
+    D = d/dz(kappa d/dz) with no flux through the top and the bottom -- the Thomas algorithm, a forward and a backward sweep
+    in one launch.  `kappa` and `mf` (None = absent) broadcast against the flux' shape, which has `a`'s levels (`outer`
+    False, Z:left) or one more (True, Z:outer); `mc` against `a`'s.  The workspace of the forward sweep is allocated here,
+    per call: the library keeps no state between calls."""
+    lib = _MEM.lib()
+    dt_, sfx = _common(a, kappa, mf, mc)
+    a = asdevice(a, dt_)
+    if a.dim() < 3:
+        raise ValueError("implicit_vertical_diffusion: the field needs (Z, Y, X) as its last three dims")
+    shape = list(a.shape)
+    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
+    kappa, mf, mc = (_prep_metric(m, dt_) for m in (kappa, mf, mc))
+    out = _empty(shape, dtype=dt_, device=a.device)
+    if out.numel() == 0:
+        return out
+    work = _empty(shape, dtype=dt_, device=a.device)
+    margs = []
+    for m, against, what in ((kappa, fshape, "kappa"), (mf, fshape, "metric of the flux"), (mc, shape, "metric of the result")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
+    _check(lib.xg_implicit_vertical_diffusion(_hip.DTYPE["float32" if sfx == "f32" else "float64"], a.data_ptr(), *margs,
+                                              work.data_ptr(), out.data_ptr(), _hip.i64(shape), len(shape), int(bool(outer)),
+                                              float(dt), _stream()))
+    return out
+
+
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""

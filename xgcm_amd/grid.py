@@ -1855,6 +1855,108 @@ class Grid:
         res = res._replace(data=_dev.tohost(out) if host else out)
         return to_xarray(res) if was_xr else res
 
+    def implicit_vertical_diffusion(self, a, kappa=None, dt=None, z_axis: str = "Z", to=None, metric_weighted: bool = True):
+        """Implicit (backward-Euler) vertical mixing: solves (I - dt D) x = a column by column, where D a is
+        d/dz(kappa da/dz) with no flux through the top and the bottom -- a tridiagonal (Thomas) solve along Z in ONE pass,
+        a forward and a backward sweep in one launch.  With `kappa` at Z:outer it is the inverse of
+
+            a -> a - dt * grid.vertical_diffusion(a, kappa, to="outer", padding="extend")
+
+        up to rounding; with `kappa` at Z:left (one face fewer: there is none below the last level) it is the same solve,
+        only the extent of `kappa` and of the flux' metric differs.  The top and the bottom are insulated, so there is no
+        `padding` and no `fill_value`: the face values of `kappa` and of the metric there are never read, and a surface
+        flux is added to `a` by the caller.
+
+        `a` at Z:center.  `kappa` at the flux position on Z (`to`: "left" or "outer"; None: "outer" when the Z axis has
+        one, else "left"), with dims among those of the flux -- a profile kappa(Z), a (Z, Y, X) field, a field with leading
+        dims, in any order: it is read through broadcast strides, never materialised; None: 1.  The metrics are whatever
+        `get_metric` returns at the flux' and at `a`'s dims (drC / drF, or registered 3-D thicknesses);
+        `metric_weighted=False` drops both divisions.  Per column, levels k = 0 .. n-1, faces k = 1 .. n-1, every operation
+        in `a`'s dtype, `dt` cast to it once, no fused multiply-add:
+
+            w[k] = dt * (kappa[k] / mf[k]);  lo[k] = w[k] / mc[k];  up[k-1] = w[k] / mc[k-1]
+            b = 1 (+ lo[k], k > 0) (+ up[k], k < n-1)
+            m = b - lo[k] * c[k-1];  r = 1 / m;  c[k] = up[k] * r;  d[k] = (a[k] + lo[k] * d[k-1]) * r
+            x[n-1] = d[n-1];  x[k] = d[k] + c[k] * x[k+1]
+
+        No pivoting: for kappa >= 0, dt >= 0 and positive metrics the matrix is an M-matrix and max|x| <= max|a| per
+        column.  The result carries `a`'s dims, coords and name; xarray in gives xarray out, host in host out, HBM in HBM
+        out.
+
+        The kernel serves `a` with Z third from last (the two dims after it are only rows and columns: the centre, u's
+        or v's points).  A level loop over whole planes with the array's own arithmetic, the same recurrence in the same
+        order and so bit-identical where both apply, serves the rest: fewer than three dims, Z elsewhere, a `kappa` or a
+        metric with a dim `a` lacks (the result then has that dim in front).
+
+        Raises ValueError for `dt` negative, NaN or infinite, for an `a` not at Z:center, a `to` that is not "left" or
+        "outer" or that the axis lacks, a `kappa` that is not at the flux position or does not fit; TypeError for integer,
+        bool or float16 fields and for mixed dtypes (a solve has no exact integer form; nothing is promoted silently);
+        NotImplementedError for chunked inputs and for face connections or a fold along Z; the metric lookup's own error
+        when `metric_weighted` and the axis has no metric."""
+        what = "implicit_vertical_diffusion"
+        (a, xr1), (kappa, xr2) = self._wrap_in(a), self._wrap_in(kappa)
+        was_xr = xr1 or xr2
+        if dt is None:
+            raise TypeError(f"{what}: dt, the time step, is required")
+        dt = float(dt)
+        if not (dt >= 0.0 and np.isfinite(dt)):
+            raise ValueError(f"{what}: dt must be finite and not negative, got {dt}")
+        if not isinstance(a, DataArray) or not (kappa is None or isinstance(kappa, DataArray)):
+            raise TypeError(f"{what}: `a` and `kappa` must be labelled arrays (`kappa` may be None)")
+        zax = self.axes[z_axis]
+        if to is None:
+            to = "outer" if "outer" in zax.coords else "left"
+        if to not in ("left", "outer") or to not in zax.coords or "center" not in zax.coords:
+            raise ValueError(f"{what}: the flux position must be 'left' or 'outer' and exist on axis {z_axis!r}, got {to!r}")
+        if gridops.complex_topology(self, z_axis):
+            raise NotImplementedError(f"{what}: face connections or a fold along {z_axis!r} make the columns a coupled system")
+        tz, zf = zax.coords["center"], zax.coords[to]
+        if tz not in a.dims or sum(d in a.dims for d in zax.coords.values()) != 1:
+            raise ValueError(f"{what}: `a` must sit at {z_axis}:center (dim {tz!r}), its dims are {a.dims}")
+        if _is_chunked(a.data) or (kappa is not None and _is_chunked(kappa.data)):
+            raise NotImplementedError(f"{what}: chunked inputs are not served; compute the array first")
+        dtype = _dt.np_dtype(a.data)
+        if dtype not in (_dt.FLOAT32, _dt.FLOAT64):
+            raise TypeError(f"{what}: a {dtype} field has no exact solve; convert it to float32 or float64 first")
+        z = a.dims.index(tz)
+        nf = a.shape[z] + (1 if to == "outer" else 0)
+        f_dims = tuple(zf if d == tz else d for d in a.dims)
+        if kappa is not None:
+            if _dt.np_dtype(kappa.data) != dtype:
+                raise TypeError(f"{what}: mixed dtypes, `a` is {dtype} and `kappa` {_dt.np_dtype(kappa.data)}; nothing is promoted")
+            if any(d in kappa.dims for d in zax.coords.values() if d != zf):
+                raise ValueError(f"{what}: `kappa` must sit at the flux position {z_axis}:{to} (dim {zf!r}), its dims are {kappa.dims}")
+            for d in kappa.dims:
+                n = nf if d == zf else (a.sizes[d] if d in a.dims else None)
+                if n is not None and kappa.sizes[d] != n:
+                    raise ValueError(f"{what}: `kappa` has {kappa.sizes[d]} entries along {d!r}, the flux has {n}")
+        mf = mc = None
+        if metric_weighted:
+            mf = self._resident(self.get_metric(_DimsOnly(f_dims, a.name), (z_axis,), _layout=f_dims), a.data)
+            mc = self._resident(self.get_metric(_DimsOnly(a.dims, a.name), (z_axis,), _layout=a.dims), a.data)
+            for m in (mf, mc):
+                if _is_chunked(m.data):
+                    raise NotImplementedError(f"{what}: chunked metrics are not served; compute them first")
+                if _dt.np_dtype(m.data) != dtype:
+                    raise TypeError(f"{what}: mixed dtypes, `a` is {dtype} and the metric {m.name!r} {_dt.np_dtype(m.data)}; "
+                                    "nothing is promoted")
+        host = not (_is_tensor(a.data) or (kappa is not None and _is_tensor(kappa.data)))
+        planes = ((kappa, f_dims), (mf, f_dims), (mc, a.dims))
+        extra = tuple(dict.fromkeys(d for m, dims in planes if m is not None for d in m.dims if d not in dims))
+        if a.ndim >= 3 and z == a.ndim - 3 and not extra:
+            out = _dev.implicit_vertical_diffusion(a.data, *(None if m is None else _aligned_view(m, dims) for m, dims in planes),
+                                                   to == "outer", dt)
+            res = a._replace(data=_dev.tohost(out) if host else out)
+        else:
+            # the level loop: every operand with the dims (extra.., a's..), Z named alike in all of them
+            dims = extra + a.dims
+            arrays = [None if m is None else _aligned_view(m, extra + d) for m, d in ((a, a.dims),) + planes]
+            if not host:
+                arrays = [None if m is None else _dev.asdevice(m) for m in arrays]
+            out = _implicit_vertical_diffusion_levels(*arrays, len(extra) + z, dt)
+            res = DataArray(out, dims, coords={k: v for k, v in a.coords.items()}, name=a.name, attrs=a.attrs)
+        return to_xarray(res) if was_xr else res
+
     # ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---------------------
     def _c_grid_vector(self, u, v, x_axis, y_axis, what):
         """dims of a C-grid vector's points: (lead, at u, at v, centre, vorticity point); raises when u / v sit elsewhere"""
@@ -2108,6 +2210,53 @@ class Grid:
 
 
 # ----------------------------------------------------------------------------------------------
+def _implicit_vertical_diffusion_levels(a, kappa, mf, mc, z: int, dt: float):
+    """`Grid.implicit_vertical_diffusion` as a loop over levels: every operation on whole planes, in the arrays' own
+    arithmetic (numpy arrays or tensors, all of one dtype), in the order of the docstring there -- so bit for bit what the
+    one-pass kernel computes.  The operands have the same number of dims and broadcast against each other, Z is dim `z` in
+    all of them; `kappa` and `mf` are indexed by face (an extent of 1 along Z: the same plane at every face), `mc` by level.
+    Some twelve plane-sized operations per level in the forward loop and two in the backward one."""
+    present = [m for m in (a, kappa, mf, mc) if m is not None]
+    n = a.shape[z]
+    shape = list(np.broadcast_shapes(*[tuple(m.shape[:z]) + (1,) + tuple(m.shape[z + 1:]) for m in present]))
+    shape[z] = n
+    if _is_tensor(a):
+        out, c = (a.new_empty(shape) for _ in range(2))
+        one, tdt = a.new_tensor(1.0), a.new_tensor(dt)   # dt is cast to the dtype once
+    else:
+        out, c = (np.empty(shape, a.dtype) for _ in range(2))
+        one, tdt = a.dtype.type(1.0), a.dtype.type(dt)
+    ix = lambda m, k: (slice(None),) * z + (k if m.shape[z] > 1 else 0,)  # noqa: E731
+    at = lambda m, k: m[ix(m, k)]  # noqa: E731
+
+    def weight(k):   # dt * kappa / mf at face k
+        g = one if kappa is None else at(kappa, k)
+        if mf is not None:
+            g = g / at(mf, k)
+        return tdt * g
+
+    w = cp = dp = None
+    for k in range(n):
+        b = one
+        if k > 0:
+            lo = w if mc is None else w / at(mc, k)
+            b = b + lo
+        if k < n - 1:
+            w = weight(k + 1)
+            up = w if mc is None else w / at(mc, k)
+            b = b + up
+        m = b if k == 0 else b - lo * cp
+        r = one / m
+        if k < n - 1:
+            cp = up * r
+            c[ix(c, k)] = cp
+        dp = (at(a, k) if k == 0 else at(a, k) + lo * dp) * r
+        out[ix(out, k)] = dp
+    for k in range(n - 2, -1, -1):
+        out[ix(out, k)] = at(out, k) + at(c, k) * at(out, k + 1)
+    return out
+
+
 def _placeholder(shape):
     """read-only stand-in of an intermediate the fused operators never form: carries a shape (for its coords), no memory"""
     return np.broadcast_to(np.zeros((), dtype=np.int8), tuple(int(n) for n in shape))
