@@ -48,6 +48,8 @@
  *   xg_vertical_diffusion  derivative(derivative(a, Z) * kappa, Z): vertical diffusion / viscosity, one pass (float64 and
  *                      float32 through one entry: the element type is an argument)
  *   xg_implicit_vertical_diffusion  (I - dt d/dz(kappa d/dz)) x = a: a tridiagonal solve along Z, one pass (one entry likewise)
+ *   xg_richardson_number  derivative(b, Z) / (interp(derivative(u, Z), X)^2 + interp(derivative(v, Z), Y)^2) at the faces of Z,
+ *                      or the squared shear alone, one pass (one entry likewise)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -467,6 +469,26 @@ int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int
 int xg_implicit_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* kappa_strides, const void* mf,
                                    const int64_t* mf_strides, const void* mc, const int64_t* mc_strides, void* work, void* out,
                                    const int64_t* shape, int ndim, int outer, double dt, void* stream);
+/* The squared vertical shear S2 and the gradient Richardson number Ri = N2 / S2 of a C-grid velocity at the faces of Z, one
+ * pass.  Arrays of identical `shape` (.., Z, Y, X): b at (Z:center, Y:center, X:center), u at (Z:center, Y:center, X:left),
+ * v at (Z:center, Y:left, X:center); `out`, at (Z face, Y:center, X:center), has nz (outer = 0, Z:left) or nz + 1 (outer = 1,
+ * Z:outer) levels.  `dtype`: XG_T_F64 or XG_T_F32; any other code is XG_ERR_INVALID.  b NULL: `out` is S2, and mb is not
+ * looked at.  It replaces the chain of nine launches
+ *   du = u[k] - u[k-1]  [/ mu]      dv = v[k] - v[k-1]  [/ mv]      db = b[k] - b[k-1]  [/ mb]         xg_stencil1d diff along Z
+ *   uz = (du[j,i] + du[j,i+1]) * 0.5                 vz = (dv[j,i] + dv[j+1,i]) * 0.5                  interp, left -> center
+ *   S2 = uz * uz + vz * vz                           Ri = db / S2                                      xg_binary
+ * in this order of operations, no fused multiply-add, IEEE quotients, no guard on S2 == 0 (inf, or NaN for 0 / 0).
+ * u, v and b are padded above level 0 and, outer = 1, below level nz-1 (periodic: the far level, extend: the level itself,
+ * fill: fill_z); then du right of the last column and dv above the last row (periodic: the difference at index 0, extend: at
+ * n-1, fill: fill_x / fill_y itself, not a difference formed from it).
+ * mu, mv, mb (the Z metric at u's points, at v's points, at the centre) live at the faces: their strides are broadcast
+ * strides (0 = broadcast) against `shape` with nz (outer = 0) or nz + 1 (outer = 1) levels along Z.  NULL: absent.
+ * The fills are cast to the element type (-0.0 and NaN keep their bits).  XG_ERR_INVALID: a NULL u, v, out or shape, a
+ * metric without strides, outer not 0 or 1, an unknown boundary code, nz = 0. */
+int xg_richardson_number(int dtype, const void* b, const void* u, const void* v, const void* mu, const int64_t* mu_strides,
+                         const void* mv, const int64_t* mv_strides, const void* mb, const int64_t* mb_strides, void* out,
+                         const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
+                         double fill_z, void* stream);
 
 /* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
 /* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).

@@ -104,6 +104,7 @@ def main():
         "vmadv": (lambda: D.vertical_momentum_advection(U, V, W, dz, dz, "periodic", "extend", "fill"), 40),  # w du/dz, w dv/dz: drF
         "vdiff": (lambda: D.vertical_diffusion(T, W, dz, dz, False, "extend"), 24),  # d/dz(kappa dT/dz), flux at Z:left: a 3-D kappa, drC, drF
         "vimpl": (lambda: D.implicit_vertical_diffusion(T, W, dz, dz, False, 3600.0), 56),  # (I - dt d/dz(kappa d/dz)) x = T, flux at Z:left: a 3-D kappa, drC, drF; d and c out and back
+        "rich": (lambda: D.richardson_number(T, U, V, dz, dz, dz, False, "periodic", "extend", "fill"), 32),  # Ri = N2 / S2 at Z:left: drC at u's, v's points and the centre
         "keUV": (lambda: D.kinetic_energy(U, V, "periodic", "extend"), 24),  # 0.5 * (interp(u*u, X) + interp(v*v, Y))
         "madv": (lambda: D.momentum_advection(U, V, dx2, dx, dx2, dx, "periodic", "extend"), 32 + 16 / nz),  # vector-invariant advection + Coriolis: its four planes from two
         "hvisc": (lambda: D.horizontal_viscosity(U, V, dx, dx2, dx, dx2, dx2, dx, dx2, dx, "periodic", "extend"), 32 + 16 / nz),  # harmonic viscosity: its six metrics and two coefficients from two planes
@@ -156,7 +157,7 @@ def main():
             R = int(c[5:])
             TR = D.synthetic((R, nz, ny, nx), 4)
             CASES[c] = ((lambda TR=TR: D.cumsum1d(TR, 1, 0, 1, 1, 0, "fill")), 16 * R)
-    if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "keUV", "madv", "hvisc")):
+    if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "rich", "keUV", "madv", "hvisc")):
         U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
     W = D.synthetic((nz, ny, nx), 54) if ("adv3" in cases or "vmadv" in cases or "vdiff" in cases or "vimpl" in cases) else None
     variants = []
@@ -186,7 +187,7 @@ def main():
                 T2 = D.synthetic((nz, ny, nx), 9, 0, 1000.0, 1000.0)
             if T3k:
                 T3 = D.synthetic((nz, ny, nx), 10, 0, 1000.0, 1000.0)
-            if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "keUV", "madv", "hvisc")):
+            if any(c in cases for c in ("vort", "divg", "flux", "advT", "adv3", "wcont", "vmadv", "rich", "keUV", "madv", "hvisc")):
                 U, V = D.synthetic((nz, ny, nx), 51), D.synthetic((nz, ny, nx), 52)
             if "adv3" in cases or "vmadv" in cases or "vdiff" in cases or "vimpl" in cases:
                 W = D.synthetic((nz, ny, nx), 54)

@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv: the last five pairs, each alone), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -259,6 +259,41 @@ def run_implicit_vertical_diffusion(reps, nz=90, n=4320):
                       "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
                       "rounds_ms_loop": [round(t, 3) for t in tc],
                       "fused_below_loop_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_richardson_number(reps, nz=90, n=4320):
+    """richardson_number in one pass against its chain of nine launches (three derivatives to Z:outer, two interps to the
+    centre, two squares, their sum, the quotient; a profile drC(Zp1); periodic / extend / extend: no shear through the top
+    and the bottom, where Ri is 0 / 0), timed in turns, every paired round reported"""
+    coords = {"XC": ("XC", np.arange(n) + 0.5), "XG": ("XG", np.arange(n) * 1.0), "YC": ("YC", np.arange(n) + 0.5),
+              "YG": ("YG", np.arange(n) * 1.0), "Z": ("Z", np.arange(nz) + 0.5), "Zp1": ("Zp1", np.arange(nz + 1) * 1.0)}
+    ds = Dataset({"drC": DataArray(D.synthetic((nz + 1,), 34, 0, 10.0, 10.0), ("Zp1",))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                            "Z": {"center": "Z", "outer": "Zp1"}},
+                padding={"X": "periodic", "Y": "extend", "Z": "extend"}, metrics={("Z",): ["drC"]}, autoparse_metadata=False)
+    B = DataArray(D.synthetic((nz, n, n), 63), ("Z", "YC", "XC"))
+    U = DataArray(D.synthetic((nz, n, n), 51), ("Z", "YC", "XG"))
+    V = DataArray(D.synthetic((nz, n, n), 52), ("Z", "YG", "XC"))
+    cells = nz * n * n
+
+    def chain():
+        uz = grid.interp(grid.derivative(U, "Z", to="outer"), "X")
+        vz = grid.interp(grid.derivative(V, "Z", to="outer"), "Y")
+        return grid.derivative(B, "Z", to="outer") / (uz * uz + vz * vz)
+
+    got, want = grid.richardson_number(B, U, V), chain()
+    ok = bool(torch.equal(got.data.view(torch.int64), want.data.view(torch.int64)))   # (the bits: Ri is NaN at faces 0 and nz)
+    del got, want
+    torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(lambda: grid.richardson_number(B, U, V), chain, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    bpc = 32   # b, u, v and Ri (the 91st face of Ri is not counted)
+    rec(5, "richardson_number fused derivative(b, Z) / (interp(derivative(u, Z), X)^2 + interp(derivative(v, Z), Y)^2), to=outer, drC(Zp1), extend: 3 reads + 1 write", med(tf), cells, bpc)
+    rec(5, "richardson_number as its chain (9 launches), fused-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": "fused richardson_number == chain bit for bit at full size", "ok": ok,
+                      "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
+                      "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
 
 
 def rec(cfg, name, ms, cells, bpc):
@@ -902,6 +937,8 @@ def main():
         run_vertical_diffusion(a.reps)
     if cfgs & {"5x", "5iv"}:
         run_implicit_vertical_diffusion(a.reps)
+    if cfgs & {"5x", "5ri"}:
+        run_richardson_number(a.reps)
     ranks.close()
 
 

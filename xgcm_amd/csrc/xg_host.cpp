@@ -821,6 +821,84 @@ int vimpl(const R* a, const R* const arr[3], const int64_t* const st[3], R* work
   return XG_OK;
 }
 
+// the squared shear / the Richardson number of the header as the stages of its chain over one (Z, Y, X) volume at a time,
+// each into a temporary: the three differences along Z at the faces (nz of them, `outer`: nz + 1) over their metrics, the
+// two means to the centre with the pad of the DIFFERENCES right of the last column / above the last row, the squares,
+// their sum, the quotient.  arr[] = {the metric at u's points, at v's points, at the centre}; b NULL: the squared shear
+template <typename R>
+int richardson(const R* b, const R* u, const R* v, const R* const arr_in[3], const int64_t* const st[3], R* out,
+               const int64_t* shape, int ndim, int outer, const int bc[3], const R fill[3]) {  // bc, fill: X, Y, Z
+  if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  for (int k = 0; k < 3; ++k)
+    if (bc[k] < XG_BC_PERIODIC || bc[k] > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", bc[k]);
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "outer %d is neither 0 (left) nor 1", outer);
+  const R* arr[3] = {arr_in[0], arr_in[1], b ? arr_in[2] : nullptr};
+  for (int k = 0; k < 3; ++k)
+    if (arr[k] && !st[k]) return fail(XG_ERR_INVALID, "metric without strides");
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx, vol = nz * plane;
+  if (nz == 0) return fail(XG_ERR_INVALID, "richardson number: no level along Z");
+  const int64_t nf = nz + outer;  // faces
+  int64_t lead = 1;
+  for (int d = 0; d < ndim - 3; ++d) lead *= shape[d];
+  if (lead == 0 || vol == 0) return XG_OK;
+  std::vector<R> d[3];  // the differences of u, v, b at the faces
+  for (int k = 0; k < (b ? 3 : 2); ++k) d[k].resize((size_t)(nf * plane));
+  std::vector<R> uz((size_t)(nf * plane)), vz((size_t)(nf * plane));
+  for (int64_t o = 0; o < lead; ++o) {
+    int64_t rem = o, off[3] = {0, 0, 0};  // the lead index decomposed for the broadcast strides
+    for (int dd = ndim - 4; dd >= 0; --dd) {
+      const int64_t i = rem % shape[dd];
+      rem /= shape[dd];
+      for (int k = 0; k < 3; ++k)
+        if (arr[k]) off[k] += i * st[k][dd];
+    }
+    const R* src[3] = {u + o * vol, v + o * vol, b ? b + o * vol : nullptr};
+    // (1) the differences along Z: level z of a padded field is a level of it, or its pad above level 0 / below level nz-1
+    for (int k = 0; k < 3; ++k) {
+      if (!src[k]) continue;
+      const R* p = src[k];
+      auto level = [&](int64_t z, int64_t c) -> R {
+        if (z >= 0 && z < nz) return p[z * plane + c];
+        if (bc[2] == XG_BC_FILL) return fill[2];
+        if (bc[2] == XG_BC_PERIODIC) return p[(z < 0 ? nz - 1 : 0) * plane + c];
+        return p[(z < 0 ? 0 : nz - 1) * plane + c];
+      };
+      for (int64_t z = 0; z < nf; ++z)
+        for (int64_t j = 0; j < ny; ++j)
+          for (int64_t i = 0; i < nx; ++i) {
+            const int64_t c = j * nx + i;
+            R x = level(z, c) - level(z - 1, c);
+            if (arr[k]) x = x / arr[k][off[k] + z * st[k][ndim - 3] + j * st[k][ndim - 2] + i * st[k][ndim - 1]];
+            d[k][z * plane + c] = x;
+          }
+    }
+    // (2) the means at the centre: du with its right neighbour, dv with the one above
+    for (int64_t z = 0; z < nf; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t c = z * plane + j * nx + i;
+          R right, above;
+          if (i + 1 < nx) right = d[0][c + 1];
+          else if (bc[0] == XG_BC_FILL) right = fill[0];
+          else right = d[0][z * plane + j * nx + (bc[0] == XG_BC_PERIODIC ? 0 : nx - 1)];
+          if (j + 1 < ny) above = d[1][c + nx];
+          else if (bc[1] == XG_BC_FILL) above = fill[1];
+          else above = d[1][z * plane + (bc[1] == XG_BC_PERIODIC ? 0 : ny - 1) * nx + i];
+          uz[c] = (d[0][c] + right) * R(0.5);
+          vz[c] = (d[1][c] + above) * R(0.5);
+        }
+    // (3) the squares, their sum, the quotient
+    R* po = out + o * nf * plane;
+    for (int64_t c = 0; c < nf * plane; ++c) {
+      const R a2 = uz[c] * uz[c], b2 = vz[c] * vz[c];
+      const R s2 = a2 + b2;
+      po[c] = b ? d[2][c] / s2 : s2;
+    }
+  }
+  return XG_OK;
+}
+
 // kinetic energy (ke_only) and the vector-invariant momentum advection of the header: the stages of the chain one after
 // the other over whole planes, each read through `get`, which pads a plane by one cell on one axis at a time (periodic:
 // the plane's own value at the wrapped index, extend: at the clamped index, fill: the fill value of that axis).
@@ -1361,6 +1439,27 @@ int xg_implicit_vertical_diffusion(int dtype, const void* a, const void* kappa, 
     return vimpl<float>((const float*)a, arr, st, (float*)work, (float*)out, shape, ndim, outer, (float)dt);
   }
   return fail(XG_ERR_INVALID, "implicit vertical diffusion: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+
+int xg_richardson_number(int dtype, const void* b, const void* u, const void* v, const void* mu, const int64_t* mus,
+                         const void* mv, const int64_t* mvs, const void* mb, const int64_t* mbs, void* out,
+                         const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
+                         double fill_z, void*) {
+  const int64_t* const st[3] = {mus, mvs, mbs};
+  const int bc[3] = {bc_x, bc_y, bc_z};
+  if (dtype == XG_T_F64) {
+    const double* const arr[3] = {(const double*)mu, (const double*)mv, (const double*)mb};
+    const double fill[3] = {fill_x, fill_y, fill_z};
+    return richardson<double>((const double*)b, (const double*)u, (const double*)v, arr, st, (double*)out, shape, ndim, outer,
+                              bc, fill);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const arr[3] = {(const float*)mu, (const float*)mv, (const float*)mb};
+    const float fill[3] = {(float)fill_x, (float)fill_y, (float)fill_z};
+    return richardson<float>((const float*)b, (const float*)u, (const float*)v, arr, st, (float*)out, shape, ndim, outer, bc,
+                             fill);
+  }
+  return fail(XG_ERR_INVALID, "richardson number: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 
 int xg_convert(const void* src, int st, void* dst, int dt, uint64_t n, int via, double scale, int flags, void*) {

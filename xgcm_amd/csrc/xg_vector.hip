@@ -2076,6 +2076,185 @@ __global__ __launch_bounds__(BLOCK) void k_vimpl(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7n: the squared vertical shear and the gradient Richardson number at the flux faces of Z in ONE pass over
+// (lead, Z, Y, X), two or three fields in, one out (nz faces at Z:left, nz + 1 at Z:outer):
+//   du[k] = (u[k] - u[k-1]) [/ mu[k]]    at u's points,     dv[k] = (v[k] - v[k-1]) [/ mv[k]]    at v's points
+//   S2[k] = uz * uz + vz * vz,   uz = (du[j,i] + du[j,i+1]) * 0.5,   vz = (dv[j,i] + dv[j+1,i]) * 0.5      (no FMA)
+//   Ri[k] = ((b[k] - b[k-1]) [/ mb[k]]) / S2[k]                                                  (RI; without it: S2)
+// i.e. diff | derivative (Z, center -> left | outer) of u, v and b, interp (X / Y, left -> center) of the first two, the
+// squares, their sum, the quotient: MITgcm's form, the shear averaged to the centre first and squared then.  Pads as the
+// chain's: u, v and b above level 0 and (`outer`) below level nz-1 (periodic: the far level, extend: the level itself,
+// fill: fill_z), then the DERIVATIVES right of the last column / above the last row (periodic: the derivative at index 0,
+// extend: at n-1, fill: the fill value itself).  No guard on S2 == 0: the quotient is IEEE's.
+// K7j's march with K7g's neighbours: a wave owns one (lead, Y segment, X tile) column and marches the faces with the rows
+// of the level above in registers -- SEG rows of u with the element right of the lane's vector where the lane forms that
+// derivative itself (the tile's last lane, the row's edge; every other lane takes the finished derivative from the lane
+// above by DPP), SEG + 1 rows of v (the row above the segment: an L2 hit, the next segment's first row), SEG rows of b.
+// u, v and b are read once and the result written once: 32 B/cell in float64 (S2: 24).  The three metrics (the Z metric at
+// u's points, at v's points, at the centre, all at the faces) are one broadcast array each, each may be absent; rows that
+// do not vary along Z are loaded once per wave.  Periodic Z costs one more level read before the march (and, `outer`, one
+// after it).
+// ------------------------------------------------------------------------------------------
+template <typename T, int SEG>
+struct RiLevel {  // what one level of a column brings: SEG rows of u and b, SEG + 1 rows of v, u right of the lane
+  T uu[SEG], vv[SEG + 1], bb[SEG];
+  real ur[SEG];
+};
+
+template <int V, bool RI, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_richardson(
+    const real* __restrict__ b, const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ out,
+    int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int bc_x,
+    real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mu, VolIdx mv, VolIdx mb, int ntl) {
+  typedef typename VecT<V>::type T;
+  typedef RiLevel<T, SEG> L;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  const int64_t nf = nz + outer;       // faces
+  // X as K7g's u: the column right of the lane's vector (periodic: column 0, extend: column nx - 1 itself); Y as K7g's v:
+  // the row above the segment (periodic: row 0 above row ny - 1, extend: row ny - 1 itself); a fill edge replaces the value
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);  // (the right side only)
+  const bool fill_r = e.edge_r && bc_x == XG_BC_FILL;
+  const int64_t q = j0 + nrow;
+  const bool fill_t = q >= ny && bc_y == XG_BC_FILL;
+  const int64_t jt = (q < ny) ? q : ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1);  // the row the top derivative is formed at
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+
+  auto fetch = [&](int64_t k) -> L {
+    L x;
+    const int64_t lv = col + k * plane;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.uu[s_] = *reinterpret_cast<const T*>(u + lv + ro[s_] + i0);
+      x.ur[s_] = e.own_r ? u[lv + ro[s_] + e.ridx] : real(0);
+      x.vv[s_] = *reinterpret_cast<const T*>(v + lv + ro[s_] + i0);
+      if (RI) x.bb[s_] = *reinterpret_cast<const T*>(b + lv + ro[s_] + i0);
+    }
+    x.vv[SEG] = *reinterpret_cast<const T*>(v + lv + jt * nx + i0);
+    return x;
+  };
+  auto padded = [&]() -> L {  // a level of the fill value
+    L x;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.uu[s_] = x.vv[s_] = splat<T>(fill_z);
+      if (RI) x.bb[s_] = splat<T>(fill_z);
+      x.ur[s_] = fill_z;
+    }
+    x.vv[SEG] = splat<T>(fill_z);
+    return x;
+  };
+
+  // the metric rows of a face: in registers, loaded again per face only when the array varies along Z; the metric of u also
+  // at the column right of the lane's vector, for the lanes that form that derivative themselves
+  T mur[SEG], mvr[SEG + 1], mbr[SEG];
+  real mrr[SEG];
+  int64_t muo = 0, mro = 0, mvo = 0, mto = 0, mbo = 0;
+  auto metrics = [&](int64_t k, bool first) {
+    if (mu.p && (first || mu.sz != 0)) {
+      load_rows<T, SEG>(mur, mu.p, muo + k * mu.sz, mu.sy, mu.sx, nrow, (ntl & 4) != 0);
+      if (e.own_r) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) mrr[s_] = mu.p[mro + k * mu.sz + ((s_ < nrow) ? s_ : nrow - 1) * mu.sy];
+      }
+    }
+    if (mv.p && (first || mv.sz != 0)) {
+      T rows[SEG];
+      load_rows<T, SEG>(rows, mv.p, mvo + k * mv.sz, mv.sy, mv.sx, nrow, (ntl & 8) != 0);
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) mvr[s_] = rows[s_];
+      T top[1];
+      load_rows<T, 1>(top, mv.p, mto + k * mv.sz, mv.sy, mv.sx, 1, (ntl & 8) != 0);
+      mvr[SEG] = top[0];
+    }
+    if (RI) {
+      if (mb.p && (first || mb.sz != 0)) load_rows<T, SEG>(mbr, mb.p, mbo + k * mb.sz, mb.sy, mb.sx, nrow, (ntl & 16) != 0);
+    }
+  };
+  if (MET) {
+    const int64_t uo = mu.p ? area_outer_off(mu.ai, o) : 0, vo = mv.p ? area_outer_off(mv.ai, o) : 0;
+    muo = uo + j0 * mu.sy + i0 * mu.sx;
+    mro = uo + j0 * mu.sy + e.ridx * mu.sx;
+    mvo = vo + j0 * mv.sy + i0 * mv.sx;
+    mto = vo + jt * mv.sy + i0 * mv.sx;
+    if (RI) {
+      if (mb.p) mbo = area_outer_off(mb.ai, o) + j0 * mb.sy + i0 * mb.sx;
+    }
+    metrics(0, true);
+  }
+
+  // one face from the level above it (`lo`) and the level below it (`hi`)
+  real* po = out + o * nf * plane + j0 * nx + i0;
+  auto face = [&](int64_t k, const L& lo, const L& hi) {
+    T du[SEG], dv[SEG + 1];
+    real dr[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      du[s_] = op2<XG_OP_DIFF>(lo.uu[s_], hi.uu[s_]);
+      dr[s_] = hi.ur[s_] - lo.ur[s_];
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG + 1; ++s_) dv[s_] = op2<XG_OP_DIFF>(lo.vv[s_], hi.vv[s_]);
+    if (MET) {
+      if (mu.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) du[s_] = du[s_] / mur[s_];
+        if (e.own_r) {
+#pragma unroll
+          for (int s_ = 0; s_ < SEG; ++s_) dr[s_] = dr[s_] / mrr[s_];
+        }
+      }
+      if (mv.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG + 1; ++s_) dv[s_] = dv[s_] / mvr[s_];
+      }
+    }
+    if (e.shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real right = from_lane_above(vec_first(du[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+        if (!e.own_r) dr[s_] = right;
+      }
+    }
+    const T top = fill_t ? splat<T>(fill_y) : dv[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        const T uz = interp_right_of(du[s_], fill_r ? fill_x : dr[s_]);
+        const T vz = op2<XG_OP_INTERP>(dv[s_], (s_ + 1 < nrow) ? dv[s_ + 1] : top);
+        T z = uz * uz + vz * vz;
+        if (RI) {
+          T db = op2<XG_OP_DIFF>(lo.bb[s_], hi.bb[s_]);
+          if (MET) {
+            if (mb.p) db = db / mbr[s_];
+          }
+          z = db / z;
+        }
+        stg_s<T, NTS>(po + k * plane + s_ * nx, z);
+      }
+    }
+  };
+
+  // face 0 lies between the pad above level 0 and level 0; the march keeps the level above the face
+  L cur = fetch(0), prev;
+  if (bc_z == XG_BC_PERIODIC) prev = fetch(nz - 1);
+  else if (bc_z == XG_BC_EXTEND) prev = cur;
+  else prev = padded();
+  for (int64_t k = 0;;) {
+    face(k, prev, cur);
+    if (++k >= nf) break;
+    prev = cur;
+    if (k < nz) cur = fetch(k);                           // (`outer`, the last face: the pad below level nz-1 --
+    else if (bc_z == XG_BC_PERIODIC) cur = fetch(0);      //  extend: the level itself, which `cur` still holds)
+    else if (bc_z == XG_BC_FILL) cur = padded();
+    if (MET) metrics(k, false);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -2915,6 +3094,74 @@ int xg_implicit_vertical_diffusion(int dtype, const void* a, const void* kappa, 
     return xg_internal_vimpl_f32((const float*)a, (const float*)kappa, kappa_strides, (const float*)mf, mf_strides,
                                  (const float*)mc, mc_strides, (float*)work, (float*)out, shape, ndim, outer, (float)dt, stream);
   return fail(XG_ERR_INVALID, "implicit vertical diffusion: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+
+// K7n's launcher: (lead, Z, Y, X) fields of `shape`, the result with nz (`outer`: nz + 1) faces, three optional broadcast
+// metrics at the faces (the Z metric at u's points, at v's points, at the centre), one wave per column.  b NULL: the squared
+// shear alone, and `mb` is not looked at.  One ABI entry for both element types (xg_richardson_number, below).
+__attribute__((visibility("hidden"))) int xg_internal_richardson_f64(
+    const double* b, const double* u, const double* v, const double* mu, const int64_t* mu_strides, const double* mv,
+    const int64_t* mv_strides, const double* mb, const int64_t* mb_strides, double* out, const int64_t* shape, int ndim,
+    int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_richardson_f32(
+    const float* b, const float* u, const float* v, const float* mu, const int64_t* mu_strides, const float* mv,
+    const int64_t* mv_strides, const float* mb, const int64_t* mb_strides, float* out, const int64_t* shape, int ndim,
+    int outer, int bc_x, float fill_x, int bc_y, float fill_y, int bc_z, float fill_z, void* stream);
+
+int XG_FN(xg_internal_richardson)(const real* b, const real* u, const real* v, const real* mu, const int64_t* mu_strides,
+                                  const real* mv, const int64_t* mv_strides, const real* mb, const int64_t* mb_strides,
+                                  real* out, const int64_t* shape, int ndim, int outer, int bc_x, real fill_x, int bc_y,
+                                  real fill_y, int bc_z, real fill_z, void* stream) {
+  const char* name = "richardson number";
+  if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  if (!b) mb = nullptr;
+  FusedPlan p;
+  const bool al = aligned16(u) && aligned16(v) && aligned16(b) && aligned16(out);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  VolIdx mi[3];  // the Z metric at u's points, at v's points, at the centre
+  const real* mp[3] = {mu, mv, mb};
+  const int64_t* ms[3] = {mu_strides, mv_strides, mb_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  // bit 0: the lane neighbour by DPP (K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
+  int vnt = vec_nt_bits(1);
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool ri = b != nullptr, met = mu != nullptr || mv != nullptr || mb != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, R_, M_, NTS) do { hipLaunchKernelGGL((k_richardson<V_, R_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, u, v, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt); } while (0)
+#define XG_N(V_, R_, M_) do { if (p.nts) XG_GO(V_, R_, M_, true); else XG_GO(V_, R_, M_, false); } while (0)
+#define XG_M(V_, R_) do { if (met) XG_N(V_, R_, true); else XG_N(V_, R_, false); } while (0)
+#define XG_V(V_) do { if (ri) XG_M(V_, true); else XG_M(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_M
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument, the fills are cast to it here
+int xg_richardson_number(int dtype, const void* b, const void* u, const void* v, const void* mu, const int64_t* mu_strides,
+                         const void* mv, const int64_t* mv_strides, const void* mb, const int64_t* mb_strides, void* out,
+                         const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
+                         double fill_z, void* stream) {
+  if (dtype == XG_T_F64)
+    return xg_internal_richardson_f64((const double*)b, (const double*)u, (const double*)v, (const double*)mu, mu_strides,
+                                      (const double*)mv, mv_strides, (const double*)mb, mb_strides, (double*)out, shape, ndim,
+                                      outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, stream);
+  if (dtype == XG_T_F32)
+    return xg_internal_richardson_f32((const float*)b, (const float*)u, (const float*)v, (const float*)mu, mu_strides,
+                                      (const float*)mv, mv_strides, (const float*)mb, mb_strides, (float*)out, shape, ndim,
+                                      outer, bc_x, (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
+  return fail(XG_ERR_INVALID, "richardson number: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 #endif
 

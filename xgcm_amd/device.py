@@ -1374,6 +1374,36 @@ def implicit_vertical_diffusion(a, kappa, mf, mc, outer: bool, dt: float) -> tor
     return out
 
 
+def richardson_number(b, u, v, mu, mv, mb, outer: bool, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0,
+                      fill_y: float = 0.0, fill_z: float = 0.0) -> torch.Tensor:
+    """Fused gradient Richardson number at the faces of Z in one pass (xg_richardson_number): the differences of u, v and `b`
+    to the level above, divided by `mu`, `mv`, `mb` (None = no division), the means of the first two with the difference
+    right of / above them, the sum of their squares, the quotient.  `b` None: the squared shear alone (`mb` is ignored).
+    `outer` False: nz faces (Z:left), the fields are padded above level 0; True: nz + 1 (Z:outer), padded on both sides.
+    The differences are padded right of the last column / above the last row.  The metrics broadcast against the result."""
+    lib = _MEM.lib()
+    dt, sfx = _common(u, v, b, mu, mv, mb)
+    u, v = asdevice(u, dt), asdevice(v, dt)
+    b = None if b is None else asdevice(b, dt)
+    if u.dim() < 3 or u.shape[-3] == 0:
+        raise ValueError("richardson_number: the fields need (Z, Y, X) as their last three dims and a level along Z")
+    if v.shape != u.shape or (b is not None and b.shape != u.shape):
+        raise ValueError("richardson_number: u, v and b must have the same shape")
+    shape = list(u.shape)
+    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
+    mets = [_prep_metric(m, dt) for m in (mu, mv, None if b is None else mb)]
+    out = _empty(fshape, dtype=dt, device=u.device)
+    if out.numel() == 0:
+        return out
+    margs = []
+    for m, what in zip(mets, ("metric at u's points", "metric at v's points", "metric at the centre")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, fshape, what))]
+    _check(lib.xg_richardson_number(_hip.DTYPE["float32" if sfx == "f32" else "float64"], _ptr(b), u.data_ptr(), v.data_ptr(),
+                                    *margs, out.data_ptr(), _hip.i64(shape), len(shape), int(bool(outer)), _hip.BC[bc_x],
+                                    float(fill_x), _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z), _stream()))
+    return out
+
+
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""

@@ -1957,6 +1957,129 @@ class Grid:
             res = DataArray(out, dims, coords={k: v for k, v in a.coords.items()}, name=a.name, attrs=a.attrs)
         return to_xarray(res) if was_xr else res
 
+    def vertical_shear_squared(self, u, v, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", to=None, padding=None,
+                               fill_value=None, metric_weighted: bool = True):
+        """Squared vertical shear of a C-grid velocity, S2 = (du/dz)^2 + (dv/dz)^2, at the cell centre on the flux faces of
+        Z in ONE pass: u and v are read once and the result written once (24 B/cell in float64).  `richardson_number`
+        without its numerator: see there for positions, pads, metrics and the cases the chain itself serves.  Bit-identical,
+        dims, coords and name included, to the chain
+
+            kw = dict(padding=padding, fill_value=fill_value)
+            step = grid.derivative if metric_weighted else grid.diff
+            uz = grid.interp(step(u, z_axis, to=to, **kw), x_axis, **kw)
+            vz = grid.interp(step(v, z_axis, to=to, **kw), y_axis, **kw)
+            s2 = uz * uz + vz * vz"""
+        return self._richardson(None, u, v, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted)
+
+    def richardson_number(self, b, u, v, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", to=None, padding=None,
+                          fill_value=None, metric_weighted: bool = True):
+        """Gradient Richardson number Ri = N2 / S2 -- what every Richardson-number mixing closure (Pacanowski-Philander, the
+        interior part of KPP) computes `kappa` from, at the faces where `vertical_diffusion` takes it -- in ONE pass: b, u
+        and v are read once and the result written once (32 B/cell in float64, against about 170 for the nine launches of
+        the chain); every intermediate stays in registers.
+
+        b at (Z:center, Y:center, X:center), u at (Z:center, Y:center, X:left), v at (Z:center, Y:left, X:center), any
+        leading dims, Z third from last; the result has dims (lead, Z face, Y:center, X:center).  `to`: the flux position
+        on Z, "left" (nz faces) or "outer" (nz + 1); None: "outer" when the Z axis has one, else "left", as in
+        `vertical_diffusion`.  Bit-identical, dims, coords and name included, to the chain
+
+            kw = dict(padding=padding, fill_value=fill_value)
+            step = grid.derivative if metric_weighted else grid.diff
+            uz = grid.interp(step(u, z_axis, to=to, **kw), x_axis, **kw)   # (Zf, YC, XG) -> (Zf, YC, XC)
+            vz = grid.interp(step(v, z_axis, to=to, **kw), y_axis, **kw)   # (Zf, YG, XC) -> (Zf, YC, XC)
+            s2 = uz * uz + vz * vz                                         # vertical_shear_squared
+            ri = step(b, z_axis, to=to, **kw) / s2
+
+        MITgcm's form: the shear is averaged to the centre first and squared then.  Pads where the chain pads.  Along Z, u,
+        v and b above level 0 and, "outer", below level nz-1 (periodic: the far level; extend: the level itself, so the
+        difference is exactly 0; fill: `fill_value`).  Along X and Y the Z-DERIVATIVES right of the last column / above the
+        last row (periodic: the derivative at index 0, extend: at n-1, fill: `fill_value` itself, not a derivative formed
+        from it).  No fused multiply-add, IEEE quotients.
+
+        No guard on S2 == 0: the quotient is IEEE's, inf, or NaN for 0 / 0 (both differences vanish at the outermost faces
+        under `extend` with "outer").  A floor on the shear belongs to the closure.
+
+        The metrics are whatever `get_metric` returns at the three derivatives' dims (drC, or registered 3-D thicknesses at
+        u's points, at v's points and at the centre), one broadcast array each, read through strides.
+
+        The chain itself runs (the same calls in the same order) for integer, float16 or mixed dtypes, for fewer than three
+        dims or Z not third from last, for u or v not on the C-grid positions above or fields of different shapes, for
+        another `to` or a position the axis lacks, for chunked inputs or chunked metrics, for a metric with dims its stage
+        lacks, for a metric lookup that raises (the chain raises it), for an axis without a boundary, for fields without a
+        level along Z, and with face connections or a fold along any of the three axes."""
+        return self._richardson(b, u, v, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted)
+
+    def _richardson(self, b, u, v, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted):
+        """`richardson_number`, or with b None `vertical_shear_squared`: one launch of K7n, or their chain"""
+        ri = b is not None
+        args = (b, u, v)
+        (b, xr0), (u, xr1), (v, xr2) = (self._wrap_in(a) for a in args)
+        was_xr = xr0 or xr1 or xr2
+        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
+        if to is None:
+            to = "outer" if "outer" in zax.coords else "left"
+        plan = None
+        fields = [f for f in (u, v, b) if f is not None]
+        served = (all(isinstance(f, DataArray) and f.ndim >= 3 for f in fields) and to in ("left", "outer") and to in zax.coords
+                  and all("center" in ax.coords for ax in (zax, yax, xax))
+                  and "left" in yax.coords and "left" in xax.coords and u.shape[-3] > 0
+                  and not gridops.complex_topology(self, z_axis))
+        if served:
+            tz, zf = zax.coords["center"], zax.coords[to]
+            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            lead = u.dims[:-3]
+            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
+            served = (u.dims == lead + (tz, yc, xl) and v.dims == lead + (tz, yl, xc) and (not ri or b.dims == lead + (tz, yc, xc))
+                      and not held & set(lead))
+        mets = [None, None, None]
+        if served:
+            f_shape = tuple(u.shape[:-3]) + (u.shape[-3] + (1 if to == "outer" else 0),) + tuple(u.shape[-2:])
+            f_dims = [lead + (zf, yc, xl), lead + (zf, yl, xc), lead + (zf, yc, xc)]   # the derivatives of u, v, b; the result
+            try:
+                if metric_weighted:
+                    for k, f in enumerate((u, v, b)):
+                        if f is not None:
+                            mets[k] = self._resident(self.get_metric(_DimsOnly(f_dims[k], f.name), (z_axis,), _layout=f_dims[k]),
+                                                     u.data)
+                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, f_dims))
+            except (KeyError, ValueError):
+                served = False  # (the chain raises it where the chain looks the metric up)
+        if served:
+            plan = self._second_order_plan(fields, x_axis, y_axis, padding, fill_value, [m for m in mets if m is not None])
+        if plan is not None:
+            bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
+            fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
+            # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as it is
+            # (None: 0.0), so a -0.0 or a NaN keeps its bits on all three axes
+            fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
+            plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            b, u, v = args
+            step = self.derivative if metric_weighted else self.diff
+            uz = self.interp(step(u, z_axis, to=to, **kw), x_axis, **kw)
+            vz = self.interp(step(v, z_axis, to=to, **kw), y_axis, **kw)
+            s2 = uz * uz + vz * vz
+            return step(b, z_axis, to=to, **kw) / s2 if ri else s2
+        bcx, bcy, fvx, fvy, bcz, fvz = plan
+        host = not any(_is_tensor(f.data) for f in fields)
+        mu, mv, mb = (None if m is None else _aligned_view(m, dims) for m, dims in zip(mets, f_dims))
+        out = _dev.richardson_number(b.data if ri else None, u.data, v.data, mu, mv, mb, to == "outer", bcx, bcy, bcz,
+                                     fvx, fvy, fvz)
+
+        # dims, coords and name as the chain's, step by step over placeholders: the derivatives at the faces (named after
+        # their quotients with the metric), the two means at the centre, the squares, their sum, the quotient
+        def faces(f, k):
+            g = self._labels_of_step(f, f_dims[k], zf, f_shape)
+            return g if mets[k] is None else g._replace(name=_name_after(g.name, mets[k]))
+
+        uz, vz = self._labels_of_step(faces(u, 0), f_dims[2], xc), self._labels_of_step(faces(v, 1), f_dims[2], yc)
+        res = self._labels_of_binary(self._labels_of_binary(uz, uz), self._labels_of_binary(vz, vz))
+        if ri:
+            res = self._labels_of_binary(faces(b, 2), res)
+        res = res._replace(data=_dev.tohost(out) if host else out)
+        return to_xarray(res) if was_xr else res
+
     # ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---------------------
     def _c_grid_vector(self, u, v, x_axis, y_axis, what):
         """dims of a C-grid vector's points: (lead, at u, at v, centre, vorticity point); raises when u / v sit elsewhere"""
@@ -1969,9 +2092,11 @@ class Grid:
         lead = u.dims[:-2]
         return lead, lead + (uy_dim, ux_dim), lead + (vy_dim, vx_dim), lead + (uy_dim, vx_dim), lead + (vy_dim, ux_dim)
 
-    def _labels_of_step(self, src, dims, out_dim):
-        """placeholder with the dims, coords and name a one-axis operator gives its result (gridops.HipGridUFunc)"""
-        return _reattach_coords([DataArray(_placeholder(src.shape), dims, name=src.name)], self, None, {out_dim}, [src])[0]
+    def _labels_of_step(self, src, dims, out_dim, shape=None):
+        """placeholder with the dims, coords and name a one-axis operator gives its result (gridops.HipGridUFunc); `shape`:
+        the result's, where the step changes the length of its axis"""
+        return _reattach_coords([DataArray(_placeholder(src.shape if shape is None else shape), dims, name=src.name)], self, None,
+                                {out_dim}, [src])[0]
 
     @staticmethod
     def _labels_of_binary(a, b):
