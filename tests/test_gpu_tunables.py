@@ -3,15 +3,15 @@
 `xg_set_tunable` / `XG_<NAME>` choose among kernels and work orders -- speed, never results (include/xgcm_hip.h "tunables";
 VERDICT r05 weak #10: "30+ knobs reachable from environment variables are a large untested configuration surface").  Here a
 battery of calls -- flat and marching stencils with and without metrics, the three scans, the reductions in every mode, pads,
-the fused vector operators, the one-pass operators K7d - K7k, both transforms -- is run once under the defaults and then again
-under each alternative value of each tunable, float64 and float32: bit for bit the same, except along the contiguous axis where
-sums are re-associated by contract (rtol 1e-12 / 1e-5).
+the fused vector operators, the one-pass operators K7d - K7k, both transforms, the pre-gathered halo forms and the gather that
+fills their slabs -- is run once under the defaults and then again under each alternative value of each tunable, float64 and
+float32: bit for bit the same, except along the contiguous axis where sums are re-associated by contract (rtol 1e-12 / 1e-5).
 
 What the battery reaches is checked, not claimed: the default run records which entries of the C ABI are fetched from the
 library, and every `xg_*_f64` / `xg_*_f32` entry of `_hip.SIGNATURES` has to be among them or in `NOT_IN_BATTERY` with its
-reason -- the halo forms, the gather, the halo put and the input generator today.  The entries for K7i - K7k
-(`_one_pass_entries`) are also compared with plain numpy before the sweep, and tests/test_tunable_battery_entries.py runs
-them through the host build of the ABI on a machine without a GPU."""
+reason -- the halo put and the input generator today.  The entries for K7i - K7k (`_one_pass_entries`) and for the halo forms
+and the gather (`_halo_entries`) are also compared with plain numpy before the sweep, and tests/test_tunable_battery_entries.py
+runs them on a machine without a GPU: through the host build of the ABI where it serves the entry, else on the oracle's double."""
 import numpy as np
 import pytest
 
@@ -36,13 +36,7 @@ ALTERNATIVES = {
 NOT_SWEPT = {"scan_chain_spin": "forces the rescue path: tests/test_gpu_chain_rescue.py", "dbg": "debug switches of single experiments"}
 # entries of the C ABI (without their _f64 / _f32 suffix) that no battery call reaches, and why: the test fails for an entry that
 # is neither reached nor named here, and for a name here that is reached or no longer exists
-_HALO = ("the halo forms run under the defaults only (tests/test_gpu_kernels.py, tests/test_topology.py): a gap of the same kind, "
-         "to be closed by battery entries of their own")
 NOT_IN_BATTERY = {
-    "xg_stencil1d_halo": _HALO, "xg_stencil1d_halo_w": _HALO, "xg_vorticity_halo": _HALO, "xg_divergence_halo": _HALO,
-    "xg_gradient_halo": _HALO, "xg_flux_halo": _HALO,
-    "xg_gather": "the face-connection gather reads pad_rows / pad_tpw / pad_nt and runs under the defaults only "
-                 "(tests/test_gpu_kernels.py): the same gap as the halo forms, to be closed with them",
     "xg_halo_put": "writes halo slabs into a padded array: it reads no tunable (through Grid's padding: tests/test_topology.py)",
     "xg_fill_synthetic": "the benchmark's input generator, no operator: tests/test_gpu_kernels.py compares it with the oracle",
 }
@@ -54,9 +48,7 @@ def _battery(D, dtype, references=None):
     reference thunk for the entries that have one"""
     f = lambda shape, seed: R.synthetic_field(shape, seed).astype(dtype)  # noqa: E731
     m = lambda shape, seed: R.synthetic_metric(shape, seed).astype(dtype)  # noqa: E731
-    a = f((5, 300, 264), 1)
-    a[1, 7, 9] = np.nan
-    odd = f((3, 65, 131), 2)
+    a, odd = _battery_fields(dtype)
     wide = f((2, 4, 40, 4100), 3)
     mxy, mxy2, mz, my = m((1, 300, 264), 4), m((1, 300, 264), 5), m((5, 1, 1), 6), m((1, 300, 1), 7)
     calls = {}
@@ -118,7 +110,8 @@ def _battery(D, dtype, references=None):
     theta_o = np.cumsum(R.synthetic_field((21, 24, 128), 13).astype(dtype) + dtype(0.55), axis=0)
     calls["tlin"] = (lambda: D.transform_linear(phi, theta, np.linspace(0.5, 9.0, 12).astype(dtype).reshape(12, 1, 1), 0), True)
     calls["tcon"] = (lambda: D.transform_conservative(phi, theta_o, np.linspace(0.0, 12.0, 14).astype(dtype), 0), True)
-    for k, (fn, reference) in _one_pass_entries(D, dtype).items():   # K7i - K7k
+    # K7i - K7k; the pre-gathered halo forms and the gather
+    for k, (fn, reference) in list(_one_pass_entries(D, dtype).items()) + list(_halo_entries(D, dtype).items()):
         assert k not in calls
         calls[k] = (fn, True)
         if references is not None:
@@ -224,6 +217,62 @@ def _one_pass_entries(D, dtype):
     return out
 
 
+def _battery_fields(dtype):
+    """the battery's own `a` (a march of 300 rows, one NaN cell) and `odd` (odd, unaligned rows)"""
+    a = R.synthetic_field((5, 300, 264), 1).astype(dtype)
+    a[1, 7, 9] = np.nan
+    return a, R.synthetic_field((3, 65, 131), 2).astype(dtype)
+
+
+def _halo_entries(D, dtype, V=None):
+    """name -> (thunk, reference) for the pre-gathered halo forms and the gather: the four vector forms at (3, 29, 260) and
+    (3, 29, 259), area / metrics level-shared in one and of the fields' own shape in the other, the seven mode pairs that
+    contain a halo rotating; `stencil1d_halo` and `stencil1d_halo_w` on the battery's `a` and `odd` along each axis, the
+    operators, the pads and the metric forms rotating; the three gather cases.  Inputs are uploaded once; the references are
+    the plain numpy statements of tests/test_halo_forms.py; every entry is exact.  `V`: the module that serves the vector
+    forms and the gather (the CPU twin passes the oracle's double, since the host build of the ABI has the two stencil forms
+    only); `D` by default"""
+    import test_halo_forms as TH
+
+    V = D if V is None else V
+    out = {}
+    pairs = iter(TH.PAIRS * 2)
+    for nx, form in zip(OP_NXS, ("shared", "own")):
+        case = TH.VectorCase(OP_NY, nx, (OP_LEAD2,), dtype)
+        if form == "shared":   # what `fused_band` asks of a call before it bands it
+            assert TH.area_shape(form, case.lead, OP_NY, nx)[0] == 1 and case.lead[0] >= 2
+        for op in ("vorticity", "divergence", "gradient", "flux"):
+            planes = {"gradient": (case.area(form, 331), case.area(form, 332)), "flux": ()}.get(op, (case.area(form),))
+            bx, by = next(pairs)
+            resident = {k: V.asdevice(x) for k, x in case.sets[op].items()}
+            dplanes = tuple(V.asdevice(p) for p in planes)
+            out[f"h{op[:4]}{nx}{form}"] = (
+                lambda case=case, op=op, p=(bx, by), d=dplanes, r=resident: case.call(V, op, *p, d, r),
+                lambda case=case, op=op, p=(bx, by), planes=planes: list(case.want(op, *p, planes)))
+    n = 0
+    for tag, x in zip(("a", "odd"), _battery_fields(dtype)):
+        xd = D.asdevice(x)
+        for axis in range(x.ndim):
+            for weighted in (False, True):
+                op, (lo, hi) = TH.OPS[n % 4], TH.STENCIL_PADS[n % 3]
+                hshape, oshape = list(x.shape), list(x.shape)
+                hshape[axis], oshape[axis] = lo + hi, x.shape[axis] + lo + hi - 1
+                halo = R.synthetic_field(tuple(hshape), 150 + n).astype(dtype)
+                halo.reshape(-1)[[0, -1]] = np.nan
+                m_in = R.synthetic_metric(TH._m_shape(TH.M_IN[1 + (n // 2) % 4], x.shape, axis), 170 + n).astype(dtype) if weighted else None
+                m_out = R.synthetic_metric(TH._m_shape(TH.M_OUT[1 + n % 2], oshape, axis), 190 + n).astype(dtype) if n % 3 else None
+                dev = lambda q: None if q is None else D.asdevice(q)  # noqa: E731
+                out[f"hst{'w' if weighted else ''}{tag}{axis}"] = (
+                    lambda a=(op, xd, dev(halo), axis, lo, hi, dev(m_out), dev(m_in)): D.stencil1d_halo(*a),
+                    lambda a=(op, x, halo, axis, lo, hi, m_out, m_in): [TH.want_stencil(*a)])
+                n += 1
+    for k in range(len(TH.GATHER_CASES)):
+        x, partner, args, want = TH.gather_case(k, dtype)
+        dx, dp, tok = V.asdevice(x), (None if partner is None else V.asdevice(partner)), V.upload_tokens(args[0])
+        out[f"hgather{k}"] = (lambda dx=dx, dp=dp, tok=tok, rest=args[1:]: V.gather(dx, dp, tok, *rest), lambda want=want: [want])
+    return out
+
+
 def _run(D, calls):
     out = {}
     for k, (fn, _) in calls.items():
@@ -277,7 +326,7 @@ def test_every_tunable_value_computes_the_same(dtype, monkeypatch):
     assert abi - reached - set(NOT_IN_BATTERY) == set(), f"ABI entries that no battery call reaches: {sorted(abi - reached - set(NOT_IN_BATTERY))}"
     assert set(NOT_IN_BATTERY) <= abi - reached, f"stale NOT_IN_BATTERY names: {sorted(set(NOT_IN_BATTERY) - (abi - reached))}"
     # the new entries against plain numpy first, so that the sweep does not only compare the library with itself
-    assert len(references) == 20
+    assert len(references) == 20 + 23   # K7i - K7k; eight vector halo entries, twelve stencil halo entries, three gathers
     for k, reference in references.items():
         ref = reference()
         assert len(ref) == len(want[k]) and all(_same_bits(g, w) for g, w in zip(want[k], ref)), f"{k}: the default result is not numpy's"

@@ -1,4 +1,5 @@
-"""The K7i - K7k entries of the tunables battery (`test_gpu_tunables._one_pass_entries`) on a machine without a GPU.
+"""The K7i - K7k entries of the tunables battery (`test_gpu_tunables._one_pass_entries`) and its entries for the pre-gathered
+halo forms and the gather (`_halo_entries`) on a machine without a GPU.
 
 The same thunks that tests/test_gpu_tunables.py sweeps over every tunable value run here once through the `host_abi` fixture
 (the product's `xgcm_amd.device` over libxgcm_host.so) and are compared bit for bit with their numpy references: the
@@ -30,6 +31,31 @@ def test_one_pass_entries_equal_their_numpy_references(host_abi, dtype):
             else:                          # the NaN cells reach the result and stay local
                 assert np.isnan(w).any() and np.isnan(w).mean() < 0.01, name
             assert TT._same_bits(g, w), name
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_halo_entries_equal_their_numpy_references(host_abi, dtype):
+    """`_halo_entries`: the two stencil forms through the host build of the ABI, the vector forms and the gather (for which
+    the host build answers `unsupported`) on the oracle's double"""
+    import test_halo_forms as TH
+    import xgcm_amd.device as D
+    from oracle import fake_device
+
+    entries = TT._halo_entries(D, dtype, V=fake_device)
+    assert len(entries) == 8 + 12 + 3
+    assert {k[:5] for k in entries} == {"hvort", "hdive", "hgrad", "hflux", "hstwa", "hstwo", "hstod", "hsta0", "hsta1", "hsta2", "hgath"}
+    for name, (thunk, reference) in entries.items():
+        got = thunk()
+        got = [D.tohost(x) for x in got] if isinstance(got, tuple) else [D.tohost(got)]
+        want = reference()
+        assert len(got) == len(want) == (2 if name[:5] in ("hgrad", "hflux") else 1), name
+        for g, w in zip(got, want):
+            assert g.dtype == np.dtype(dtype), name
+            assert np.isnan(w).any() and np.isnan(w).mean() < 0.01, name
+            assert TT._same_bits(g, w), name
+    # the eight vector entries take the mode pairs in turn: between them every pair that contains a halo
+    vector = [k for k in entries if k[:5] in ("hvort", "hdive", "hgrad", "hflux")]
+    assert len(vector) == 8 and set((TH.PAIRS * 2)[:len(vector)]) == set(TH.PAIRS) and len(set(TH.PAIRS)) == 7
 
 
 def test_the_entries_meet_every_boundary_mode_and_shape():
