@@ -139,16 +139,9 @@ def test_under_graph_capture(monkeypatch):
     TI._same_bits(out.data.cpu().numpy(), TI._want_of(ds, h2, k2, "outer", True))
 
 
-@pytest.mark.parametrize("dtype", TI.DTYPES, ids=["f64", "f32"])
-def test_every_tunable_value_computes_the_same(dtype):
-    """`device.implicit_vertical_diffusion` under every value of every tunable of the battery's table, on the battery's own
-    shapes, both flux positions, a 3-D kappa and both forms of the metrics: bit for bit what the defaults give, and that is
-    the numpy statement's"""
-    import warnings
-
-    from xgcm_amd import _hip
-    from xgcm_amd import device as D
-
+def tunable_calls(D, dtype):
+    """(calls, references) of the K7m tunable sweep: name -> thunk that calls `D` on inputs uploaded once, name -> thunk
+    that gives numpy's result of the same call; tests/test_gpu_guarded_memory.py runs the same table between guard bands"""
     f = lambda shape, seed: R.synthetic_field(shape, seed).astype(dtype)  # noqa: E731
     m = lambda shape, seed: R.synthetic_metric(shape, seed).astype(dtype)  # noqa: E731
     calls, references = {}, {}
@@ -168,6 +161,20 @@ def test_every_tunable_value_computes_the_same(dtype):
             dt = TI.abi_dt({"mf": mf, "mc": mc})
             calls[key] = lambda da=da, d=d, to=to, dt=dt: D.implicit_vertical_diffusion(da, *d, to == "outer", dt)
             references[key] = lambda a=a, h=(kappa, mf, mc), dt=dt: TI.statement(a, *h, dt)
+    return calls, references
+
+
+@pytest.mark.parametrize("dtype", TI.DTYPES, ids=["f64", "f32"])
+def test_every_tunable_value_computes_the_same(dtype):
+    """`device.implicit_vertical_diffusion` under every value of every tunable of the battery's table, on the battery's own
+    shapes, both flux positions, a 3-D kappa and both forms of the metrics: bit for bit what the defaults give, and that is
+    the numpy statement's"""
+    import warnings
+
+    from xgcm_amd import _hip
+    from xgcm_amd import device as D
+
+    calls, references = tunable_calls(D, dtype)
     run = lambda: {k: D.tohost(fn()) for k, fn in calls.items()}  # noqa: E731
     want = run()
     for k, reference in references.items():

@@ -125,16 +125,9 @@ def test_under_graph_capture(monkeypatch):
     TR._same_bits(got, c2.want()[0])
 
 
-@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
-def test_every_tunable_value_computes_the_same(dtype):
-    """`device.richardson_number` under every value of every tunable of the battery's table, on the battery's own shapes, both
-    face positions, with and without b and both forms of the metrics: bit for bit what the defaults give, and that is
-    numpy's"""
-    import warnings
-
-    from xgcm_amd import _hip
-    from xgcm_amd import device as D
-
+def tunable_calls(D, dtype):
+    """(calls, references) of the K7n tunable sweep: name -> thunk that calls `D` on inputs uploaded once, name -> thunk
+    that gives numpy's result of the same call; tests/test_gpu_guarded_memory.py runs the same table between guard bands"""
     f = lambda shape, seed: R.synthetic_field(shape, seed).astype(dtype)  # noqa: E731
     m = lambda shape, seed: R.synthetic_metric(shape, seed).astype(dtype)  # noqa: E731
     calls, references = {}, {}
@@ -155,6 +148,20 @@ def test_every_tunable_value_computes_the_same(dtype):
                 dev[0] if ri else None, dev[1], dev[2], *dm, to == "outer", *pads, *fill)
             references[key] = lambda h=(b, u, v), mets=mets, to=to, pads=pads, ri=ri: TR._want(
                 h[0] if ri else None, h[1], h[2], pads, to, TR.FILL, *(mets if ri else mets[:2]))
+    return calls, references
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_every_tunable_value_computes_the_same(dtype):
+    """`device.richardson_number` under every value of every tunable of the battery's table, on the battery's own shapes, both
+    face positions, with and without b and both forms of the metrics: bit for bit what the defaults give, and that is
+    numpy's"""
+    import warnings
+
+    from xgcm_amd import _hip
+    from xgcm_amd import device as D
+
+    calls, references = tunable_calls(D, dtype)
     run = lambda: {k: D.tohost(fn()) for k, fn in calls.items()}  # noqa: E731
     want = run()
     for k, reference in references.items():

@@ -140,15 +140,9 @@ def test_under_graph_capture(monkeypatch):
     assert got.shape == (2, nz, ny, nx) and torch.equal(got.view(torch.int64), want.data.view(torch.int64))
 
 
-@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
-def test_every_tunable_value_computes_the_same(dtype):
-    """`device.vertical_diffusion` under every value of every tunable of the battery's table, on the battery's own shapes, both
-    flux positions, a 3-D kappa and both forms of the metrics: bit for bit what the defaults give, and that is numpy's"""
-    import warnings
-
-    from xgcm_amd import _hip
-    from xgcm_amd import device as D
-
+def tunable_calls(D, dtype):
+    """(calls, references) of the K7l tunable sweep: name -> thunk that calls `D` on inputs uploaded once, name -> thunk
+    that gives numpy's result of the same call; tests/test_gpu_guarded_memory.py runs the same table between guard bands"""
     f = lambda shape, seed: R.synthetic_field(shape, seed).astype(dtype)  # noqa: E731
     m = lambda shape, seed: R.synthetic_metric(shape, seed).astype(dtype)  # noqa: E731
     calls, references = {}, {}
@@ -165,6 +159,19 @@ def test_every_tunable_value_computes_the_same(dtype):
             key = f"{nx}{to}{pz}"
             calls[key] = lambda da=da, d=d, to=to, pz=pz: D.vertical_diffusion(da, *d, to == "outer", pz, 0.375)
             references[key] = lambda a=a, h=(kappa, mf, mc), to=to, pz=pz: TD._want(a, *h, to, pz, dtype(0.375))
+    return calls, references
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_every_tunable_value_computes_the_same(dtype):
+    """`device.vertical_diffusion` under every value of every tunable of the battery's table, on the battery's own shapes, both
+    flux positions, a 3-D kappa and both forms of the metrics: bit for bit what the defaults give, and that is numpy's"""
+    import warnings
+
+    from xgcm_amd import _hip
+    from xgcm_amd import device as D
+
+    calls, references = tunable_calls(D, dtype)
     run = lambda: {k: D.tohost(fn()) for k, fn in calls.items()}  # noqa: E731
     want = run()
     for k, reference in references.items():
