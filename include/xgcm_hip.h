@@ -48,6 +48,7 @@
  *   xg_vertical_diffusion  derivative(derivative(a, Z) * kappa, Z): vertical diffusion / viscosity, one pass (float64 and
  *                      float32 through one entry: the element type is an argument)
  *   xg_implicit_vertical_diffusion  (I - dt d/dz(kappa d/dz)) x = a: a tridiagonal solve along Z, one pass (one entry likewise)
+ *   xg_implicit_vertical_viscosity  that solve for u and for v with one centre-point nu averaged to their columns, one pass
  *   xg_richardson_number  derivative(b, Z) / (interp(derivative(u, Z), X)^2 + interp(derivative(v, Z), Y)^2) at the faces of Z,
  *                      or the squared shear alone, one pass (one entry likewise)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
@@ -469,6 +470,25 @@ int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int
 int xg_implicit_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* kappa_strides, const void* mf,
                                    const int64_t* mf_strides, const void* mc, const int64_t* mc_strides, void* work, void* out,
                                    const int64_t* shape, int ndim, int outer, double dt, void* stream);
+/* Implicit vertical viscosity of a C-grid velocity with ONE viscosity at the centre points, one pass: two solves of the entry
+ * above, (I - dt d/dz(kappa_u d/dz)) xu = u and (I - dt d/dz(kappa_v d/dz)) xv = v, whose face weights are nu averaged to
+ * u's and to v's column in the element type, in this order:
+ *   kappa_u[k, j, i] = (nu[k, j, i-1] + nu[k, j, i]) * 0.5          kappa_v[k, j, i] = (nu[k, j-1, i] + nu[k, j, i]) * 0.5
+ * then w[k] = dt * (kappa[k] [/ mf[k]]) and the recurrence of xg_implicit_vertical_diffusion, operation by operation.
+ * u at (Z:center, Y:center, X:left), v at (Z:center, Y:left, X:center), both of `shape` (.., Z, Y, X), contiguous; the
+ * results and the two workspaces have that shape and element type (none may alias another).  nu at (Z face, Y:center,
+ * X:center) with broadcast strides (0 = broadcast) against `shape` with nz (outer = 0) or nz + 1 (outer = 1) levels along Z;
+ * faces 0 and nz are never read.  Only nu is padded: left of column 0 by bc_x (XG_BC_PERIODIC: column nx-1, XG_BC_EXTEND:
+ * column 0, XG_BC_FILL: fill_x cast to the element type, a -0.0 or a NaN keeping its bits) and below row 0 by bc_y (row ny-1,
+ * row 0, fill_y).  There is no pad along Z.  mfu / mfv: the metric of the flux at u's / v's points, strides as nu's; mcu /
+ * mcv: the metric of the result, against `shape` itself; NULL: absent.  The workspaces hold c on return (scratch).
+ * XG_ERR_INVALID: a NULL u, v, nu, result, workspace or shape, a plane without strides, outer not 0 or 1, a boundary code
+ * other than the three above, dt negative, NaN or infinite, a dtype other than XG_T_F64 / XG_T_F32. */
+int xg_implicit_vertical_viscosity(int dtype, const void* u, const void* v, const void* nu, const int64_t* nu_strides,
+                                   const void* mfu, const int64_t* mfu_strides, const void* mcu, const int64_t* mcu_strides,
+                                   const void* mfv, const int64_t* mfv_strides, const void* mcv, const int64_t* mcv_strides,
+                                   void* work_u, void* work_v, void* out_u, void* out_v, const int64_t* shape, int ndim,
+                                   int outer, int bc_x, double fill_x, int bc_y, double fill_y, double dt, void* stream);
 /* The squared vertical shear S2 and the gradient Richardson number Ri = N2 / S2 of a C-grid velocity at the faces of Z, one
  * pass.  Arrays of identical `shape` (.., Z, Y, X): b at (Z:center, Y:center, X:center), u at (Z:center, Y:center, X:left),
  * v at (Z:center, Y:left, X:center); `out`, at (Z face, Y:center, X:center), has nz (outer = 0, Z:left) or nz + 1 (outer = 1,

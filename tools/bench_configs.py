@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -291,6 +291,55 @@ def run_richardson_number(reps, nz=90, n=4320):
     rec(5, "richardson_number fused derivative(b, Z) / (interp(derivative(u, Z), X)^2 + interp(derivative(v, Z), Y)^2), to=outer, drC(Zp1), extend: 3 reads + 1 write", med(tf), cells, bpc)
     rec(5, "richardson_number as its chain (9 launches), fused-equivalent bytes", med(tc), cells, bpc)
     print(json.dumps({"config": 5, "check": "fused richardson_number == chain bit for bit at full size", "ok": ok,
+                      "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
+                      "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_implicit_vertical_viscosity(reps, nz=90, ny=4320, nx=4320):
+    """implicit_vertical_viscosity in one pass (one launch per component) against its chain of four calls (two interps of nu,
+    two implicit_vertical_diffusion solves; two face-sized temporaries) on resident tensors: nu (nz + 1, ny, nx) at Z:outer,
+    drC(Zp1), drF(Z), X periodic, Y extend, timed in turns, every paired round reported.  Fields, results, workspaces and the
+    chain's temporaries take about 120 GB at 4320 x 4320 x 90; when that allocation fails the pair runs at 75 x 2400 x 3600
+    and the records say so."""
+    coords = {"XC": ("XC", np.arange(nx) + 0.5), "XG": ("XG", np.arange(nx) * 1.0), "YC": ("YC", np.arange(ny) + 0.5),
+              "YG": ("YG", np.arange(ny) * 1.0), "Z": ("Z", np.arange(nz) + 0.5), "Zp1": ("Zp1", np.arange(nz + 1) * 1.0)}
+    drf, drc = D.synthetic((nz,), 33, 0, 10.0, 10.0), D.synthetic((nz + 1,), 34, 0, 10.0, 10.0)
+    ds = Dataset({"drF": DataArray(drf, ("Z",)), "drC": DataArray(drc, ("Zp1",))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                            "Z": {"center": "Z", "outer": "Zp1"}},
+                padding={"X": "periodic", "Y": "extend", "Z": "extend"}, metrics={("Z",): ["drF", "drC"]}, autoparse_metadata=False)
+    dt = 3600.0                                                                        # coupling dt nu / (drC drF) <= 3.6
+    cells = nz * ny * nx
+    try:
+        U = DataArray(D.synthetic((nz, ny, nx), 51), ("Z", "YC", "XG"))
+        V = DataArray(D.synthetic((nz, ny, nx), 52), ("Z", "YG", "XC"))
+        NU = DataArray(D.synthetic((nz + 1, ny, nx), 62, 0, 0.1, 0.0), ("Zp1", "YC", "XC"))   # 0 .. 0.1 m2/s over 10 .. 20 m layers
+
+        def chain():
+            nu_u, nu_v = grid.interp(NU, "X"), grid.interp(NU, "Y")
+            return grid.implicit_vertical_diffusion(U, nu_u, dt), grid.implicit_vertical_diffusion(V, nu_v, dt)
+
+        got, want = grid.implicit_vertical_viscosity(U, V, NU, dt=dt), chain()
+        ok = all(bool(torch.equal(g.data.view(torch.int64), w.data.view(torch.int64))) for g, w in zip(got, want))
+        del got, want
+        torch.cuda.empty_cache()
+        tf, tc = timeit_rounds(lambda: grid.implicit_vertical_viscosity(U, V, NU, dt=dt), chain, max(3, reps // 2))
+    except torch.cuda.OutOfMemoryError:
+        if (nz, ny, nx) == (75, 2400, 3600):
+            raise
+        print(json.dumps({"config": 5, "note": f"{nz} x {ny} x {nx} does not fit: implicit_vertical_viscosity at 75 x 2400 x 3600"}), flush=True)
+        U = V = NU = None
+        torch.cuda.empty_cache()
+        return run_implicit_vertical_viscosity(reps, 75, 2400, 3600)
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    # per component a, nu, d out and back, c out and back, x: 56; nu is read by each of the two launches (its 91st face is not
+    # counted).  The chain asks for 144: the two interps 16 + 16, the two solves 2 x 56
+    bpc = 112
+    size = f"{nz} x {ny} x {nx}"
+    rec(5, f"implicit_vertical_viscosity one pass (u and v, one launch each, nu averaged in the coefficient stage), {size}, drC / drF: per component a, nu, d and c out and back, x", med(tf), cells, bpc)
+    rec(5, f"implicit_vertical_viscosity as its chain (2 interps of nu + 2 implicit_vertical_diffusion), {size}, one-pass-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": f"one-pass implicit_vertical_viscosity == chain bit for bit at {size}", "ok": ok,
                       "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
                       "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
@@ -939,6 +988,8 @@ def main():
         run_implicit_vertical_diffusion(a.reps)
     if cfgs & {"5x", "5ri"}:
         run_richardson_number(a.reps)
+    if "5vv" in cfgs:   # (not part of 5x: about 120 GB)
+        run_implicit_vertical_viscosity(a.reps, *(shp or (90, 4320, 4320)))
     ranks.close()
 
 

@@ -209,6 +209,9 @@ SIGNATURES["xg_vertical_diffusion"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, 
                                                C.c_int, C.c_double, _vp])
 SIGNATURES["xg_implicit_vertical_diffusion"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _i64p,
                                                         C.c_int, C.c_int, C.c_double, _vp])
+SIGNATURES["xg_implicit_vertical_viscosity"] = (C.c_int, [C.c_int, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p,
+                                                        _vp, _vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                        C.c_double, C.c_double, _vp])
 SIGNATURES["xg_richardson_number"] = (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_int,
                                               C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, _vp])
 

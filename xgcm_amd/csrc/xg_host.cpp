@@ -758,9 +758,11 @@ int vdiff(const R* a, const R* const arr[3], const int64_t* const st[3], R* out,
 // the implicit vertical diffusion of the header, level by level over one (Z, Y, X) volume at a time: the Thomas algorithm with
 // every cell of a level advanced before the next level is touched.  c goes into `work`, d into `out`; the backward loop
 // turns d into x.  arr[] = {kappa, the metric of the flux, the metric of the result}; faces 0 and nz are never read.
+// `nb_axis` 0 (X) / 1 (Y): the implicit vertical viscosity of the header for one component -- kappa is the mean of arr[0] and
+// its neighbour left of / below the cell, (neighbour + value) * 0.5, the neighbour of column / row 0 padded by `bc` / `fill`.
 template <typename R>
 int vimpl(const R* a, const R* const arr[3], const int64_t* const st[3], R* work, R* out, const int64_t* shape, int ndim,
-          int outer, R dt) {
+          int outer, R dt, int nb_axis = -1, int bc = XG_BC_EXTEND, R fill = 0) {
   if (!a || !out || !work || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
   if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
   if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "outer %d is neither 0 (left) nor 1", outer);
@@ -785,6 +787,12 @@ int vimpl(const R* a, const R* const arr[3], const int64_t* const st[3], R* work
     // dt * kappa / mf at face z (1 .. nz-1)
     auto weight = [&](int64_t z, int64_t j, int64_t i) -> R {
       R g = arr[0] ? at(0, z, j, i) : one;
+      if (nb_axis >= 0) {
+        const int64_t q = nb_axis == 0 ? i : j, n = nb_axis == 0 ? nx : ny;
+        const int64_t src = q > 0 ? q - 1 : (bc == XG_BC_PERIODIC ? n - 1 : 0);
+        const R nb = (q == 0 && bc == XG_BC_FILL) ? fill : (nb_axis == 0 ? at(0, z, j, src) : at(0, z, src, i));
+        g = (nb + g) * R(0.5);
+      }
       if (arr[1]) g = g / at(1, z, j, i);
       return dt * g;
     };
@@ -819,6 +827,24 @@ int vimpl(const R* a, const R* const arr[3], const int64_t* const st[3], R* work
       for (int64_t c = z * plane; c < (z + 1) * plane; ++c) pd[c] = pd[c] + pc[c] * pd[c + plane];
   }
   return XG_OK;
+}
+
+// the implicit vertical viscosity of the header: `vimpl` for u with nu averaged along X and for v with nu averaged along Y
+template <typename R>
+int vvisc(const R* u, const R* v, const R* nu, const int64_t* nus, const void* const met[4], const int64_t* const ms[4], R* work_u,
+          R* work_v, R* out_u, R* out_v, const int64_t* shape, int ndim, int outer, int bc_x, R fill_x, int bc_y, R fill_y, R dt) {
+  if (!u || !v || !nu || !out_u || !out_v || !work_u || !work_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+  for (int b : {bc_x, bc_y})
+    if (b < XG_BC_PERIODIC || b > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", b);
+  const R* const au[3] = {nu, (const R*)met[0], (const R*)met[1]};
+  const R* const av[3] = {nu, (const R*)met[2], (const R*)met[3]};
+  const int64_t* const su[3] = {nus, ms[0], ms[1]};
+  const int64_t* const sv[3] = {nus, ms[2], ms[3]};
+  for (int k = 0; k < 3; ++k)
+    if ((au[k] && !su[k]) || (av[k] && !sv[k])) return fail(XG_ERR_INVALID, "a plane without strides");
+  const int rc = vimpl<R>(u, au, su, work_u, out_u, shape, ndim, outer, dt, 0, bc_x, fill_x);
+  return rc ? rc : vimpl<R>(v, av, sv, work_v, out_v, shape, ndim, outer, dt, 1, bc_y, fill_y);
 }
 
 // the squared shear / the Richardson number of the header as the stages of its chain over one (Z, Y, X) volume at a time,
@@ -1460,6 +1486,23 @@ int xg_richardson_number(int dtype, const void* b, const void* u, const void* v,
                              fill);
   }
   return fail(XG_ERR_INVALID, "richardson number: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+
+int xg_implicit_vertical_viscosity(int dtype, const void* u, const void* v, const void* nu, const int64_t* nus, const void* mfu,
+                                   const int64_t* mfus, const void* mcu, const int64_t* mcus, const void* mfv, const int64_t* mfvs,
+                                   const void* mcv, const int64_t* mcvs, void* work_u, void* work_v, void* out_u, void* out_v,
+                                   const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y,
+                                   double dt, void*) {
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(XG_ERR_INVALID, "implicit vertical viscosity: dt %g is negative or not finite", dt);
+  const void* const met[4] = {mfu, mcu, mfv, mcv};
+  const int64_t* const ms[4] = {mfus, mcus, mfvs, mcvs};
+  if (dtype == XG_T_F64)
+    return vvisc<double>((const double*)u, (const double*)v, (const double*)nu, nus, met, ms, (double*)work_u, (double*)work_v,
+                         (double*)out_u, (double*)out_v, shape, ndim, outer, bc_x, fill_x, bc_y, fill_y, dt);
+  if (dtype == XG_T_F32)
+    return vvisc<float>((const float*)u, (const float*)v, (const float*)nu, nus, met, ms, (float*)work_u, (float*)work_v,
+                        (float*)out_u, (float*)out_v, shape, ndim, outer, bc_x, (float)fill_x, bc_y, (float)fill_y, (float)dt);
+  return fail(XG_ERR_INVALID, "implicit vertical viscosity: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 
 int xg_convert(const void* src, int st, void* dst, int dt, uint64_t n, int via, double scale, int flags, void*) {

@@ -2076,6 +2076,192 @@ __global__ __launch_bounds__(BLOCK) void k_vimpl(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7o: implicit vertical viscosity of a C-grid velocity, K7m for u and for v with ONE viscosity nu at the centre points:
+//   u (COMP 0, at X:left):   kappa[k] = (nu[k, j, i-1] + nu[k, j, i]) * 0.5       interp_left_of, K7j's neighbour
+//   v (COMP 1, at Y:left):   kappa[k] = (nu[k, j-1, i] + nu[k, j, i]) * 0.5       op2<XG_OP_INTERP>, K7j's row below
+// formed in the coefficient stage of face k, everything after it K7m's recurrence in K7m's order (see there; no FMA).  nu is
+// padded left of column 0 / below row 0 (periodic: column nx-1 / row ny-1, extend: column 0 / row 0, fill: the fill value in
+// place of the loaded value); there is no pad along Z and faces 0 and nz are never read.  K7m's geometry: a wave owns one
+// (lead, Y segment, X tile) column set of ONE component -- the component is a template parameter and the launcher starts the
+// kernel once per component (both components in one wave would keep two sets of K7m's pipelined coefficients live).  u: nu
+// left of the lane's vector comes from the lane below by DPP where `ntl` bit 0 allows, the tile's first lane and the row's
+// edge load their own; v: the row below the segment is one more row per face (the segment before's last row: an L2 hit).
+// d goes into `out`, c into the workspace `cw`; every lane reads back only what it stored itself (no barrier, LDS or atomic),
+// so both are stored plainly and only the final store of x obeys `nt_store`.
+// float64 per component: a 8 + nu 8 + d out and back 16 + c out and back 16 + x 8 = 56 B/cell, 112 for both (nu read by each).
+// ------------------------------------------------------------------------------------------
+template <int V, int COMP, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_vvisc(
+    const real* __restrict__ a, real* __restrict__ cw, real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk, int64_t nz,
+    int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, real dt, int bc, real fill, VolIdx kp, VolIdx mf, VolIdx mc, int ntl) {
+  typedef typename VecT<V>::type T;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row, which this lane owns too)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = col + (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx + i0;
+  const T one = splat<T>(real(1)), tdt = splat<T>(dt);
+  // u: nu left of the lane's vector (periodic: column nx - 1, extend: column 0 itself); v: the row below the segment
+  // (periodic: row ny - 1 below row 0, extend: row 0 itself); a fill edge loads the clamped cell and replaces it
+  const LaneEdges e = lane_edges<V>(i0, nx, bc, ntl);
+  const bool fill_e = (COMP == 0 ? e.edge_l : j0 == 0) && bc == XG_BC_FILL;
+  const int64_t rb = j0 > 0 ? j0 - 1 : ((bc == XG_BC_PERIODIC) ? ny - 1 : 0);
+
+  // nu is loaded per face (it is a field of the faces); the two metrics per face / level only when they vary along Z, else
+  // once (and not at all for a column of one level, which has no face)
+  T kr[SEG], mfr[SEG], mcr[SEG];
+  int64_t mfo = 0, mco = 0;
+  const int64_t kpb = area_outer_off(kp.ai, o);                 // nu's (Z, Y, X) volume of this lead index
+  const int64_t kpo = kpb + j0 * kp.sy + i0 * kp.sx;
+  if (MET) {
+    if (mf.p) {
+      mfo = area_outer_off(mf.ai, o) + j0 * mf.sy + i0 * mf.sx;
+      if (mf.sz == 0 && nz > 1) load_rows<T, SEG>(mfr, mf.p, mfo, mf.sy, mf.sx, nrow, (ntl & 8) != 0);
+    }
+    if (mc.p) {
+      mco = area_outer_off(mc.ai, o) + j0 * mc.sy + i0 * mc.sx;
+      if (mc.sz == 0 && nz > 1) load_rows<T, SEG>(mcr, mc.p, mco, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
+    }
+  }
+  // w = w[k + 1] on return from coef(k) (k < nz-1), which needs w = w[k] on entry (k > 0): the coefficients of level k
+  T w[SEG];
+  auto coef = [&](int64_t k, T (&a_)[SEG], T (&lo_)[SEG], T (&up_)[SEG], T (&b_)[SEG]) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) a_[s_] = *reinterpret_cast<const T*>(a + ro[s_] + k * plane);
+    if (MET && nz > 1) {
+      if (mc.p && mc.sz != 0) load_rows<T, SEG>(mcr, mc.p, mco + k * mc.sz, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) b_[s_] = one;
+    if (k > 0) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        T l = w[s_];
+        if (MET) {
+          if (mc.p) l = l / mcr[s_];
+        }
+        lo_[s_] = l;
+        b_[s_] = b_[s_] + l;
+      }
+    }
+    if (k + 1 < nz) {
+      // face k + 1: nu's rows and its neighbour, every load before the first shuffle
+      const int64_t fz = (k + 1) * kp.sz;
+      load_rows<T, SEG>(kr, kp.p, kpo + fz, kp.sy, kp.sx, nrow, (ntl & 4) != 0);
+      T kap[SEG];
+      if (COMP == 0) {
+        real kl[SEG];
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_)
+          kl[s_] = e.own_l ? kp.p[kpb + fz + (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * kp.sy + e.lidx * kp.sx] : real(0);
+        if (e.shl) {
+#pragma unroll
+          for (int s_ = 0; s_ < SEG; ++s_) {
+            const real left = from_lane_below(vec_last(kr[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+            if (!e.own_l) kl[s_] = left;
+          }
+        }
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) kap[s_] = interp_left_of(kr[s_], fill_e ? fill : kl[s_]);
+      } else {
+        T kb[1];
+        load_rows<T, 1>(kb, kp.p, kpb + fz + rb * kp.sy + i0 * kp.sx, kp.sy, kp.sx, 1, (ntl & 4) != 0);
+        if (fill_e) kb[0] = splat<T>(fill);
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) kap[s_] = op2<XG_OP_INTERP>(s_ == 0 ? kb[0] : kr[(s_ > 0) ? s_ - 1 : 0], kr[s_]);
+      }
+      if (MET) {
+        if (mf.p && mf.sz != 0) load_rows<T, SEG>(mfr, mf.p, mfo + (k + 1) * mf.sz, mf.sy, mf.sx, nrow, (ntl & 8) != 0);
+      }
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        T g = kap[s_];
+        if (MET) {
+          if (mf.p) g = g / mfr[s_];
+        }
+        w[s_] = tdt * g;
+        T u = w[s_];
+        if (MET) {
+          if (mc.p) u = u / mcr[s_];
+        }
+        up_[s_] = u;
+        b_[s_] = b_[s_] + u;
+      }
+    }
+  };
+
+  // ---- forward: d into out, c into cw; the last level's d is x itself ----
+  T ac[SEG], lo[SEG], up[SEG], b[SEG], cp[SEG], dp[SEG];
+  coef(0, ac, lo, up, b);
+  for (int64_t k = 0; k < nz; ++k) {
+    const bool more = k + 1 < nz;
+    T an[SEG], lon[SEG], upn[SEG], bn[SEG];
+    if (more) coef(k + 1, an, lon, upn, bn);
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      T m = b[s_], d = ac[s_];
+      if (k > 0) {
+        m = m - lo[s_] * cp[s_];
+        d = d + lo[s_] * dp[s_];
+      }
+      const T r = one / m;
+      d = d * r;
+      dp[s_] = d;
+      if (more) {
+        cp[s_] = up[s_] * r;
+        if (s_ < nrow) {
+          stg<T, false>(out + ro[s_] + k * plane, d);
+          stg<T, false>(cw + ro[s_] + k * plane, cp[s_]);
+        }
+      } else if (s_ < nrow) {
+        stg_s<T, NTS>(out + ro[s_] + k * plane, d);
+      }
+    }
+    if (more) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        ac[s_] = an[s_];
+        lo[s_] = lon[s_];
+        up[s_] = upn[s_];
+        b[s_] = bn[s_];
+      }
+    }
+  }
+  if (nz < 2) return;
+
+  // ---- backward: x[k] = d[k] + c[k] * x[k+1], what this lane stored read back one level ahead of its use ----
+  T dk[SEG], ck[SEG];
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) {
+    dk[s_] = *reinterpret_cast<const T*>(out + ro[s_] + (nz - 2) * plane);
+    ck[s_] = *reinterpret_cast<const T*>(cw + ro[s_] + (nz - 2) * plane);
+  }
+  for (int64_t k = nz - 2; k >= 0; --k) {
+    T dn[SEG], cn[SEG];
+    if (k > 0) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        dn[s_] = *reinterpret_cast<const T*>(out + ro[s_] + (k - 1) * plane);
+        cn[s_] = *reinterpret_cast<const T*>(cw + ro[s_] + (k - 1) * plane);
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      dp[s_] = dk[s_] + ck[s_] * dp[s_];
+      if (s_ < nrow) stg_s<T, NTS>(out + ro[s_] + k * plane, dp[s_]);
+    }
+    if (k > 0) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        dk[s_] = dn[s_];
+        ck[s_] = cn[s_];
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // K7n: the squared vertical shear and the gradient Richardson number at the flux faces of Z in ONE pass over
 // (lead, Z, Y, X), two or three fields in, one out (nz faces at Z:left, nz + 1 at Z:outer):
 //   du[k] = (u[k] - u[k-1]) [/ mu[k]]    at u's points,     dv[k] = (v[k] - v[k-1]) [/ mv[k]]    at v's points
@@ -3094,6 +3280,94 @@ int xg_implicit_vertical_diffusion(int dtype, const void* a, const void* kappa, 
     return xg_internal_vimpl_f32((const float*)a, (const float*)kappa, kappa_strides, (const float*)mf, mf_strides,
                                  (const float*)mc, mc_strides, (float*)work, (float*)out, shape, ndim, outer, (float)dt, stream);
   return fail(XG_ERR_INVALID, "implicit vertical diffusion: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+
+// K7o's launcher: K7m's arguments twice -- u and v, a workspace and a result each, the metric of the flux and of the result at
+// u's and at v's points -- with ONE nu at the centre points of the faces and the boundaries that pad it along X and Y.  One
+// plan for both components (same shape; the lane width is NV only when all six field pointers are 16-byte aligned), one launch
+// per component.  One ABI entry for both element types (xg_implicit_vertical_viscosity, below).
+__attribute__((visibility("hidden"))) int xg_internal_vvisc_f64(
+    const double* u, const double* v, const double* nu, const int64_t* nu_strides, const double* const met[4],
+    const int64_t* const met_strides[4], double* work_u, double* work_v, double* out_u, double* out_v, const int64_t* shape,
+    int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, double dt, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_vvisc_f32(
+    const float* u, const float* v, const float* nu, const int64_t* nu_strides, const float* const met[4],
+    const int64_t* const met_strides[4], float* work_u, float* work_v, float* out_u, float* out_v, const int64_t* shape,
+    int ndim, int outer, int bc_x, float fill_x, int bc_y, float fill_y, float dt, void* stream);
+
+int XG_FN(xg_internal_vvisc)(const real* u, const real* v, const real* nu, const int64_t* nu_strides, const real* const met[4],
+                             const int64_t* const met_strides[4], real* work_u, real* work_v, real* out_u, real* out_v,
+                             const int64_t* shape, int ndim, int outer, int bc_x, real fill_x, int bc_y, real fill_y, real dt,
+                             void* stream) {
+  const char* name = "implicit vertical viscosity";
+  if (!u || !v || !nu || !out_u || !out_v || !work_u || !work_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (!nu_strides) return fail(XG_ERR_INVALID, "%s: a plane without strides", name);
+  for (int k = 0; k < 4; ++k)
+    if (met[k] && !met_strides[k]) return fail(XG_ERR_INVALID, "%s: a plane without strides", name);
+  FusedPlan p;
+  const bool al = aligned16(u) && aligned16(v) && aligned16(out_u) && aligned16(out_v) && aligned16(work_u) && aligned16(work_v);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  VolIdx ni, mi[4];  // nu; the metric of the flux and of the result at u's points, then at v's
+  if ((rc = vol_index(&ni, nu, nu_strides, shape, ndim))) return rc;
+  for (int k = 0; k < 4; ++k)
+    if ((rc = vol_index(&mi[k], met[k], met_strides[k], shape, ndim))) return rc;
+  auto vec = [&](const VolIdx& x) { return p.V > 1 && x.p && x.sz % NV == 0 && plane_vec_ok(x.p, x.ai, x.sy, x.sx); };
+  const real* fa[2] = {u, v};
+  real* fw[2] = {work_u, work_v};
+  real* fo[2] = {out_u, out_v};
+  const int fbc[2] = {bc_x, bc_y};
+  const real ffill[2] = {fill_x, fill_y};
+  for (int c = 0; c < 2; ++c) {
+    const VolIdx &mf = mi[2 * c], &mc = mi[2 * c + 1];
+    // bit 0: the lane neighbour by DPP (K7j; u only), bits 2 / 3 / 4: the rows of nu / the flux metric / the result's metric
+    // are aligned vectors
+    const int vnt = (c == 0 ? vec_nt_bits(1) : 0) | (vec(ni) ? 4 : 0) | (vec(mf) ? 8 : 0) | (vec(mc) ? 16 : 0);
+    const bool met_ = mf.p != nullptr || mc.p != nullptr;
+    rc = fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, C_, M_, NTS) do { hipLaunchKernelGGL((k_vvisc<V_, C_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, fa[c], fw[c], fo[c], o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, dt, fbc[c], ffill[c], ni, mf, mc, vnt); } while (0)
+#define XG_N(V_, C_, M_) do { if (p.nts) XG_GO(V_, C_, M_, true); else XG_GO(V_, C_, M_, false); } while (0)
+#define XG_M(V_, C_) do { if (met_) XG_N(V_, C_, true); else XG_N(V_, C_, false); } while (0)
+#define XG_V(V_) do { if (c == 0) XG_M(V_, 0); else XG_M(V_, 1); } while (0)
+      if (p.V > 1) XG_V(NV);
+      else XG_V(1);
+#undef XG_V
+#undef XG_M
+#undef XG_N
+#undef XG_GO
+    });
+    if (rc) return rc;
+  }
+  return XG_OK;
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument, dt and the fills are cast to it
+// here, once
+int xg_implicit_vertical_viscosity(int dtype, const void* u, const void* v, const void* nu, const int64_t* nu_strides,
+                                   const void* mfu, const int64_t* mfu_strides, const void* mcu, const int64_t* mcu_strides,
+                                   const void* mfv, const int64_t* mfv_strides, const void* mcv, const int64_t* mcv_strides,
+                                   void* work_u, void* work_v, void* out_u, void* out_v, const int64_t* shape, int ndim,
+                                   int outer, int bc_x, double fill_x, int bc_y, double fill_y, double dt, void* stream) {
+  if (!(dt >= 0.0) || !__builtin_isfinite(dt))
+    return fail(XG_ERR_INVALID, "implicit vertical viscosity: dt %g is negative or not finite", dt);
+  const int64_t* const ms[4] = {mfu_strides, mcu_strides, mfv_strides, mcv_strides};
+  if (dtype == XG_T_F64) {
+    const double* const mp[4] = {(const double*)mfu, (const double*)mcu, (const double*)mfv, (const double*)mcv};
+    return xg_internal_vvisc_f64((const double*)u, (const double*)v, (const double*)nu, nu_strides, mp, ms, (double*)work_u,
+                                 (double*)work_v, (double*)out_u, (double*)out_v, shape, ndim, outer, bc_x, fill_x, bc_y,
+                                 fill_y, dt, stream);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const mp[4] = {(const float*)mfu, (const float*)mcu, (const float*)mfv, (const float*)mcv};
+    return xg_internal_vvisc_f32((const float*)u, (const float*)v, (const float*)nu, nu_strides, mp, ms, (float*)work_u,
+                                 (float*)work_v, (float*)out_u, (float*)out_v, shape, ndim, outer, bc_x, (float)fill_x, bc_y,
+                                 (float)fill_y, (float)dt, stream);
+  }
+  return fail(XG_ERR_INVALID, "implicit vertical viscosity: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 #endif
 

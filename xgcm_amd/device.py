@@ -1374,6 +1374,41 @@ def implicit_vertical_diffusion(a, kappa, mf, mc, outer: bool, dt: float) -> tor
     return out
 
 
+def implicit_vertical_viscosity(u, v, nu, mfu, mcu, mfv, mcv, outer: bool, bc_x: str, bc_y: str, dt: float,
+                                fill_x: float = 0.0, fill_y: float = 0.0):
+    """Implicit vertical viscosity of a C-grid velocity in one pass (xg_implicit_vertical_viscosity): `implicit_vertical_diffusion`
+    of u and of v with the centre-point `nu` averaged to u's column, (nu[i-1] + nu[i]) * 0.5, and to v's, (nu[j-1] + nu[j]) *
+    0.5, inside the solve's coefficient stage.  `bc_x` / `fill_x` pad `nu` left of column 0, `bc_y` / `fill_y` below row 0.
+    `nu`, `mfu` and `mfv` (the metrics of the two fluxes; None = absent) broadcast against the flux' shape, which has the
+    fields' levels (`outer` False, Z:left) or one more (True, Z:outer); `mcu` and `mcv` against the fields'.  Returns
+    `(xu, xv)`.  The two workspaces of the forward sweeps are allocated here, per call: the library keeps no state."""
+    lib = _MEM.lib()
+    dt_, sfx = _common(u, v, nu, mfu, mcu, mfv, mcv)
+    u, v = asdevice(u, dt_), asdevice(v, dt_)
+    if u.dim() < 3:
+        raise ValueError("implicit_vertical_viscosity: the fields need (Z, Y, X) as their last three dims")
+    if v.shape != u.shape:
+        raise ValueError("implicit_vertical_viscosity: u and v must have the same shape")
+    if nu is None:
+        raise ValueError("implicit_vertical_viscosity: nu is required")
+    shape = list(u.shape)
+    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
+    nu, mfu, mcu, mfv, mcv = (_prep_metric(m, dt_) for m in (nu, mfu, mcu, mfv, mcv))
+    out_u, out_v = (_empty(shape, dtype=dt_, device=u.device) for _ in range(2))
+    if out_u.numel() == 0:
+        return out_u, out_v
+    work_u, work_v = (_empty(shape, dtype=dt_, device=u.device) for _ in range(2))
+    margs = []
+    for m, against, what in ((nu, fshape, "nu"), (mfu, fshape, "metric of u's flux"), (mcu, shape, "metric of u's result"),
+                             (mfv, fshape, "metric of v's flux"), (mcv, shape, "metric of v's result")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
+    _check(lib.xg_implicit_vertical_viscosity(_hip.DTYPE["float32" if sfx == "f32" else "float64"], u.data_ptr(), v.data_ptr(),
+                                              *margs, work_u.data_ptr(), work_v.data_ptr(), out_u.data_ptr(), out_v.data_ptr(),
+                                              _hip.i64(shape), len(shape), int(bool(outer)), _hip.BC[bc_x], float(fill_x),
+                                              _hip.BC[bc_y], float(fill_y), float(dt), _stream()))
+    return out_u, out_v
+
+
 def richardson_number(b, u, v, mu, mv, mb, outer: bool, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0,
                       fill_y: float = 0.0, fill_z: float = 0.0) -> torch.Tensor:
     """Fused gradient Richardson number at the faces of Z in one pass (xg_richardson_number): the differences of u, v and `b`

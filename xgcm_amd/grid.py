@@ -1957,6 +1957,99 @@ class Grid:
             res = DataArray(out, dims, coords={k: v for k, v in a.coords.items()}, name=a.name, attrs=a.attrs)
         return to_xarray(res) if was_xr else res
 
+    def implicit_vertical_viscosity(self, u, v, nu, dt=None, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", to=None,
+                                    padding=None, fill_value=None, metric_weighted: bool = True):
+        """Implicit (backward-Euler) vertical viscosity of a C-grid velocity with ONE viscosity `nu` at the centre points of
+        the faces of Z -- where `richardson_number` puts Ri and a closure its nu -- in ONE pass: the two averages of nu to
+        u's and to v's column are formed inside the coefficient stage of the two solves (MITgcm's implicit momentum mixing).
+        Returns `(xu, xv)`.  Bit-identical, dims, coords, name and attrs included, to the chain
+
+            kw   = dict(padding=padding, fill_value=fill_value)
+            nu_u = grid.interp(nu, x_axis, **kw)          # (Zf, YC, XC) -> (Zf, YC, XG): (nu[i-1] + nu[i]) * 0.5
+            nu_v = grid.interp(nu, y_axis, **kw)          # (Zf, YC, XC) -> (Zf, YG, XC): (nu[j-1] + nu[j]) * 0.5
+            xu   = grid.implicit_vertical_diffusion(u, nu_u, dt, z_axis=z_axis, to=to, metric_weighted=metric_weighted)
+            xv   = grid.implicit_vertical_diffusion(v, nu_v, dt, z_axis=z_axis, to=to, metric_weighted=metric_weighted)
+
+        which is four launches and two face-sized temporaries.  See `implicit_vertical_diffusion` for the solve: the
+        recurrence, its order, the insulated top and bottom (no pad along Z; faces 0 and n of `nu` are never read).
+
+        u at (lead, Z:center, Y:center, X:left), v at (lead, Z:center, Y:left, X:center), the same shape and the same
+        float32 or float64 dtype, Z third from last.  `nu` in that dtype at (Zf, Y:center, X:center), Zf the flux position
+        `to` ("left" or "outer"; None: "outer" when the Z axis has one, else "left"), with any subset of the leading dims
+        in any order: it is read through broadcast strides, never materialised.  `padding` and `fill_value` pad `nu` only,
+        left of column 0 and below row 0 (periodic: column nx-1 / row ny-1, extend: column 0 / row 0, fill: the fill value
+        cast to the dtype, a -0.0 or a NaN keeping its bits); X and Y may differ.  The metrics are whatever `get_metric`
+        returns along Z at u's flux dims, u's dims, v's flux dims and v's dims, one broadcast array each;
+        `metric_weighted=False` drops all four.  `xu` carries u's dims, coords, name and attrs, `xv` v's; xarray in gives
+        xarray out, host in host out, a tensor among u, v, nu HBM out.
+
+        The chain itself runs (the same calls in the same order, raising what it raises) for `nu` None, for another dtype or
+        mixed dtypes, for u or v elsewhere or of different shapes, for a `nu` not at (Zf, Y:center, X:center), lacking one
+        of the three dims or with a dim the fields lack, for Z not third from last, for chunked inputs or chunked metrics,
+        for a metric with dims its stage lacks, for a metric lookup that raises, for a missing X or Y boundary, and with
+        face connections or a fold along any of the three axes.
+
+        Raises, before any work, TypeError for a missing `dt` and ValueError for a `dt` negative, NaN or infinite, as
+        `implicit_vertical_diffusion` does."""
+        what = "implicit_vertical_viscosity"
+        args, to_arg = (u, v, nu), to
+        (u, xr1), (v, xr2), (nu, xr3) = (self._wrap_in(a) for a in args)
+        if dt is None:
+            raise TypeError(f"{what}: dt, the time step, is required")
+        dt = float(dt)
+        if not (dt >= 0.0 and np.isfinite(dt)):
+            raise ValueError(f"{what}: dt must be finite and not negative, got {dt}")
+        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
+        if to is None:
+            to = "outer" if "outer" in zax.coords else "left"
+        plan = None
+        served = (all(isinstance(f, DataArray) for f in (u, v, nu)) and u.ndim >= 3 and to in ("left", "outer") and to in zax.coords
+                  and all("center" in ax.coords for ax in (zax, yax, xax)) and "left" in yax.coords and "left" in xax.coords
+                  and not gridops.complex_topology(self, z_axis) and not _is_chunked(nu.data))
+        mets = [None] * 4
+        if served:
+            tz, zf = zax.coords["center"], zax.coords[to]
+            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            lead = u.dims[:-3]
+            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
+            nu_dims = lead + (zf, yc, xc)   # the dims nu is read at: those of `lead` it lacks are broadcast
+            f_shape = tuple(u.shape[:-3]) + (u.shape[-3] + (1 if to == "outer" else 0),) + tuple(u.shape[-2:])
+            served = (u.dims == lead + (tz, yc, xl) and v.dims == lead + (tz, yl, xc) and not held & set(lead)
+                      and {zf, yc, xc} <= set(nu.dims) <= set(nu_dims) and len(set(nu.dims)) == nu.ndim
+                      and all(nu.sizes[d] == n for d, n in zip(nu_dims, f_shape) if d in nu.dims))
+        if served:
+            # the stages of the two solves: u's flux, u's result, v's flux, v's result
+            m_dims = [lead + (zf, yc, xl), u.dims, lead + (zf, yl, xc), v.dims]
+            try:
+                if metric_weighted:
+                    for k, f in enumerate((u, u, v, v)):
+                        mets[k] = self._resident(self.get_metric(_DimsOnly(m_dims[k], f.name), (z_axis,), _layout=m_dims[k]), u.data)
+                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, m_dims))
+            except (KeyError, ValueError):
+                served = False  # (the chain raises it where the chain looks the metric up)
+        if served:
+            plan = self._second_order_plan([u, v], x_axis, y_axis, padding, fill_value, [nu] + [m for m in mets if m is not None])
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            u, v, nu = args
+            nu_u = self.interp(nu, x_axis, **kw)
+            nu_v = self.interp(nu, y_axis, **kw)
+            xu = self.implicit_vertical_diffusion(u, nu_u, dt, z_axis=z_axis, to=to_arg, metric_weighted=metric_weighted)
+            xv = self.implicit_vertical_diffusion(v, nu_v, dt, z_axis=z_axis, to=to_arg, metric_weighted=metric_weighted)
+            return xu, xv
+        bcx, bcy = plan[0], plan[1]
+        # the one-axis operators of the chain hand their fill value on as it is (None: 0.0): a -0.0 or a NaN keeps its bits
+        fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
+        fvx, fvy = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis))
+        host = not any(_is_tensor(f.data) for f in (u, v, nu))
+        ou, ov = _dev.implicit_vertical_viscosity(u.data, v.data, _aligned_view(nu, nu_dims),
+                                                  *(None if m is None else _aligned_view(m, dims) for m, dims in zip(mets, m_dims)),
+                                                  to == "outer", bcx, bcy, dt, fvx, fvy)
+        xu = u._replace(data=_dev.tohost(ou) if host else ou)
+        xv = v._replace(data=_dev.tohost(ov) if host else ov)
+        # (the chain's nu_u / nu_v are xarray objects when nu is one, and so is each result whose field or nu is one)
+        return (to_xarray(xu) if xr1 or xr3 else xu), (to_xarray(xv) if xr2 or xr3 else xv)
+
     def vertical_shear_squared(self, u, v, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", to=None, padding=None,
                                fill_value=None, metric_weighted: bool = True):
         """Squared vertical shear of a C-grid velocity, S2 = (du/dz)^2 + (dv/dz)^2, at the cell centre on the flux faces of
