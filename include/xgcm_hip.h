@@ -51,6 +51,8 @@
  *   xg_implicit_vertical_viscosity  that solve for u and for v with one centre-point nu averaged to their columns, one pass
  *   xg_richardson_number  derivative(b, Z) / (interp(derivative(u, Z), X)^2 + interp(derivative(v, Z), Y)^2) at the faces of Z,
  *                      or the squared shear alone, one pass (one entry likewise)
+ *   xg_richardson_mixing  the Pacanowski-Philander closure on that Richardson number: nu and kappa at the faces of Z from
+ *                      b, u and v, one pass (one entry likewise)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -507,6 +509,19 @@ int xg_implicit_vertical_viscosity(int dtype, const void* u, const void* v, cons
  * metric without strides, outer not 0 or 1, an unknown boundary code, nz = 0. */
 int xg_richardson_number(int dtype, const void* b, const void* u, const void* v, const void* mu, const int64_t* mu_strides,
                          const void* mv, const int64_t* mv_strides, const void* mb, const int64_t* mb_strides, void* out,
+                         const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
+                         double fill_z, void* stream);
+/* The Pacanowski-Philander (1981) mixing coefficients at the faces of Z, one pass: xg_richardson_number's N2 and S2 (its
+ * arrays, positions, pads, metrics and order of operations; b is required), then, per face,
+ *   ri = N2 / (S2 + shear_floor)      rp = (ri + |ri|) * 0.5      den = 1 + alpha * rp
+ *   nu = nu0 / (den * den) + nu_b     kappa = nu / den + kappa_b
+ * in this order, no fused multiply-add, IEEE quotients.  rp is max(ri, 0) for every finite ri (+0.0 for -0.0), NaN for a NaN
+ * and for -inf.  The five scalars and the fills are cast to the element type once.  `out_nu` and `out_kappa` have
+ * xg_richardson_number's `out` shape each and may not overlap.  XG_ERR_INVALID: a NULL b, u, v, out_nu, out_kappa or shape,
+ * a metric without strides, outer not 0 or 1, an unknown boundary code, nz = 0. */
+int xg_richardson_mixing(int dtype, const void* b, const void* u, const void* v, const void* mu, const int64_t* mu_strides,
+                         const void* mv, const int64_t* mv_strides, const void* mb, const int64_t* mb_strides, double nu0,
+                         double alpha, double nu_b, double kappa_b, double shear_floor, void* out_nu, void* out_kappa,
                          const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
                          double fill_z, void* stream);
 

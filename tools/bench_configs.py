@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only; 5pp: richardson_mixing against its chain, alone only), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -292,6 +292,49 @@ def run_richardson_number(reps, nz=90, n=4320):
     rec(5, "richardson_number as its chain (9 launches), fused-equivalent bytes", med(tc), cells, bpc)
     print(json.dumps({"config": 5, "check": "fused richardson_number == chain bit for bit at full size", "ok": ok,
                       "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
+                      "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_richardson_mixing(reps, nz=90, n=4320):
+    """richardson_mixing in one pass against its chain (vertical_shear_squared, itself one pass, the derivative of b and the
+    closure as twelve launches of array arithmetic; a profile drC(Zp1); periodic / extend / extend, to="outer", a shear floor
+    of 2^-10 so that the outermost faces are finite), timed in turns, every paired round reported.  Fields 40 GB, the two
+    results 27 GB, the chain's live temporaries about 110 GB: some 180 GB at the peak of the comparison."""
+    coords = {"XC": ("XC", np.arange(n) + 0.5), "XG": ("XG", np.arange(n) * 1.0), "YC": ("YC", np.arange(n) + 0.5),
+              "YG": ("YG", np.arange(n) * 1.0), "Z": ("Z", np.arange(nz) + 0.5), "Zp1": ("Zp1", np.arange(nz + 1) * 1.0)}
+    ds = Dataset({"drC": DataArray(D.synthetic((nz + 1,), 34, 0, 10.0, 10.0), ("Zp1",))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                            "Z": {"center": "Z", "outer": "Zp1"}},
+                padding={"X": "periodic", "Y": "extend", "Z": "extend"}, metrics={("Z",): ["drC"]}, autoparse_metadata=False)
+    B = DataArray(D.synthetic((nz, n, n), 63), ("Z", "YC", "XC"))
+    U = DataArray(D.synthetic((nz, n, n), 51), ("Z", "YC", "XG"))
+    V = DataArray(D.synthetic((nz, n, n), 52), ("Z", "YG", "XC"))
+    cells = nz * n * n
+    nu0, alpha, nu_b, kappa_b, floor = 5e-3, 5.0, 1e-4, 1e-5, 2.0 ** -10
+
+    def chain():
+        s2 = grid.vertical_shear_squared(U, V, to="outer")
+        n2 = grid.derivative(B, "Z", to="outer")
+        ri = n2 / (s2 + floor)
+        rp = (ri + abs(ri)) * 0.5
+        den = 1.0 + alpha * rp
+        nu = nu0 / (den * den) + nu_b
+        return nu, nu / den + kappa_b
+
+    one = lambda: grid.richardson_mixing(B, U, V, nu0, alpha, nu_b, kappa_b, floor, to="outer")  # noqa: E731
+    got, want = one(), chain()
+    ok = all(bool(torch.equal(g.data.view(torch.int64), w.data.view(torch.int64))) for g, w in zip(got, want))   # (the bits)
+    finite = all(bool(torch.isfinite(g.data).all()) for g in got)
+    del got, want
+    torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(one, chain, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    bpc = 40   # b, u, v, nu and kappa (the 91st face of the results is not counted)
+    rec(5, "richardson_mixing one pass: nu, kappa of the Pacanowski-Philander closure from b, u, v, to=outer, drC(Zp1), extend: 3 reads + 2 writes", med(tf), cells, bpc)
+    rec(5, "richardson_mixing as its chain (vertical_shear_squared + derivative + 12 launches of arithmetic), one-pass-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": "one-pass richardson_mixing == chain bit for bit at full size, both results", "ok": ok,
+                      "results_finite": finite, "speedup": round(med(tc) / med(tf), 2), "rounds_ms_fused": [round(t, 3) for t in tf],
                       "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
 
@@ -990,6 +1033,8 @@ def main():
         run_richardson_number(a.reps)
     if "5vv" in cfgs:   # (not part of 5x: about 120 GB)
         run_implicit_vertical_viscosity(a.reps, *(shp or (90, 4320, 4320)))
+    if "5pp" in cfgs:   # (not part of 5x: about 180 GB)
+        run_richardson_mixing(a.reps)
     ranks.close()
 
 

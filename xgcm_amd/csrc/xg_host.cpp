@@ -850,20 +850,24 @@ int vvisc(const R* u, const R* v, const R* nu, const int64_t* nus, const void* c
 // the squared shear / the Richardson number of the header as the stages of its chain over one (Z, Y, X) volume at a time,
 // each into a temporary: the three differences along Z at the faces (nz of them, `outer`: nz + 1) over their metrics, the
 // two means to the centre with the pad of the DIFFERENCES right of the last column / above the last row, the squares,
-// their sum, the quotient.  arr[] = {the metric at u's points, at v's points, at the centre}; b NULL: the squared shear
+// their sum, the quotient.  arr[] = {the metric at u's points, at v's points, at the centre}; b NULL: the squared shear.
+// `clo` = {nu0, alpha, nu_b, kappa_b, shear_floor}: the Pacanowski-Philander closure on that quotient as its own stages, nu
+// into `out` and kappa into `out_kappa` (xg_richardson_mixing)
 template <typename R>
 int richardson(const R* b, const R* u, const R* v, const R* const arr_in[3], const int64_t* const st[3], R* out,
-               const int64_t* shape, int ndim, int outer, const int bc[3], const R fill[3]) {  // bc, fill: X, Y, Z
-  if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "ndim %d not in [3,%d]", ndim, XG_MAX_NDIM);
+               const int64_t* shape, int ndim, int outer, const int bc[3], const R fill[3],  // bc, fill: X, Y, Z
+               const R* clo = nullptr, R* out_kappa = nullptr) {
+  const char* name = clo ? "richardson mixing" : "richardson number";
+  if (!u || !v || !out || !shape || (clo && (!b || !out_kappa))) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "%s: ndim %d not in [3,%d]", name, ndim, XG_MAX_NDIM);
   for (int k = 0; k < 3; ++k)
-    if (bc[k] < XG_BC_PERIODIC || bc[k] > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "boundary mode %d: periodic, fill or extend", bc[k]);
-  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "outer %d is neither 0 (left) nor 1", outer);
+    if (bc[k] < XG_BC_PERIODIC || bc[k] > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "%s: boundary mode %d: periodic, fill or extend", name, bc[k]);
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
   const R* arr[3] = {arr_in[0], arr_in[1], b ? arr_in[2] : nullptr};
   for (int k = 0; k < 3; ++k)
-    if (arr[k] && !st[k]) return fail(XG_ERR_INVALID, "metric without strides");
+    if (arr[k] && !st[k]) return fail(XG_ERR_INVALID, "%s: metric without strides", name);
   const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx, vol = nz * plane;
-  if (nz == 0) return fail(XG_ERR_INVALID, "richardson number: no level along Z");
+  if (nz == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
   const int64_t nf = nz + outer;  // faces
   int64_t lead = 1;
   for (int d = 0; d < ndim - 3; ++d) lead *= shape[d];
@@ -919,7 +923,16 @@ int richardson(const R* b, const R* u, const R* v, const R* const arr_in[3], con
     for (int64_t c = 0; c < nf * plane; ++c) {
       const R a2 = uz[c] * uz[c], b2 = vz[c] * vz[c];
       const R s2 = a2 + b2;
-      po[c] = b ? d[2][c] / s2 : s2;
+      if (!clo) {
+        po[c] = b ? d[2][c] / s2 : s2;
+        continue;
+      }
+      const R ri = d[2][c] / (s2 + clo[4]);
+      const R rp = (ri + std::fabs(ri)) * R(0.5);
+      const R den = R(1) + clo[1] * rp;
+      const R nu = clo[0] / (den * den) + clo[2];
+      po[c] = nu;
+      out_kappa[o * nf * plane + c] = nu / den + clo[3];
     }
   }
   return XG_OK;
@@ -1503,6 +1516,29 @@ int xg_implicit_vertical_viscosity(int dtype, const void* u, const void* v, cons
     return vvisc<float>((const float*)u, (const float*)v, (const float*)nu, nus, met, ms, (float*)work_u, (float*)work_v,
                         (float*)out_u, (float*)out_v, shape, ndim, outer, bc_x, (float)fill_x, bc_y, (float)fill_y, (float)dt);
   return fail(XG_ERR_INVALID, "implicit vertical viscosity: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+
+int xg_richardson_mixing(int dtype, const void* b, const void* u, const void* v, const void* mu, const int64_t* mus,
+                         const void* mv, const int64_t* mvs, const void* mb, const int64_t* mbs, double nu0, double alpha,
+                         double nu_b, double kappa_b, double shear_floor, void* out_nu, void* out_kappa, const int64_t* shape,
+                         int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void*) {
+  const int64_t* const st[3] = {mus, mvs, mbs};
+  const int bc[3] = {bc_x, bc_y, bc_z};
+  if (!b || !out_nu || !out_kappa) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (dtype == XG_T_F64) {
+    const double* const arr[3] = {(const double*)mu, (const double*)mv, (const double*)mb};
+    const double fill[3] = {fill_x, fill_y, fill_z}, clo[5] = {nu0, alpha, nu_b, kappa_b, shear_floor};
+    return richardson<double>((const double*)b, (const double*)u, (const double*)v, arr, st, (double*)out_nu, shape, ndim,
+                              outer, bc, fill, clo, (double*)out_kappa);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const arr[3] = {(const float*)mu, (const float*)mv, (const float*)mb};
+    const float fill[3] = {(float)fill_x, (float)fill_y, (float)fill_z};
+    const float clo[5] = {(float)nu0, (float)alpha, (float)nu_b, (float)kappa_b, (float)shear_floor};
+    return richardson<float>((const float*)b, (const float*)u, (const float*)v, arr, st, (float*)out_nu, shape, ndim, outer, bc,
+                             fill, clo, (float*)out_kappa);
+  }
+  return fail(XG_ERR_INVALID, "richardson mixing: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 
 int xg_convert(const void* src, int st, void* dst, int dt, uint64_t n, int via, double scale, int flags, void*) {

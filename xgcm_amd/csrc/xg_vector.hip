@@ -2280,6 +2280,8 @@ __global__ __launch_bounds__(BLOCK) void k_vvisc(
 // u's points, at v's points, at the centre, all at the faces) are one broadcast array each, each may be absent; rows that
 // do not vary along Z are loaded once per wave.  Periodic Z costs one more level read before the march (and, `outer`, one
 // after it).
+// K7p (k_rimix, below) is a COPY of this kernel up to N2 and S2 -- fetch, padded, metrics, face, the march -- with another
+// epilogue: whatever is fixed or changed in the march here has to be made there too.
 // ------------------------------------------------------------------------------------------
 template <typename T, int SEG>
 struct RiLevel {  // what one level of a column brings: SEG rows of u and b, SEG + 1 rows of v, u right of the lane
@@ -2420,6 +2422,172 @@ __global__ __launch_bounds__(BLOCK) void k_richardson(
           z = db / z;
         }
         stg_s<T, NTS>(po + k * plane + s_ * nx, z);
+      }
+    }
+  };
+
+  // face 0 lies between the pad above level 0 and level 0; the march keeps the level above the face
+  L cur = fetch(0), prev;
+  if (bc_z == XG_BC_PERIODIC) prev = fetch(nz - 1);
+  else if (bc_z == XG_BC_EXTEND) prev = cur;
+  else prev = padded();
+  for (int64_t k = 0;;) {
+    face(k, prev, cur);
+    if (++k >= nf) break;
+    prev = cur;
+    if (k < nz) cur = fetch(k);                           // (`outer`, the last face: the pad below level nz-1 --
+    else if (bc_z == XG_BC_PERIODIC) cur = fetch(0);      //  extend: the level itself, which `cur` still holds)
+    else if (bc_z == XG_BC_FILL) cur = padded();
+    if (MET) metrics(k, false);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// K7p: the Pacanowski-Philander (1981) mixing coefficients at the flux faces of Z in ONE pass over (lead, Z, Y, X), three
+// fields in, two out (nz faces at Z:left, nz + 1 at Z:outer): K7n's N2 and S2, line by line in its order, then the closure
+//   ri = N2 / (S2 + shear_floor)      rp = (ri + |ri|) * 0.5      den = 1 + alpha * rp
+//   nu = nu0 / (den * den) + nu_b     kappa = nu / den + kappa_b                                  (no FMA, IEEE quotients)
+// as the epilogue of every face, and two stores.  rp is max(ri, 0) for every finite ri (+0.0 for -0.0); a NaN stays one,
+// -inf gives NaN.  K7n's march, neighbours, pads and metrics unchanged: b, u and v are read once and each result written
+// once, 40 B/cell in float64.  The five scalars arrive in `real`.
+// ------------------------------------------------------------------------------------------
+struct RimixScalars {
+  real nu0, alpha, nu_b, kappa_b, floor;
+};
+
+template <int V, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_rimix(
+    const real* __restrict__ b, const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ out_nu,
+    real* __restrict__ out_kappa, int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile,
+    FastDiv nseg, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mu, VolIdx mv,
+    VolIdx mb, int ntl, RimixScalars c) {
+  typedef typename VecT<V>::type T;
+  typedef RiLevel<T, SEG> L;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  const int64_t nf = nz + outer;       // faces
+  // X and Y as K7n's: the column right of the lane's vector, the row above the segment; a fill edge replaces the value
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);  // (the right side only)
+  const bool fill_r = e.edge_r && bc_x == XG_BC_FILL;
+  const int64_t q = j0 + nrow;
+  const bool fill_t = q >= ny && bc_y == XG_BC_FILL;
+  const int64_t jt = (q < ny) ? q : ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1);  // the row the top derivative is formed at
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+
+  auto fetch = [&](int64_t k) -> L {
+    L x;
+    const int64_t lv = col + k * plane;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.uu[s_] = *reinterpret_cast<const T*>(u + lv + ro[s_] + i0);
+      x.ur[s_] = e.own_r ? u[lv + ro[s_] + e.ridx] : real(0);
+      x.vv[s_] = *reinterpret_cast<const T*>(v + lv + ro[s_] + i0);
+      x.bb[s_] = *reinterpret_cast<const T*>(b + lv + ro[s_] + i0);
+    }
+    x.vv[SEG] = *reinterpret_cast<const T*>(v + lv + jt * nx + i0);
+    return x;
+  };
+  auto padded = [&]() -> L {  // a level of the fill value
+    L x;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.uu[s_] = x.vv[s_] = x.bb[s_] = splat<T>(fill_z);
+      x.ur[s_] = fill_z;
+    }
+    x.vv[SEG] = splat<T>(fill_z);
+    return x;
+  };
+
+  // the metric rows of a face, as K7n holds them
+  T mur[SEG], mvr[SEG + 1], mbr[SEG];
+  real mrr[SEG];
+  int64_t muo = 0, mro = 0, mvo = 0, mto = 0, mbo = 0;
+  auto metrics = [&](int64_t k, bool first) {
+    if (mu.p && (first || mu.sz != 0)) {
+      load_rows<T, SEG>(mur, mu.p, muo + k * mu.sz, mu.sy, mu.sx, nrow, (ntl & 4) != 0);
+      if (e.own_r) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) mrr[s_] = mu.p[mro + k * mu.sz + ((s_ < nrow) ? s_ : nrow - 1) * mu.sy];
+      }
+    }
+    if (mv.p && (first || mv.sz != 0)) {
+      T rows[SEG];
+      load_rows<T, SEG>(rows, mv.p, mvo + k * mv.sz, mv.sy, mv.sx, nrow, (ntl & 8) != 0);
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) mvr[s_] = rows[s_];
+      T top[1];
+      load_rows<T, 1>(top, mv.p, mto + k * mv.sz, mv.sy, mv.sx, 1, (ntl & 8) != 0);
+      mvr[SEG] = top[0];
+    }
+    if (mb.p && (first || mb.sz != 0)) load_rows<T, SEG>(mbr, mb.p, mbo + k * mb.sz, mb.sy, mb.sx, nrow, (ntl & 16) != 0);
+  };
+  if (MET) {
+    const int64_t uo = mu.p ? area_outer_off(mu.ai, o) : 0, vo = mv.p ? area_outer_off(mv.ai, o) : 0;
+    muo = uo + j0 * mu.sy + i0 * mu.sx;
+    mro = uo + j0 * mu.sy + e.ridx * mu.sx;
+    mvo = vo + j0 * mv.sy + i0 * mv.sx;
+    mto = vo + jt * mv.sy + i0 * mv.sx;
+    if (mb.p) mbo = area_outer_off(mb.ai, o) + j0 * mb.sy + i0 * mb.sx;
+    metrics(0, true);
+  }
+
+  // one face from the level above it (`lo`) and the level below it (`hi`)
+  const int64_t po = o * nf * plane + j0 * nx + i0;
+  const T one = splat<T>(real(1)), half = splat<T>(real(0.5));
+  auto face = [&](int64_t k, const L& lo, const L& hi) {
+    T du[SEG], dv[SEG + 1];
+    real dr[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      du[s_] = op2<XG_OP_DIFF>(lo.uu[s_], hi.uu[s_]);
+      dr[s_] = hi.ur[s_] - lo.ur[s_];
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG + 1; ++s_) dv[s_] = op2<XG_OP_DIFF>(lo.vv[s_], hi.vv[s_]);
+    if (MET) {
+      if (mu.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) du[s_] = du[s_] / mur[s_];
+        if (e.own_r) {
+#pragma unroll
+          for (int s_ = 0; s_ < SEG; ++s_) dr[s_] = dr[s_] / mrr[s_];
+        }
+      }
+      if (mv.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG + 1; ++s_) dv[s_] = dv[s_] / mvr[s_];
+      }
+    }
+    if (e.shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real right = from_lane_above(vec_first(du[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+        if (!e.own_r) dr[s_] = right;
+      }
+    }
+    const T top = fill_t ? splat<T>(fill_y) : dv[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        const T uz = interp_right_of(du[s_], fill_r ? fill_x : dr[s_]);
+        const T vz = op2<XG_OP_INTERP>(dv[s_], (s_ + 1 < nrow) ? dv[s_ + 1] : top);
+        const T s2 = uz * uz + vz * vz;
+        T db = op2<XG_OP_DIFF>(lo.bb[s_], hi.bb[s_]);
+        if (MET) {
+          if (mb.p) db = db / mbr[s_];
+        }
+        // the closure, one operation per line of the chain
+        const T ri = db / (s2 + splat<T>(c.floor));
+        const T rp = (ri + __builtin_elementwise_abs(ri)) * half;
+        const T den = one + splat<T>(c.alpha) * rp;
+        const T nu = splat<T>(c.nu0) / (den * den) + splat<T>(c.nu_b);
+        const T ka = nu / den + splat<T>(c.kappa_b);
+        const int64_t at = po + k * plane + s_ * nx;
+        stg_s<T, NTS>(out_nu + at, nu);
+        stg_s<T, NTS>(out_kappa + at, ka);
       }
     }
   };
@@ -3436,6 +3604,78 @@ int xg_richardson_number(int dtype, const void* b, const void* u, const void* v,
                                       (const float*)mv, mv_strides, (const float*)mb, mb_strides, (float*)out, shape, ndim,
                                       outer, bc_x, (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
   return fail(XG_ERR_INVALID, "richardson number: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+
+// K7p's launcher: K7n's with b required, the closure's five scalars in `real` and two results.  One ABI entry for both
+// element types (xg_richardson_mixing, below).
+__attribute__((visibility("hidden"))) int xg_internal_rimix_f64(
+    const double* b, const double* u, const double* v, const double* mu, const int64_t* mu_strides, const double* mv,
+    const int64_t* mv_strides, const double* mb, const int64_t* mb_strides, double nu0, double alpha, double nu_b,
+    double kappa_b, double shear_floor, double* out_nu, double* out_kappa, const int64_t* shape, int ndim, int outer,
+    int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_rimix_f32(
+    const float* b, const float* u, const float* v, const float* mu, const int64_t* mu_strides, const float* mv,
+    const int64_t* mv_strides, const float* mb, const int64_t* mb_strides, float nu0, float alpha, float nu_b, float kappa_b,
+    float shear_floor, float* out_nu, float* out_kappa, const int64_t* shape, int ndim, int outer, int bc_x, float fill_x,
+    int bc_y, float fill_y, int bc_z, float fill_z, void* stream);
+
+int XG_FN(xg_internal_rimix)(const real* b, const real* u, const real* v, const real* mu, const int64_t* mu_strides,
+                             const real* mv, const int64_t* mv_strides, const real* mb, const int64_t* mb_strides, real nu0,
+                             real alpha, real nu_b, real kappa_b, real shear_floor, real* out_nu, real* out_kappa,
+                             const int64_t* shape, int ndim, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
+                             real fill_z, void* stream) {
+  const char* name = "richardson mixing";
+  if (!b || !u || !v || !out_nu || !out_kappa || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  FusedPlan p;
+  const bool al = aligned16(u) && aligned16(v) && aligned16(b) && aligned16(out_nu) && aligned16(out_kappa);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  VolIdx mi[3];  // the Z metric at u's points, at v's points, at the centre
+  const real* mp[3] = {mu, mv, mb};
+  const int64_t* ms[3] = {mu_strides, mv_strides, mb_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  // bit 0: the lane neighbour by DPP (K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
+  int vnt = vec_nt_bits(1);
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool met = mu != nullptr || mv != nullptr || mb != nullptr;
+  const RimixScalars c = {nu0, alpha, nu_b, kappa_b, shear_floor};
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_rimix<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, u, v, out_nu, out_kappa, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt, c); } while (0)
+#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument, the fills and the closure's
+// scalars are cast to it here
+int xg_richardson_mixing(int dtype, const void* b, const void* u, const void* v, const void* mu, const int64_t* mu_strides,
+                         const void* mv, const int64_t* mv_strides, const void* mb, const int64_t* mb_strides, double nu0,
+                         double alpha, double nu_b, double kappa_b, double shear_floor, void* out_nu, void* out_kappa,
+                         const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
+                         double fill_z, void* stream) {
+  if (dtype == XG_T_F64)
+    return xg_internal_rimix_f64((const double*)b, (const double*)u, (const double*)v, (const double*)mu, mu_strides,
+                                 (const double*)mv, mv_strides, (const double*)mb, mb_strides, nu0, alpha, nu_b, kappa_b,
+                                 shear_floor, (double*)out_nu, (double*)out_kappa, shape, ndim, outer, bc_x, fill_x, bc_y,
+                                 fill_y, bc_z, fill_z, stream);
+  if (dtype == XG_T_F32)
+    return xg_internal_rimix_f32((const float*)b, (const float*)u, (const float*)v, (const float*)mu, mu_strides,
+                                 (const float*)mv, mv_strides, (const float*)mb, mb_strides, (float)nu0, (float)alpha,
+                                 (float)nu_b, (float)kappa_b, (float)shear_floor, (float*)out_nu, (float*)out_kappa, shape,
+                                 ndim, outer, bc_x, (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
+  return fail(XG_ERR_INVALID, "richardson mixing: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 #endif
 

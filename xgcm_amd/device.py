@@ -1439,6 +1439,37 @@ def richardson_number(b, u, v, mu, mv, mb, outer: bool, bc_x: str, bc_y: str, bc
     return out
 
 
+def richardson_mixing(b, u, v, mu, mv, mb, nu0: float, alpha: float, nu_b: float, kappa_b: float, shear_floor: float,
+                      outer: bool, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0, fill_y: float = 0.0,
+                      fill_z: float = 0.0):
+    """Fused Pacanowski-Philander mixing coefficients at the faces of Z in one pass (xg_richardson_mixing): N2 and S2 as
+    `richardson_number` forms them from `b`, `u`, `v` and the metrics, then ri = N2 / (S2 + shear_floor),
+    rp = (ri + |ri|) * 0.5, den = 1 + alpha * rp, nu = nu0 / (den * den) + nu_b, kappa = nu / den + kappa_b.  The five
+    scalars are cast to the fields' dtype once.  Returns (nu, kappa), two tensors of `richardson_number`'s result shape."""
+    lib = _MEM.lib()
+    dt, sfx = _common(u, v, b, mu, mv, mb)
+    b, u, v = asdevice(b, dt), asdevice(u, dt), asdevice(v, dt)
+    if u.dim() < 3 or u.shape[-3] == 0:
+        raise ValueError("richardson_mixing: the fields need (Z, Y, X) as their last three dims and a level along Z")
+    if v.shape != u.shape or b.shape != u.shape:
+        raise ValueError("richardson_mixing: u, v and b must have the same shape")
+    shape = list(u.shape)
+    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
+    mets = [_prep_metric(m, dt) for m in (mu, mv, mb)]
+    nu, kappa = _empty(fshape, dtype=dt, device=u.device), _empty(fshape, dtype=dt, device=u.device)
+    if nu.numel() == 0:
+        return nu, kappa
+    margs = []
+    for m, what in zip(mets, ("metric at u's points", "metric at v's points", "metric at the centre")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, fshape, what))]
+    _check(lib.xg_richardson_mixing(_hip.DTYPE["float32" if sfx == "f32" else "float64"], b.data_ptr(), u.data_ptr(),
+                                    v.data_ptr(), *margs, float(nu0), float(alpha), float(nu_b), float(kappa_b),
+                                    float(shear_floor), nu.data_ptr(), kappa.data_ptr(), _hip.i64(shape), len(shape),
+                                    int(bool(outer)), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z],
+                                    float(fill_z), _stream()))
+    return nu, kappa
+
+
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""

@@ -2102,8 +2102,50 @@ class Grid:
         level along Z, and with face connections or a fold along any of the three axes."""
         return self._richardson(b, u, v, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted)
 
-    def _richardson(self, b, u, v, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted):
-        """`richardson_number`, or with b None `vertical_shear_squared`: one launch of K7n, or their chain"""
+    def richardson_mixing(self, b, u, v, nu0=5e-3, alpha=5.0, nu_b=1e-4, kappa_b=1e-5, shear_floor=0.0, x_axis: str = "X",
+                          y_axis: str = "Y", z_axis: str = "Z", to=None, padding=None, fill_value=None,
+                          metric_weighted: bool = True):
+        """Vertical viscosity `nu` and diffusivity `kappa` of the Pacanowski-Philander (1981) closure -- the middle link of
+        the Ri -> nu -> mixing loop, at the faces where `implicit_vertical_viscosity` takes nu and `vertical_diffusion` /
+        `implicit_vertical_diffusion` take kappa -- in ONE pass: b, u and v are read once and both results written once
+        (40 B/cell in float64, against about 250 for the chain's launches); Ri and every other intermediate stay in registers.
+
+        Positions, `to`, pads, metrics and leading dims are `richardson_number`'s: b at the centre, u at (Y:center, X:left),
+        v at (Y:left, X:center), Z third from last; both results have dims (lead, Z face, Y:center, X:center).  Returns
+        (nu, kappa), bit-identical, dims, coords and names included, to the chain
+
+            kw   = dict(padding=padding, fill_value=fill_value)
+            step = grid.derivative if metric_weighted else grid.diff
+            s2   = grid.vertical_shear_squared(u, v, x_axis, y_axis, z_axis, to=to, metric_weighted=metric_weighted, **kw)
+            n2   = step(b, z_axis, to=to, **kw)
+            ri   = n2 / (s2 + shear_floor)          # an additive floor on the shear
+            rp   = (ri + abs(ri)) * 0.5             # max(ri, 0)
+            den  = 1.0 + alpha * rp
+            nu   = nu0 / (den * den) + nu_b         # exponent 2, as a product
+            kappa = nu / den + kappa_b
+
+        Every operation is in the fields' dtype, each scalar cast to it once; no fused multiply-add, IEEE quotients.  The
+        defaults are PP81's constants in SI units (m2/s; `shear_floor` in 1/s2): an interface choice, nothing measured.
+
+        `rp` is max(ri, 0) for every finite ri and +0.0 for -0.0, so where the column is statically unstable (Ri < 0) the
+        results are the closure's maximum, exactly `nu0 + nu_b` and `(nu0 + nu_b) + kappa_b`; elsewhere
+        nu_b <= nu <= nu0 + nu_b.  Ri = +inf (N2 > 0 over no shear) gives the background values nu_b and kappa_b (alpha > 0); a NaN
+        stays NaN in both results; Ri = -inf gives NaN (inf - inf), as the chain does.  With `shear_floor=0.0` the
+        outermost faces under `extend` with "outer" are 0 / 0 = NaN (both differences vanish there); the implicit solves
+        never read those faces (no flux through the top and the bottom), and a positive `shear_floor` makes them finite.
+
+        Out of scope: convective adjustment (a larger kappa where N2 < 0), an exponent other than 2, clipping of nu.
+
+        The one pass serves the call when each of the five scalars is a Python int or float, or a numpy floating scalar that
+        does not promote the fields' dtype.  For anything else (a labelled or plain array, a numpy scalar of a wider type)
+        and in every case `richardson_number` hands to its chain (the list in its docstring), the chain above itself runs,
+        the same calls in the same order, raising what it raises."""
+        return self._richardson(b, u, v, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted,
+                                closure=(nu0, alpha, nu_b, kappa_b, shear_floor))
+
+    def _richardson(self, b, u, v, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted, closure=None):
+        """`richardson_number`, or with b None `vertical_shear_squared`: one launch of K7n, or their chain.  `closure`
+        (nu0, alpha, nu_b, kappa_b, shear_floor): `richardson_mixing`, one launch of K7p, or its chain"""
         ri = b is not None
         args = (b, u, v)
         (b, xr0), (u, xr1), (v, xr2) = (self._wrap_in(a) for a in args)
@@ -2139,6 +2181,8 @@ class Grid:
                 served = False  # (the chain raises it where the chain looks the metric up)
         if served:
             plan = self._second_order_plan(fields, x_axis, y_axis, padding, fill_value, [m for m in mets if m is not None])
+        if plan is not None and closure is not None and not all(_weak_scalar(s, u.data) for s in closure):
+            plan = None   # (an array, a wider numpy scalar: the chain's own promotion)
         if plan is not None:
             bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
             fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
@@ -2150,6 +2194,15 @@ class Grid:
             kw = dict(padding=padding, fill_value=fill_value)
             b, u, v = args
             step = self.derivative if metric_weighted else self.diff
+            if closure is not None:
+                nu0, alpha, nu_b, kappa_b, shear_floor = closure
+                s2 = self.vertical_shear_squared(u, v, x_axis, y_axis, z_axis, to=to, metric_weighted=metric_weighted, **kw)
+                n2 = step(b, z_axis, to=to, **kw)
+                r = n2 / (s2 + shear_floor)
+                rp = (r + abs(r)) * 0.5
+                den = 1.0 + alpha * rp
+                nu = nu0 / (den * den) + nu_b
+                return nu, nu / den + kappa_b
             uz = self.interp(step(u, z_axis, to=to, **kw), x_axis, **kw)
             vz = self.interp(step(v, z_axis, to=to, **kw), y_axis, **kw)
             s2 = uz * uz + vz * vz
@@ -2157,8 +2210,12 @@ class Grid:
         bcx, bcy, fvx, fvy, bcz, fvz = plan
         host = not any(_is_tensor(f.data) for f in fields)
         mu, mv, mb = (None if m is None else _aligned_view(m, dims) for m, dims in zip(mets, f_dims))
-        out = _dev.richardson_number(b.data if ri else None, u.data, v.data, mu, mv, mb, to == "outer", bcx, bcy, bcz,
-                                     fvx, fvy, fvz)
+        if closure is not None:
+            outs = _dev.richardson_mixing(b.data, u.data, v.data, mu, mv, mb, *(float(s) for s in closure), to == "outer",
+                                          bcx, bcy, bcz, fvx, fvy, fvz)
+        else:
+            outs = (_dev.richardson_number(b.data if ri else None, u.data, v.data, mu, mv, mb, to == "outer", bcx, bcy, bcz,
+                                           fvx, fvy, fvz),)
 
         # dims, coords and name as the chain's, step by step over placeholders: the derivatives at the faces (named after
         # their quotients with the metric), the two means at the centre, the squares, their sum, the quotient
@@ -2170,8 +2227,10 @@ class Grid:
         res = self._labels_of_binary(self._labels_of_binary(uz, uz), self._labels_of_binary(vz, vz))
         if ri:
             res = self._labels_of_binary(faces(b, 2), res)
-        res = res._replace(data=_dev.tohost(out) if host else out)
-        return to_xarray(res) if was_xr else res
+        # (the closure's steps pair an array with itself or with a scalar: coords and name stay the quotient's)
+        outs = tuple(res._replace(data=_dev.tohost(out) if host else out) for out in outs)
+        outs = tuple(to_xarray(r) for r in outs) if was_xr else outs
+        return outs if closure is not None else outs[0]
 
     # ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---------------------
     def _c_grid_vector(self, u, v, x_axis, y_axis, what):
@@ -2473,6 +2532,16 @@ def _implicit_vertical_diffusion_levels(a, kappa, mf, mc, z: int, dt: float):
     for k in range(n - 2, -1, -1):
         out[ix(out, k)] = at(out, k) + at(c, k) * at(out, k + 1)
     return out
+
+
+def _weak_scalar(s, data) -> bool:
+    """is `s` a scalar that `DataArray._binary` casts to the dtype of `data` -- a Python int or float, or a numpy floating
+    scalar that does not promote it -- and whose cast through a C double is that cast?"""
+    if isinstance(s, np.floating):   # (np.float64 is a Python float too, and strong)
+        return np.result_type(_dt.np_dtype(data), s) == _dt.np_dtype(data)
+    if isinstance(s, bool) or not isinstance(s, (int, float)):
+        return False
+    return isinstance(s, float) or abs(s) <= 2 ** 53   # (a larger int: double rounding on the way to float32)
 
 
 def _placeholder(shape):
