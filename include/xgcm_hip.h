@@ -566,8 +566,8 @@ int xg_momentum_advection_f64(const double* u, const double* v, const double* co
  * column and below the first row, the PRODUCT zeta [* nu_z] above the last row and right of the last column.  Periodic:
  * the STAGE's value at the wrapped index, extend: at the clamped index, fill: the fill value itself (never a quotient or
  * a product formed from it).  fill_x / fill_y pad u, v and the product D * nu_d; zfill_x / zfill_y pad the product
- * zeta * nu_z (the chain's one-axis differences keep the sign of a -0.0 fill that its two-axis operators drop, so a
- * caller that mirrors the chain passes +0.0 and -0.0 here).  The six metrics rA, rAz, dxC, dyC, dyG (the Y metric at u's
+ * zeta * nu_z (a caller that mirrors the chain passes the same pair twice: every operator of the chain keeps the sign
+ * of a -0.0 fill).  The six metrics rA, rAz, dxC, dyC, dyG (the Y metric at u's
  * points), dxG (the X metric at v's points) come together or are all NULL (the plain differences); nu_d (at the centre)
  * and nu_z (at the vorticity point) come together or are both NULL.  The eight planes use broadcast strides
  * (0 = broadcast) against `shape`.  XG_BC_HALO is not accepted. */

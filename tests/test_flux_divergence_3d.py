@@ -62,11 +62,11 @@ def _volume(ds, volume):
     return R.binary("mul", np.asarray(ds["rA"].values)[None], np.asarray(ds["drF"].values)[:, None, None])
 
 
-def _want(u, v, w, t, px, py, pz, vol):
+def _want(u, v, w, t, px, py, pz, vol, fill=FILL):
     zax = t.ndim - 3
-    fx, fy = R.flux(u, v, t, px, py, FILL["X"], FILL["Y"])
-    fz = R.binary("mul", w, R.stencil1d("interp", t, zax, 1, 0, pz, FILL["Z"]))
-    out = R.divergence(fx, fy, 1.0, px, py, FILL["X"], FILL["Y"]) + R.stencil1d("diff", fz, zax, 0, 1, pz, FILL["Z"])
+    fx, fy = R.flux(u, v, t, px, py, fill["X"], fill["Y"])
+    fz = R.binary("mul", w, R.stencil1d("interp", t, zax, 1, 0, pz, fill["Z"]))
+    out = R.divergence(fx, fy, 1.0, px, py, fill["X"], fill["Y"]) + R.stencil1d("diff", fz, zax, 0, 1, pz, fill["Z"])
     return out if vol is None else out / vol
 
 

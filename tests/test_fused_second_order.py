@@ -55,18 +55,18 @@ def _fields(lead, ny, nx, dtype, dims, nan=False):
             DataArray(t, dims + ("YC", "XC"), name="T"))
 
 
-def _want_flux_div(u, v, t, px, py, area):
-    fx, fy = R.flux(u, v, t, px, py, FILL["X"], FILL["Y"])
-    return R.divergence(fx, fy, area, px, py, FILL["X"], FILL["Y"])
+def _want_flux_div(u, v, t, px, py, area, fill=FILL):
+    fx, fy = R.flux(u, v, t, px, py, fill["X"], fill["Y"])
+    return R.divergence(fx, fy, area, px, py, fill["X"], fill["Y"])
 
 
-def _want_laplacian(a, px, py, met):
+def _want_laplacian(a, px, py, met, fill=FILL):
     if met is None:
-        gx, gy = R.gradient(a, px, py, FILL["X"], FILL["Y"])
-        return R.divergence(gx, gy, 1.0, px, py, FILL["X"], FILL["Y"])
-    gx, gy = R.gradient(a, px, py, FILL["X"], FILL["Y"], mx=met["dxC"], my=met["dyC"])
+        gx, gy = R.gradient(a, px, py, fill["X"], fill["Y"])
+        return R.divergence(gx, gy, 1.0, px, py, fill["X"], fill["Y"])
+    gx, gy = R.gradient(a, px, py, fill["X"], fill["Y"], mx=met["dxC"], my=met["dyC"])
     gx, gy = R.binary("mul", gx, met["dyG"]), R.binary("mul", gy, met["dxG"])
-    return R.divergence(gx, gy, met["rA"], px, py, FILL["X"], FILL["Y"])
+    return R.divergence(gx, gy, met["rA"], px, py, fill["X"], fill["Y"])
 
 
 def _metric_arrays(ds, dims, met_lead):

@@ -70,7 +70,7 @@ def _default(dtype):
     references = {}
     calls = _tables(D, dtype, references)
     want = {k: _hosted(D, fn()) for k, (fn, _) in calls.items()}
-    assert len(references) == 20 + 23 + 24
+    assert len(references) == 20 + 23 + 20 + 24
     for k, reference in references.items():
         ref = reference()
         assert len(ref) == len(want[k]) and all(TT._same_bits(g, w) for g, w in zip(want[k], ref)), f"{k}: the default result is not numpy's"

@@ -88,11 +88,18 @@ def _same(got, want):
     if isinstance(want.data, torch.Tensor):
         assert got.data.is_cuda and want.data.is_cuda and got.data.dtype == want.data.dtype
         g, w = got.data, want.data
-        assert torch.equal(torch.nan_to_num(g, nan=0.0), torch.nan_to_num(w, nan=0.0))
-        assert torch.equal(torch.isnan(g), torch.isnan(w))
+        # bit patterns, NaN masks apart: -0.0 is not +0.0
+        nan = torch.isnan(w)
+        assert torch.equal(torch.isnan(g), nan)
+        as_int = {4: torch.int32, 8: torch.int64}[g.element_size()]
+        zero = torch.zeros((), dtype=g.dtype, device=g.device)
+        assert torch.equal(torch.where(nan, zero, g).contiguous().view(as_int), torch.where(nan, zero, w).contiguous().view(as_int))
     else:
-        assert got.data.dtype == want.data.dtype
-        assert np.array_equal(got.data, want.data, equal_nan=True)
+        assert got.data.dtype == want.data.dtype and got.data.shape == want.data.shape
+        nan = np.isnan(want.data)
+        assert np.array_equal(np.isnan(got.data), nan)
+        bits, zero = {4: np.uint32, 8: np.uint64}[got.data.dtype.itemsize], got.data.dtype.type(0)
+        assert np.array_equal(np.where(nan, zero, got.data).view(bits), np.where(nan, zero, want.data).view(bits))
 
 
 def _check(grid, u, v, f=None, **kw):

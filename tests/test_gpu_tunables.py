@@ -9,8 +9,9 @@ float32: bit for bit the same, except along the contiguous axis where sums are r
 
 What the battery reaches is checked, not claimed: the default run records which entries of the C ABI are fetched from the
 library, and every `xg_*_f64` / `xg_*_f32` entry of `_hip.SIGNATURES` has to be among them or in `NOT_IN_BATTERY` with its
-reason -- the halo put and the input generator today.  The entries for K7i - K7k (`_one_pass_entries`) and for the halo forms
-and the gather (`_halo_entries`) are also compared with plain numpy before the sweep, and tests/test_tunable_battery_entries.py
+reason -- the halo put and the input generator today.  The entries for the fused vector operators and K7d - K7h
+(`_early_entries`), for K7i - K7k (`_one_pass_entries`) and for the halo forms and the gather (`_halo_entries`) are also
+compared with plain numpy before the sweep, and tests/test_tunable_battery_entries.py
 runs them on a machine without a GPU: through the host build of the ABI where it serves the entry, else on the oracle's double."""
 import numpy as np
 import pytest
@@ -76,35 +77,12 @@ def _battery(D, dtype, references=None):
     calls["padz"] = (lambda: D.pad_nd(a, {0: (1, 1)}, {0: "fill"}, {0: 3.0}), True)
     calls["mul"] = (lambda: D.binary("mul", a, mxy), True)
     calls["div"] = (lambda: D.binary("div", a, mz), True)
-    u, v = f((6, 64, 256), 8), f((6, 64, 256), 9)
-    area = m((1, 64, 256), 10)
-    calls["vort"] = (lambda: D.vorticity(u, v, area, "fill", "fill"), True)
-    calls["divg"] = (lambda: D.divergence(u, v, area, "periodic", "extend"), True)
-    calls["grad"] = (lambda: D.gradient(u, "periodic", "extend", 0.0, 0.0, area, area), True)
-    calls["flux"] = (lambda: D.flux(u, v, u, "periodic", "extend"), True)
-    calls["i2"] = (lambda: D.stencil2d("interp", u, 0, (1, 0), "periodic", 0.0, (1, 0), "extend", 0.0), True)
-    calls["i2mw"] = (lambda: D.stencil2d("interp", u, 0, (1, 0), "periodic", 0.0, (1, 0), "extend", 0.0, (area[0], area[0], area[0])), True)
-    # the one-pass operators K7d - K7h: level-shared (1, Y, X) planes (band-major work order under the defaults), metrics of
-    # the fields' own shape (the plain order), and the 3-D entries; inputs uploaded once
-    dev = lambda x: D.asdevice(x)  # noqa: E731
-    du, dv = dev(u), dev(v)
-    shared = [dev(m((1, 64, 256), 20 + k)) for k in range(5)]
-    full = [dev(m((6, 64, 256), 30 + k)) for k in range(5)]
-    for tag, (m0, m1, m2, m3, m4) in (("", shared), ("u", full)):   # "u": unshared metrics
-        cor = dev(f(tuple(m0.shape), 40) * dtype(3.0))
-        calls["fdiv" + tag] = (lambda m4=m4: D.flux_divergence(du, dv, du, m4, "periodic", "extend", 1.5, -0.5), True)
-        calls["lap" + tag] = (lambda m0=m0, m1=m1, m2=m2, m3=m3, m4=m4: D.laplacian(du, "fill", "periodic", 1.5, -0.5, m0, m1, m2, m3, m4), True)
-        calls["lapa" + tag] = (lambda m4=m4: D.laplacian(du, "extend", "fill", 1.5, -0.5, area=m4), True)
-        calls["madv" + tag] = (lambda cor=cor, m0=m0, m1=m1, m2=m2: D.momentum_advection(du, dv, cor, m0, m1, m2, "periodic", "fill", 1.5, -0.5), True)
-    calls["madv0"] = (lambda: D.momentum_advection(du, dv, None, None, None, None, "extend", "periodic"), True)
-    calls["ke"] = (lambda: D.kinetic_energy(du, dv, "fill", "extend", 1.5, -0.5), True)
-    u3, v3, w3, t3 = (dev(f((2, 6, 64, 256), 50 + k)) for k in range(4))
-    vol, vol2, mu, mv, ar3 = (dev(m((1, 6, 64, 256), 60 + k)) for k in range(5))
-    drf, ra = dev(m((1, 6, 1, 1), 66)), dev(m((1, 1, 64, 256), 67))
-    calls["fdiv3"] = (lambda: D.flux_divergence_3d(u3, v3, w3, t3, vol, vol2, "periodic", "extend", "fill", 1.5, -0.5, 0.25), True)
-    calls["fdiv3p"] = (lambda: D.flux_divergence_3d(u3, v3, w3, t3, ra, drf, "fill", "periodic", "extend", 1.5, -0.5, 0.25), True)
-    calls["wcont"] = (lambda: D.vertical_velocity(u3, v3, mu, drf, mv, drf, ar3, "periodic", "extend", "fill", 1.5, -0.5, 0.25), True)
-    calls["wcontr"] = (lambda: D.vertical_velocity(u3, v3, ra, drf, ra, drf, ra, "extend", "fill", "periodic", 1.5, -0.5, 0.25, True), True)
+    # the fused vector operators and the one-pass operators K7d - K7h
+    for k, (fn, reference) in _early_entries(D, dtype).items():
+        assert k not in calls
+        calls[k] = (fn, True)
+        if references is not None:
+            references[k] = reference
     phi = f((20, 24, 128), 11)
     theta = np.cumsum(R.synthetic_field((20, 24, 128), 12).astype(dtype) + dtype(0.55), axis=0)
     theta_o = np.cumsum(R.synthetic_field((21, 24, 128), 13).astype(dtype) + dtype(0.55), axis=0)
@@ -117,6 +95,85 @@ def _battery(D, dtype, references=None):
         if references is not None:
             references[k] = reference
     return calls
+
+
+def _early_entries(D, dtype, V=None):
+    """name -> (thunk, reference) for the fused vector operators (`vort`, `divg`, `grad`, `flux`), the two-axis stencil
+    (`i2`, `i2mw`) and the one-pass operators K7d - K7h: level-shared (1, Y, X) planes (band-major work order under the
+    defaults; no tag), metrics of the fields' own shape (the plain order; tag "u": unshared) and the 3-D entries.  The thunk
+    calls `D` on inputs uploaded once, the reference gives the plain numpy result of the same call over the host copies of
+    the same inputs, by the numpy statements of the operators' CPU suites.  Every entry is exact.  `V`: the module that
+    serves the vector operators and the two-axis stencil (the CPU twin passes the oracle's double, since the host build of the
+    ABI has the one-axis and the one-pass operators only); `D` by default"""
+    import types
+
+    import test_flux_divergence_3d as T3
+    import test_momentum_advection as TM
+    import test_vertical_velocity as TV
+    from test_fused_second_order import _want_flux_div, _want_laplacian
+
+    f = lambda shape, seed: R.synthetic_field(shape, seed).astype(dtype)  # noqa: E731
+    m = lambda shape, seed: R.synthetic_metric(shape, seed).astype(dtype)  # noqa: E731
+    dev = lambda x: D.asdevice(x)  # noqa: E731
+    u, v = f((6, 64, 256), 8), f((6, 64, 256), 9)
+    area = m((1, 64, 256), 10)
+    zero = {"X": 0.0, "Y": 0.0}
+    V = D if V is None else V
+    out = {}
+    out["vort"] = (lambda: V.vorticity(u, v, area, "fill", "fill"), lambda: [R.vorticity(u, v, area, "fill", "fill")])
+    out["divg"] = (lambda: V.divergence(u, v, area, "periodic", "extend"), lambda: [R.divergence(u, v, area, "periodic", "extend")])
+    out["grad"] = (lambda: V.gradient(u, "periodic", "extend", 0.0, 0.0, area, area),
+                   lambda: list(R.gradient(u, "periodic", "extend", 0.0, 0.0, area, area)))
+    out["flux"] = (lambda: V.flux(u, v, u, "periodic", "extend"), lambda: list(R.flux(u, v, u, "periodic", "extend")))
+    # the two-axis stencil: the two one-axis operators one after the other, X then Y; weighted: times the metric at the
+    # current position before each axis, divided by the one at the new position after it
+    out["i2"] = (lambda: V.stencil2d("interp", u, 0, (1, 0), "periodic", 0.0, (1, 0), "extend", 0.0),
+                 lambda: [R.stencil1d("interp", R.stencil1d("interp", u, 2, 1, 0, "periodic", 0.0), 1, 1, 0, "extend", 0.0)])
+    out["i2mw"] = (lambda: V.stencil2d("interp", u, 0, (1, 0), "periodic", 0.0, (1, 0), "extend", 0.0, (area[0], area[0], area[0])),
+                   lambda: [R.stencil1d("interp", R.stencil1d("interp", u, 2, 1, 0, "periodic", 0.0, area[0], area[0]), 1, 1, 0,
+                                        "extend", 0.0, area[0], area[0])])
+    du, dv = dev(u), dev(v)
+    fill = {"X": 1.5, "Y": -0.5, "Z": 0.25}
+    shared = [m((1, 64, 256), 20 + k) for k in range(5)]
+    full = [m((6, 64, 256), 30 + k) for k in range(5)]
+    for tag, planes in (("", shared), ("u", full)):   # "u": unshared metrics
+        m0, m1, m2, m3, m4 = planes
+        d0, d1, d2, d3, d4 = (dev(x) for x in planes)
+        cor = f(tuple(m0.shape), 40) * dtype(3.0)
+        dcor = dev(cor)
+        out["fdiv" + tag] = (lambda d4=d4: D.flux_divergence(du, dv, du, d4, "periodic", "extend", 1.5, -0.5),
+                             lambda m4=m4: [_want_flux_div(u, v, u, "periodic", "extend", m4, fill=fill)])
+        met = {"dxC": m0, "dyC": m1, "dyG": m2, "dxG": m3, "rA": m4}
+        out["lap" + tag] = (lambda d=(d0, d1, d2, d3, d4): D.laplacian(du, "fill", "periodic", 1.5, -0.5, *d),
+                            lambda met=met: [_want_laplacian(u, "fill", "periodic", met, fill=fill)])
+        one = np.ones((), dtype=dtype)   # (x / 1 and x * 1 are exact: the chain with the area alone)
+        only = {"dxC": one, "dyC": one, "dyG": one, "dxG": one, "rA": m4}
+        out["lapa" + tag] = (lambda d4=d4: D.laplacian(du, "extend", "fill", 1.5, -0.5, area=d4),
+                             lambda only=only: [_want_laplacian(u, "extend", "fill", only, fill=fill)])
+        ds = {k: types.SimpleNamespace(values=x) for k, x in (("rAz", m0), ("dxC", m1), ("dyC", m2))}
+        out["madv" + tag] = (lambda d=(dcor, d0, d1, d2): D.momentum_advection(du, dv, *d, "periodic", "fill", 1.5, -0.5),
+                             lambda ds=ds, cor=cor: list(TM._want(u, v, "periodic", "fill", ds, cor, fill=fill)))
+    out["madv0"] = (lambda: D.momentum_advection(du, dv, None, None, None, None, "extend", "periodic"),
+                    lambda: list(TM._want(u, v, "extend", "periodic", None, None, fill=zero)))
+    out["ke"] = (lambda: D.kinetic_energy(du, dv, "fill", "extend", 1.5, -0.5), lambda: [TM._want_ke(u, v, "fill", "extend", fill=fill)])
+    h3 = [f((2, 6, 64, 256), 50 + k) for k in range(4)]
+    u3, v3, w3, t3 = (dev(x) for x in h3)
+    hm = [m((1, 6, 64, 256), 60 + k) for k in range(5)]
+    vol, vol2, mu, mv, ar3 = (dev(x) for x in hm)
+    hdrf, hra = m((1, 6, 1, 1), 66), m((1, 1, 64, 256), 67)
+    drf, ra = dev(hdrf), dev(hra)
+    mul = lambda a, b: R.binary("mul", a, b)  # noqa: E731
+    out["fdiv3"] = (lambda: D.flux_divergence_3d(u3, v3, w3, t3, vol, vol2, "periodic", "extend", "fill", 1.5, -0.5, 0.25),
+                    lambda: [T3._want(*h3, "periodic", "extend", "fill", mul(hm[0], hm[1]), fill=fill)])
+    out["fdiv3p"] = (lambda: D.flux_divergence_3d(u3, v3, w3, t3, ra, drf, "fill", "periodic", "extend", 1.5, -0.5, 0.25),
+                     lambda: [T3._want(*h3, "fill", "periodic", "extend", mul(hra, hdrf), fill=fill)])
+    out["wcont"] = (lambda: D.vertical_velocity(u3, v3, mu, drf, mv, drf, ar3, "periodic", "extend", "fill", 1.5, -0.5, 0.25),
+                    lambda: [TV._want(h3[0], h3[1], "periodic", "extend", "fill", False, faces=(mul(hm[2], hdrf), mul(hm[3], hdrf)),
+                                      area=hm[4], fill=fill)])
+    out["wcontr"] = (lambda: D.vertical_velocity(u3, v3, ra, drf, ra, drf, ra, "extend", "fill", "periodic", 1.5, -0.5, 0.25, True),
+                     lambda: [TV._want(h3[0], h3[1], "extend", "fill", "periodic", True, faces=(mul(hra, hdrf), mul(hra, hdrf)),
+                                       area=hra, fill=fill)])
+    return out
 
 
 # K7i - K7k.  ny = 29: 15 two-row segments, the last of one row, ragged against bands of 1, 2, 4 and 8 segments (vec_zb_rows
@@ -326,7 +383,8 @@ def test_every_tunable_value_computes_the_same(dtype, monkeypatch):
     assert abi - reached - set(NOT_IN_BATTERY) == set(), f"ABI entries that no battery call reaches: {sorted(abi - reached - set(NOT_IN_BATTERY))}"
     assert set(NOT_IN_BATTERY) <= abi - reached, f"stale NOT_IN_BATTERY names: {sorted(set(NOT_IN_BATTERY) - (abi - reached))}"
     # the new entries against plain numpy first, so that the sweep does not only compare the library with itself
-    assert len(references) == 20 + 23   # K7i - K7k; eight vector halo entries, twelve stencil halo entries, three gathers
+    # K7i - K7k; eight vector halo entries, twelve stencil halo entries, three gathers; the vector operators and K7d - K7h
+    assert len(references) == 20 + 23 + 20
     for k, reference in references.items():
         ref = reference()
         assert len(ref) == len(want[k]) and all(_same_bits(g, w) for g, w in zip(want[k], ref)), f"{k}: the default result is not numpy's"

@@ -19,6 +19,7 @@ def _same(got, want):
     assert len(got) == len(want) == 2
     for g, w in zip(got, want):
         TM._same_labelled(g, w)
+        TM._same_bits(np.asarray(g.values), np.asarray(w.values))   # bit patterns, NaN masks apart: -0.0 is not +0.0
 
 
 def _counted(monkeypatch):

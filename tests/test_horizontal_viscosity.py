@@ -70,9 +70,9 @@ def _coefficients(form, lead, ny, nx, dtype, dims, ds):
 
 
 def _want(u, v, px, py, ds=None, nu=(None, None), fill=FILL):
-    """the chain; `ds`: the dataset whose six metrics weight it (None: unweighted).  The two-axis operators of the chain
-    take their fill as `float(fill or 0.0)`, its one-axis operators as it is."""
-    pos = {k: float(f or 0.0) for k, f in fill.items()}
+    """the chain; `ds`: the dataset whose six metrics weight it (None: unweighted).  Every operator of the chain, two-axis or
+    one-axis, takes its fill as it is: a -0.0 fill keeps its sign."""
+    pos = {k: float(f) for k, f in fill.items()}
     one = np.asarray(1.0, dtype=u.dtype)
     met = (lambda k: np.asarray(ds[k].values)) if ds is not None else (lambda k: None)
     div = R.divergence(u, v, one if ds is None else met("rA"), px, py, pos["X"], pos["Y"])
@@ -185,9 +185,9 @@ def _chain(grid, u, v, viscosity_d=None, viscosity_z=None, x_axis="X", y_axis="Y
 @pytest.mark.parametrize("weighted", [True, False])
 @pytest.mark.parametrize("which", ["X", "Y", "XY"])
 def test_a_negative_zero_fill_leaves_the_chains_bit_patterns(host_abi, monkeypatch, dtype, weighted, which):
-    """all-zero fields (+0.0 and -0.0 mixed), fill_value = -0.0: the two-axis operators of the chain pad with +0.0, its
-    one-axis differences of zeta with -0.0, and (-0.0) - (+0.0) differs from (+0.0) - (+0.0) in its sign bit.  Compared as
-    integers with the oracle AND with the chain itself run through Grid over the oracle double."""
+    """all-zero fields (+0.0 and -0.0 mixed), fill_value = -0.0: every operator of the chain pads with -0.0, and
+    (-0.0) - (+0.0) differs from (+0.0) - (+0.0) in its sign bit.  Compared as integers with the oracle AND with the chain
+    itself run through Grid over the oracle double."""
     from oracle import fake_device
 
     calls = _Calls(monkeypatch)

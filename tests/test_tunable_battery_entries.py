@@ -1,5 +1,6 @@
-"""The K7i - K7k entries of the tunables battery (`test_gpu_tunables._one_pass_entries`) and its entries for the pre-gathered
-halo forms and the gather (`_halo_entries`) on a machine without a GPU.
+"""The K7i - K7k entries of the tunables battery (`test_gpu_tunables._one_pass_entries`), its entries for the fused vector
+operators and K7d - K7h (`_early_entries`) and those for the pre-gathered halo forms and the gather (`_halo_entries`) on a
+machine without a GPU.
 
 The same thunks that tests/test_gpu_tunables.py sweeps over every tunable value run here once through the `host_abi` fixture
 (the product's `xgcm_amd.device` over libxgcm_host.so) and are compared bit for bit with their numpy references: the
@@ -30,6 +31,28 @@ def test_one_pass_entries_equal_their_numpy_references(host_abi, dtype):
                 assert not np.isnan(w).any(), name
             else:                          # the NaN cells reach the result and stay local
                 assert np.isnan(w).any() and np.isnan(w).mean() < 0.01, name
+            assert TT._same_bits(g, w), name
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_early_entries_equal_their_numpy_references(host_abi, dtype):
+    """`_early_entries`: K7d - K7h through the host build of the ABI; the fused vector operators and the two-axis stencil
+    (which the host build does not have) on the oracle's double"""
+    import xgcm_amd.device as D
+    from oracle import fake_device
+
+    entries = TT._early_entries(D, dtype, V=fake_device)
+    two = ("grad", "flux", "madv", "madvu", "madv0")
+    assert list(entries) == ["vort", "divg", "grad", "flux", "i2", "i2mw", "fdiv", "lap", "lapa", "madv", "fdivu", "lapu", "lapau",
+                             "madvu", "madv0", "ke", "fdiv3", "fdiv3p", "wcont", "wcontr"]
+    for name, (thunk, reference) in entries.items():
+        got = thunk()
+        got = [D.tohost(x) for x in got] if isinstance(got, tuple) else [D.tohost(got)]
+        want = reference()
+        assert len(got) == len(want) == (2 if name in two else 1), name
+        for g, w in zip(got, want):
+            assert g.dtype == np.dtype(dtype), name
+            assert np.isfinite(w).all() and (w != 0).any(), name
             assert TT._same_bits(g, w), name
 
 

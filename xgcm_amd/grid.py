@@ -50,7 +50,7 @@ from .labeled import (CHUNKED_INPUT_MESSAGE, DataArray, Dataset, _aligned_view, 
                       _result_name,
                       from_xarray, is_xarray, to_xarray)
 from .metrics import iterate_axis_combinations
-from .padding import FoldSpec, InteriorOf, halo_cells, no_boundary_error, pad
+from .padding import FoldSpec, InteriorOf, fill_of, halo_cells, no_boundary_error, pad
 
 
 def _maybe_promote_str_to_list(a):
@@ -706,8 +706,8 @@ class Grid:
                     return None  # mixed precision (a float32 field, float64 metrics): numpy's steps, one axis at a time
                 planes.append(self._resident(m, array.data).data)
                 named = _name_after(named, m)
-        out = _dev.stencil2d(funcname, array.data, 0 if x_is_a else 1, padx, bc[ax_x], float(fv[ax_x] or 0.0), pady,
-                             bc[ax_y], float(fv[ax_y] or 0.0), **({"metrics": planes} if planes is not None else {}))
+        out = _dev.stencil2d(funcname, array.data, 0 if x_is_a else 1, padx, bc[ax_x], fill_of(fv[ax_x]), pady,
+                             bc[ax_y], fill_of(fv[ax_y]), **({"metrics": planes} if planes is not None else {}))
         rename = {dim_a: out_a, dim_b: out_b}
         res = DataArray(_dev.tohost(out) if host else out, tuple(rename.get(d, d) for d in array.dims), name=named)
         return _reattach_coords([res], self, None, {out_a, out_b}, [array])[0]
@@ -1098,7 +1098,7 @@ class Grid:
                     raise no_boundary_error(ax)
                 halos[ax] = None
                 modes[ax] = bc[ax]
-        return (modes[x_axis], modes[y_axis], float(fv[x_axis] or 0.0), float(fv[y_axis] or 0.0), halos[x_axis],
+        return (modes[x_axis], modes[y_axis], fill_of(fv[x_axis]), fill_of(fv[y_axis]), halos[x_axis],
                 halos[y_axis])
 
     def _two_component_halos(self, u, v, x_axis, y_axis, widths, padding, fill_value, x_of: str, y_of: str):
@@ -1120,7 +1120,7 @@ class Grid:
                     raise no_boundary_error(ax)
                 halos[ax] = None
                 modes[ax] = bc[ax]
-        return (modes[x_axis], modes[y_axis], float(fv[x_axis] or 0.0), float(fv[y_axis] or 0.0), halos[x_axis],
+        return (modes[x_axis], modes[y_axis], fill_of(fv[x_axis]), fill_of(fv[y_axis]), halos[x_axis],
                 halos[y_axis])
 
     def divergence(self, u, v, x_axis: str = "X", y_axis: str = "Y", padding=None, fill_value=None,
@@ -1243,7 +1243,7 @@ class Grid:
         fv = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
         if bc[x_axis] is None or bc[y_axis] is None:
             return None  # (the chain raises the missing-boundary error)
-        return bc[x_axis], bc[y_axis], float(fv[x_axis] or 0.0), float(fv[y_axis] or 0.0)
+        return bc[x_axis], bc[y_axis], fill_of(fv[x_axis]), fill_of(fv[y_axis])
 
     def flux_divergence(self, u, v, tracer, x_axis: str = "X", y_axis: str = "Y", padding=None, fill_value=None,
                         metric_weighted: bool = True):
@@ -1406,7 +1406,7 @@ class Grid:
             if plan is not None:
                 bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
                 fv = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
-                plan = None if bc[z_axis] is None else plan + (bc[z_axis], float(fv[z_axis] or 0.0))
+                plan = None if bc[z_axis] is None else plan + (bc[z_axis], fill_of(fv[z_axis]))
         if plan is None:
             kw = dict(padding=padding, fill_value=fill_value)
             fx, fy = self.flux(args[0], args[1], args[3], x_axis, y_axis, **kw)
@@ -2402,9 +2402,9 @@ class Grid:
         column.  Periodic: the stage's own value at the wrapped index; extend: at the clamped index; fill: `fill_value`
         itself, never a quotient or a product formed from it.
 
-        Signed zeros: `divergence`, `vorticity` and `gradient` turn a -0.0 fill value into +0.0, the one-axis operators
-        of the last stage hand it on as it is.  The kernel takes a separate fill pair for the pads of zeta * nu_z, so a
-        -0.0 fill goes through the one pass too and leaves the chain's bit patterns.
+        Signed zeros: every operator of the chain hands a -0.0 fill value on as it is, and so does the one pass (the
+        kernel takes a fill pair of its own for the pads of zeta * nu_z: the same values), which leaves the chain's bit
+        patterns.
 
         Metrics: with `metric_weighted`, whatever `get_metric` returns at each stage's dims -- the (X, Y) metric at the
         centre and at the vorticity point, the X metric at u's and the Y metric at v's points (the gradient), the Y metric
@@ -2454,7 +2454,7 @@ class Grid:
             gv = dy + zx
             return gu, gv
         bcx, bcy, fvx, fvy = plan
-        # the one-axis operators of the last stage hand their fill value on as it is (None: 0.0): a -0.0 keeps its sign there
+        # the fill of the last stage's one-axis operators (None: 0.0); the same values as the plan's, a -0.0 included
         fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
         zfx, zfy = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis))
         host = not (_is_tensor(u.data) or _is_tensor(v.data))

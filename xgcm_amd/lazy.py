@@ -370,13 +370,13 @@ class StencilNode(Node):
 
     def halo(self, widths):
         """(boundary mode, fill value, pre-gathered halo slab or None) of this node's axis, as the node itself pads"""
-        from .padding import halo_cells
+        from .padding import fill_of, halo_cells
 
         if self.complex:
             h = halo_cells(plain(self.arg), self.grid, self.ax_name, widths, padding=self.remaining.get("padding"),
                            fill_value=self.remaining.get("fill_value"), other_component=plain(self.other_component))
             return "halo", 0.0, h.data
-        return self.bc, float(self.fv or 0.0), None
+        return self.bc, fill_of(self.fv), None
 
 
 def defer_stencil(grid, funcname, ufunc, sig, arg, ax_name, other_component, m_in, m_out, remaining, out_dims):

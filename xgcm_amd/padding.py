@@ -47,6 +47,12 @@ def no_boundary_error(ax: str) -> ValueError:
     )
 
 
+def fill_of(value) -> float:
+    """The fill value of one axis as the device layer takes it: None is 0.0, every float stays as it is -- the falsy
+    test `value or <zero>` would turn a -0.0 fill into +0.0, and the sign of a zero shows in a difference against it"""
+    return 0.0 if value is None else float(value)
+
+
 def _strip_all_coords(obj):
     if isinstance(obj, dict):
         return {k: _strip_all_coords(v) for k, v in obj.items()}
