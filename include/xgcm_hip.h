@@ -53,6 +53,8 @@
  *                      or the squared shear alone, one pass (one entry likewise)
  *   xg_richardson_mixing  the Pacanowski-Philander closure on that Richardson number: nu and kappa at the faces of Z from
  *                      b, u and v, one pass (one entry likewise)
+ *   xg_isopycnal_slope  -interp(interp(derivative(b, X | Y), X | Y), Z) / derivative(b, Z): the slopes of the b-surfaces at
+ *                      the faces of Z, one pass (one entry likewise)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -524,6 +526,25 @@ int xg_richardson_mixing(int dtype, const void* b, const void* u, const void* v,
                          double alpha, double nu_b, double kappa_b, double shear_floor, void* out_nu, void* out_kappa,
                          const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
                          double fill_z, void* stream);
+/* The isopycnal slopes at the faces of Z, one pass.  b of `shape` (.., Z, Y, X) at the cell centre; `out_x` and `out_y` have
+ * nz (outer = 0, Z:left) or nz + 1 (outer = 1, Z:outer) levels along Z and may not overlap.  Replaces the chain
+ *   gx = interp(interp(diff(b, X) [/ mx], X), Z)      center -> left -> center along X, then center -> the faces of Z
+ *   gy = interp(interp(diff(b, Y) [/ my], Y), Z)      the same along Y
+ *   bz = diff(b, Z) [/ mz]                            center -> the faces of Z
+ *   out_x = -1 * (gx / bz)    out_y = -1 * (gy / bz)  no fused multiply-add, IEEE quotients, no guard on bz == 0
+ * Every stage pads its own input: b left of column 0 / below row 0 (periodic: b[n-1], extend: b[0], fill: the fill value);
+ * the DIFFERENCE (over its metric) right of the last column / above the last row (periodic: the one at index 0, extend: at
+ * n-1, fill: the fill value itself); the LEVEL MEANS above level 0 and (outer = 1) below level nz-1 (periodic: the far
+ * level's, extend: the level's own, fill: fill_z itself); b above level 0 and (outer = 1) below level nz-1 likewise.
+ * mx (at b's levels, the columns of X:left) and my (at b's levels, the rows of Y:left) have broadcast strides (0 =
+ * broadcast) against `shape`; mz (at the faces) against `shape` with the results' levels along Z.  NULL: absent.  The fills
+ * are cast to the element type (-0.0 and NaN keep their bits).  XG_ERR_INVALID: an element type other than XG_T_F64 /
+ * XG_T_F32, a NULL b, out_x, out_y or shape, a metric without strides, outer not 0 or 1, an unknown boundary code, nz = 0;
+ * the results are untouched then. */
+int xg_isopycnal_slope(int dtype, const void* b, const void* mx, const int64_t* mx_strides, const void* my,
+                       const int64_t* my_strides, const void* mz, const int64_t* mz_strides, void* out_x, void* out_y,
+                       const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
+                       double fill_z, void* stream);
 
 /* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
 /* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).

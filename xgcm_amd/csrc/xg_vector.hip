@@ -2609,6 +2609,219 @@ __global__ __launch_bounds__(BLOCK) void k_rimix(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7q: the isopycnal slopes at the flux faces of Z in ONE pass over (lead, Z, Y, X), one field in, two out (nz faces at
+// Z:left, nz + 1 at Z:outer).  Per level
+//   g[i] = (b[i] - b[i-1]) [/ mx[i]]      G_x[i] = (g[i] + g[i+1]) * 0.5        and the same along Y with my: G_y
+// per face
+//   gx = (G_x[k-1] + G_x[k]) * 0.5    gy = (G_y[k-1] + G_y[k]) * 0.5    bz = (b[k] - b[k-1]) [/ mz[k]]
+//   sx = -1 * (gx / bz)               sy = -1 * (gy / bz)                                  (no FMA, IEEE quotients)
+// i.e. diff | derivative (X / Y, center -> left), interp back (left -> center), interp (Z, center -> left | outer); diff |
+// derivative (Z) of b; the two quotients, negated.  Pads as the chain's: b left of column 0 / below row 0, then the
+// DERIVATIVE right of the last column / above the last row (periodic: the derivative at index 0, extend: at n-1, fill: the
+// fill value itself), then the LEVEL MEANS G above level 0 and (`outer`) below level nz-1 (periodic: the far level's,
+// extend: the level's own, fill: fill_z itself); b along Z as K7n's.  No guard on bz == 0.
+// K7n's wave-task and march: a wave owns one (lead, Y segment, X tile) column and keeps the level above the face in
+// registers -- not its rows but what the faces need of it, G_x, G_y and b of the segment.  A level brings SEG + 2 rows of b
+// (the row below and the row above the segment: L2 hits, the neighbouring segments' rows) and, for the segment's rows, the
+// element left of and right of the lane's vector: b left of it from the lane below by DPP, the finished derivative right of
+// it from the lane above by DPP; the tile's first / last lane and the row's edges load their own.  The rows of the level
+// below the next face are requested before a face's quotients.  b is read once and each result written once: 24 B/cell in float64.
+// mx at b's levels and u's columns, my at b's levels and v's rows, mz at the faces: one broadcast array each, each may be
+// absent; rows that do not vary along Z are loaded once per wave, mx also at the column right of the lane, my also at the
+// row above the segment.  Periodic Z costs one more level before the march (and, `outer`, one after it).
+// ------------------------------------------------------------------------------------------
+template <typename T, int SEG>
+struct IsRows {  // what one level of a column brings: the row below, SEG rows with b left and right of the lane, the row above
+  T bb[SEG], below, above;
+  real bl[SEG], br[SEG];
+};
+template <typename T, int SEG>
+struct IsLevel {  // what a face needs of a level
+  T gx[SEG], gy[SEG], bb[SEG];
+};
+
+template <int V, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_islope(
+    const real* __restrict__ b, real* __restrict__ out_x, real* __restrict__ out_y, int64_t o0, u32 nouter, u32 nblk,
+    int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int bc_x, real fill_x, int bc_y, real fill_y,
+    int bc_z, real fill_z, VolIdx mx, VolIdx my, VolIdx mz, int ntl) {
+  typedef typename VecT<V>::type T;
+  typedef IsRows<T, SEG> Rows;
+  typedef IsLevel<T, SEG> L;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  const int64_t nf = nz + outer;       // faces
+  // X: the columns left and right of the lane's vector, always inside the row (wrapped at a periodic edge, clamped at any
+  // other: the clamped left column IS the extend pad of b); a fill edge replaces b on the left, a fill or extend edge the
+  // derivative on the right
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);
+  const bool per_x = bc_x == XG_BC_PERIODIC, per_z = bc_z == XG_BC_PERIODIC;
+  const bool fill_l = e.edge_l && bc_x == XG_BC_FILL;
+  const bool pad_r = e.edge_r && !per_x;
+  // Y: the row below the segment (periodic: row ny - 1 below row 0, extend: row 0 itself) and the row above it, where the
+  // top derivative is formed (periodic: row 0 above row ny - 1); wave-uniform
+  const bool fill_b = j0 == 0 && bc_y == XG_BC_FILL;
+  const int64_t jb = (j0 > 0) ? j0 - 1 : ((bc_y == XG_BC_PERIODIC) ? ny - 1 : 0);
+  const int64_t q = j0 + nrow;
+  const bool pad_t = q >= ny && bc_y != XG_BC_PERIODIC;
+  const int64_t jt = (q < ny) ? q : ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1);
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+
+  // the rows of mx and my of a level: in registers, loaded again per level only when the array varies along Z
+  T mxr[SEG], myr[SEG], myt;
+  real mxrr[SEG];
+  int64_t mxo = 0, mro = 0, myo = 0, mto = 0, mzo = 0;
+  auto hmetrics = [&](int64_t k, bool first) {
+    if (mx.p && (first || mx.sz != 0)) {
+      load_rows<T, SEG>(mxr, mx.p, mxo + k * mx.sz, mx.sy, mx.sx, nrow, (ntl & 4) != 0);
+      if (e.own_r) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) mxrr[s_] = mx.p[mro + k * mx.sz + ((s_ < nrow) ? s_ : nrow - 1) * mx.sy];
+      }
+    }
+    if (my.p && (first || my.sz != 0)) {
+      load_rows<T, SEG>(myr, my.p, myo + k * my.sz, my.sy, my.sx, nrow, (ntl & 8) != 0);
+      T top[1];
+      load_rows<T, 1>(top, my.p, mto + k * my.sz, my.sy, my.sx, 1, (ntl & 8) != 0);
+      myt = top[0];
+    }
+  };
+  if (MET) {
+    const int64_t xo = mx.p ? area_outer_off(mx.ai, o) : 0, yo = my.p ? area_outer_off(my.ai, o) : 0;
+    mxo = xo + j0 * mx.sy + i0 * mx.sx;
+    mro = xo + j0 * mx.sy + e.ridx * mx.sx;
+    myo = yo + j0 * my.sy + i0 * my.sx;
+    mto = yo + jt * my.sy + i0 * my.sx;
+    if (mz.p) mzo = area_outer_off(mz.ai, o) + j0 * mz.sy + i0 * mz.sx;
+    hmetrics(0, true);
+  }
+
+  auto fetch = [&](int64_t k) -> Rows {  // (with the level's own mx and my rows: `level` is the only reader of both)
+    Rows x;
+    const int64_t lv = col + k * plane;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.bb[s_] = *reinterpret_cast<const T*>(b + lv + ro[s_] + i0);
+      x.bl[s_] = e.own_l ? b[lv + ro[s_] + e.lidx] : real(0);
+      x.br[s_] = e.own_r ? b[lv + ro[s_] + e.ridx] : real(0);
+    }
+    x.below = *reinterpret_cast<const T*>(b + lv + jb * nx + i0);
+    x.above = *reinterpret_cast<const T*>(b + lv + jt * nx + i0);
+    if (MET) hmetrics(k, false);
+    return x;
+  };
+  // G_x, G_y and b of the segment from the rows of a level
+  auto level = [&](const Rows& x) -> L {
+    L r;
+    T g[SEG], h[SEG];
+    real gr[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      real left = x.bl[s_];
+      if (e.shl) {
+        const real dpp = from_lane_below(vec_last(x.bb[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+        if (!e.own_l) left = dpp;
+      }
+      if (fill_l) left = fill_x;
+      g[s_] = dvdx_of(x.bb[s_], left);
+      gr[s_] = x.br[s_] - vec_last(x.bb[s_]);
+      const T lower = (s_ == 0) ? (fill_b ? splat<T>(fill_y) : x.below) : x.bb[(s_ > 0) ? s_ - 1 : 0];
+      h[s_] = x.bb[s_] - lower;
+    }
+    T top = x.above - x.bb[SEG - 1];  // (short tails repeat the last row: bb[SEG - 1] is row nrow - 1)
+    if (MET) {
+      if (mx.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) g[s_] = g[s_] / mxr[s_];
+        if (e.own_r) {
+#pragma unroll
+          for (int s_ = 0; s_ < SEG; ++s_) gr[s_] = gr[s_] / mxrr[s_];
+        }
+      }
+      if (my.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) h[s_] = h[s_] / myr[s_];
+        top = top / myt;
+      }
+    }
+    if (e.shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real right = from_lane_above(vec_first(g[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+        if (!e.own_r) gr[s_] = right;
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (pad_r) gr[s_] = (bc_x == XG_BC_FILL) ? fill_x : vec_last(g[s_]);
+      r.gx[s_] = interp_right_of(g[s_], gr[s_]);
+      T up = (s_ + 1 < nrow) ? h[(s_ + 1 < SEG) ? s_ + 1 : s_] : top;
+      if (s_ + 1 >= nrow && pad_t) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : h[s_];
+      r.gy[s_] = op2<XG_OP_INTERP>(h[s_], up);
+      r.bb[s_] = x.bb[s_];
+    }
+    return r;
+  };
+  auto padded = [&]() -> L {  // a level of the fill value: the pad of the level means and of b
+    L r;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) r.gx[s_] = r.gy[s_] = r.bb[s_] = splat<T>(fill_z);
+    return r;
+  };
+
+  // one face from the level above it (`lo`) and the level below it (`hi`)
+  const int64_t po = o * nf * plane + j0 * nx + i0;
+  const T minus = splat<T>(real(-1));
+  auto face = [&](int64_t k, const L& lo, const L& hi, const T (&mzr)[SEG]) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        const T gx = op2<XG_OP_INTERP>(lo.gx[s_], hi.gx[s_]);
+        const T gy = op2<XG_OP_INTERP>(lo.gy[s_], hi.gy[s_]);
+        T bz = op2<XG_OP_DIFF>(lo.bb[s_], hi.bb[s_]);
+        if (MET) {
+          if (mz.p) bz = bz / mzr[s_];
+        }
+        const int64_t at = po + k * plane + s_ * nx;
+        stg_s<T, NTS>(out_x + at, minus * (gx / bz));
+        stg_s<T, NTS>(out_y + at, minus * (gy / bz));
+      }
+    }
+  };
+
+  // face 0 lies between the pad above level 0 and level 0; the march keeps the level above the face, and has the rows of
+  // the level below the NEXT face on their way while a face's quotients run.  The next face's mz rows are asked for after
+  // the face: a second set of them in flight beside the rows costs the float64 metric instance its third wave per SIMD
+  // (175 VGPRs against 167; 11.7 against 10.4 ms on 4320 x 4320 x 90 -- EXPERIMENTS.md "K7q")
+  T mzc[SEG];
+  auto zmetric = [&](T (&dst)[SEG], int64_t k, bool first) {
+    if (mz.p && (first || mz.sz != 0)) load_rows<T, SEG>(dst, mz.p, mzo + k * mz.sz, mz.sy, mz.sx, nrow, (ntl & 16) != 0);
+  };
+  L prev;
+  if (per_z) prev = level(fetch(nz - 1));
+  L cur = level(fetch(0));
+  if (bc_z == XG_BC_EXTEND) prev = cur;
+  else if (bc_z == XG_BC_FILL) prev = padded();
+  if (MET) zmetric(mzc, 0, true);
+  for (int64_t k = 0;;) {
+    const int64_t kn = k + 1;
+    const bool more = kn < nf, read = kn < nz || (more && per_z);  // (`outer`, the last face: the pad below level nz-1)
+    Rows nxt;
+    if (read) nxt = fetch(kn < nz ? kn : 0);
+    face(k, prev, cur, mzc);
+    if (!more) break;
+    if (MET) zmetric(mzc, kn, false);
+    prev = cur;
+    if (read) cur = level(nxt);                      // (extend: the level itself, which `cur` still holds)
+    else if (bc_z == XG_BC_FILL) cur = padded();
+    k = kn;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -3676,6 +3889,71 @@ int xg_richardson_mixing(int dtype, const void* b, const void* u, const void* v,
                                  (float)nu_b, (float)kappa_b, (float)shear_floor, (float*)out_nu, (float*)out_kappa, shape,
                                  ndim, outer, bc_x, (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
   return fail(XG_ERR_INVALID, "richardson mixing: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+
+// K7q's launcher: a (lead, Z, Y, X) field of `shape`, both results with nz (`outer`: nz + 1) faces, three optional
+// broadcast metrics (mx and my at the field's levels, mz at the faces), one wave per column.  One ABI entry for both
+// element types (xg_isopycnal_slope, below).
+__attribute__((visibility("hidden"))) int xg_internal_islope_f64(
+    const double* b, const double* mx, const int64_t* mx_strides, const double* my, const int64_t* my_strides,
+    const double* mz, const int64_t* mz_strides, double* out_x, double* out_y, const int64_t* shape, int ndim, int outer,
+    int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_islope_f32(
+    const float* b, const float* mx, const int64_t* mx_strides, const float* my, const int64_t* my_strides, const float* mz,
+    const int64_t* mz_strides, float* out_x, float* out_y, const int64_t* shape, int ndim, int outer, int bc_x, float fill_x,
+    int bc_y, float fill_y, int bc_z, float fill_z, void* stream);
+
+int XG_FN(xg_internal_islope)(const real* b, const real* mx, const int64_t* mx_strides, const real* my,
+                              const int64_t* my_strides, const real* mz, const int64_t* mz_strides, real* out_x, real* out_y,
+                              const int64_t* shape, int ndim, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
+                              real fill_z, void* stream) {
+  const char* name = "isopycnal slope";
+  if (!b || !out_x || !out_y || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  VolIdx mi[3];  // mx and my at the field's levels, mz at the faces
+  const real* mp[3] = {mx, my, mz};
+  const int64_t* ms[3] = {mx_strides, my_strides, mz_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  FusedPlan p;
+  const bool al = aligned16(b) && aligned16(out_x) && aligned16(out_y);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  // bit 0: the lane neighbours by DPP (K7c, K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
+  int vnt = vec_nt_bits(1);
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool met = mx != nullptr || my != nullptr || mz != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_islope<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, out_x, out_y, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt); } while (0)
+#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument, the fills are cast to it here
+int xg_isopycnal_slope(int dtype, const void* b, const void* mx, const int64_t* mx_strides, const void* my,
+                       const int64_t* my_strides, const void* mz, const int64_t* mz_strides, void* out_x, void* out_y,
+                       const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
+                       double fill_z, void* stream) {
+  if (dtype == XG_T_F64)
+    return xg_internal_islope_f64((const double*)b, (const double*)mx, mx_strides, (const double*)my, my_strides,
+                                  (const double*)mz, mz_strides, (double*)out_x, (double*)out_y, shape, ndim, outer, bc_x,
+                                  fill_x, bc_y, fill_y, bc_z, fill_z, stream);
+  if (dtype == XG_T_F32)
+    return xg_internal_islope_f32((const float*)b, (const float*)mx, mx_strides, (const float*)my, my_strides,
+                                  (const float*)mz, mz_strides, (float*)out_x, (float*)out_y, shape, ndim, outer, bc_x,
+                                  (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
+  return fail(XG_ERR_INVALID, "isopycnal slope: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 #endif
 

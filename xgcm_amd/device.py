@@ -1470,6 +1470,33 @@ def richardson_mixing(b, u, v, mu, mv, mb, nu0: float, alpha: float, nu_b: float
     return nu, kappa
 
 
+def isopycnal_slope(b, mx, my, mz, outer: bool, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0, fill_y: float = 0.0,
+                    fill_z: float = 0.0):
+    """Fused isopycnal slopes at the faces of Z in one pass (xg_isopycnal_slope): the differences of `b` to the column / row
+    before, divided by `mx` / `my` (None = no division), their means with the difference after, the means of those with the
+    level above; the difference of `b` to the level above divided by `mz`; the two quotients, negated.  `outer` False: nz
+    faces (Z:left), padded above level 0; True: nz + 1 (Z:outer), padded on both sides.  `mx` and `my` broadcast against
+    `b`, `mz` against the results.  Returns (sx, sy)."""
+    lib = _MEM.lib()
+    dt, sfx = _common(b, mx, my, mz)
+    b = asdevice(b, dt)
+    if b.dim() < 3 or b.shape[-3] == 0:
+        raise ValueError("isopycnal_slope: the field needs (Z, Y, X) as its last three dims and a level along Z")
+    shape = list(b.shape)
+    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
+    mets = [_prep_metric(m, dt) for m in (mx, my, mz)]
+    sx, sy = _empty(fshape, dtype=dt, device=b.device), _empty(fshape, dtype=dt, device=b.device)
+    if sx.numel() == 0:
+        return sx, sy
+    margs = []
+    for m, against, what in zip(mets, (shape, shape, fshape), ("X metric", "Y metric", "Z metric at the faces")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
+    _check(lib.xg_isopycnal_slope(_hip.DTYPE["float32" if sfx == "f32" else "float64"], b.data_ptr(), *margs, sx.data_ptr(),
+                                  sy.data_ptr(), _hip.i64(shape), len(shape), int(bool(outer)), _hip.BC[bc_x], float(fill_x),
+                                  _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z), _stream()))
+    return sx, sy
+
+
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""

@@ -2232,6 +2232,112 @@ class Grid:
         outs = tuple(to_xarray(r) for r in outs) if was_xr else outs
         return outs if closure is not None else outs[0]
 
+    def isopycnal_slope(self, b, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", to=None, padding=None,
+                        fill_value=None, metric_weighted: bool = True):
+        """Slopes of the surfaces of constant b (buoyancy, density, any tracer), Sx = -(db/dx) / (db/dz) and
+        Sy = -(db/dy) / (db/dz) -- what Gent-McWilliams eddy transport, Redi diffusion and every isoneutral diagnostic
+        start from, at the centre points of the faces of Z, where MITgcm's gmredi forms them and `richardson_number`,
+        `richardson_mixing` and `vertical_diffusion` put their face fields -- in ONE pass: b is read once and both results
+        written once (24 B/cell in float64, against about 190 for the eleven launches of the chain); every intermediate
+        stays in registers.
+
+        b at (Z:center, Y:center, X:center), any leading dims, Z third from last; both results have dims (lead, Z face,
+        Y:center, X:center).  `to`: the face position on Z, "left" (nz faces) or "outer" (nz + 1); None: "outer" when the Z
+        axis has one, else "left", as in `richardson_number`.  Returns (sx, sy), bit-identical, dims, coords and names
+        included, to the chain
+
+            kw   = dict(padding=padding, fill_value=fill_value)
+            step = grid.derivative if metric_weighted else grid.diff
+            gx = grid.interp(grid.interp(step(b, x_axis, **kw), x_axis, **kw), z_axis, to=to, **kw)
+            gy = grid.interp(grid.interp(step(b, y_axis, **kw), y_axis, **kw), z_axis, to=to, **kw)
+            bz = step(b, z_axis, to=to, **kw)
+            sx, sy = -(gx / bz), -(gy / bz)
+
+        Sign convention: all three derivatives run along increasing index, so the result is the slope of the b-surfaces in
+        the grid's own Z coordinate, d(Z of the surface) / dx and / dy.  For a Z index that grows downward with positive
+        `drC` (MITgcm) that is the slope of their DEPTH: positive where the surface deepens towards larger x.
+
+        Pads where the chain pads, every stage its own input.  b left of column 0 / below row 0 (periodic: b[n-1], extend:
+        b[0], fill: `fill_value`); the DERIVATIVE right of the last column / above the last row (periodic: the derivative
+        at index 0, extend: at n-1, fill: `fill_value` itself); the LEVEL MEANS above level 0 and, "outer", below level
+        nz-1 (periodic: the far level's, extend: the level's own, fill: `fill_value` itself); b along Z as
+        `richardson_number` pads it.  No fused multiply-add, IEEE quotients, no guard on db/dz == 0: under `extend` the
+        outermost faces are x / 0.
+
+        Out of scope: slope clipping and tapering (GM's `clipping`, `gkw91`, `dm95`, `ldd97`), the natural follow-up.
+
+        The metrics are whatever `get_metric` returns for X at dims (lead, Z:center, Y:center, X:left), for Y at (lead,
+        Z:center, Y:left, X:center) and for Z at (lead, Z face, Y:center, X:center) (dxC, dyC, drC, or registered 3-D
+        arrays), one broadcast array each, read through strides; each may be absent on its own terms.
+
+        The chain itself runs (the same calls in the same order) for integer, float16 or mixed dtypes, for fewer than three
+        dims or Z not third from last, for b elsewhere than the centre, for another `to` or a position the axis lacks, for
+        a chunked input or chunked metrics, for a metric with dims its stage lacks, for a metric lookup that raises (the
+        chain raises it), for an axis without a boundary, for a field without a level along Z, and with face connections
+        or a fold along any of the three axes."""
+        arg = b
+        b, was_xr = self._wrap_in(b)
+        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
+        if to is None:
+            to = "outer" if "outer" in zax.coords else "left"
+        plan = None
+        served = (isinstance(b, DataArray) and b.ndim >= 3 and to in ("left", "outer") and to in zax.coords
+                  and all("center" in ax.coords for ax in (zax, yax, xax))
+                  and "left" in yax.coords and "left" in xax.coords and b.shape[-3] > 0
+                  and not gridops.complex_topology(self, z_axis))
+        if served:
+            tz, zf = zax.coords["center"], zax.coords[to]
+            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            lead = b.dims[:-3]
+            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
+            served = b.dims == lead + (tz, yc, xc) and not held & set(lead)
+        mets = [None, None, None]
+        if served:
+            f_shape = tuple(b.shape[:-3]) + (b.shape[-3] + (1 if to == "outer" else 0),) + tuple(b.shape[-2:])
+            c_dims = lead + (tz, yc, xc)
+            m_dims = [lead + (tz, yc, xl), lead + (tz, yl, xc), lead + (zf, yc, xc)]   # the three derivatives' dims
+            try:
+                if metric_weighted:
+                    for k, ax in enumerate((x_axis, y_axis, z_axis)):
+                        mets[k] = self._resident(self.get_metric(_DimsOnly(m_dims[k], b.name), (ax,), _layout=m_dims[k]), b.data)
+                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, m_dims))
+            except (KeyError, ValueError):
+                served = False  # (the chain raises it where the chain looks the metric up)
+        if served:
+            plan = self._second_order_plan([b], x_axis, y_axis, padding, fill_value, [m for m in mets if m is not None])
+        if plan is not None:
+            bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
+            fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
+            # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as it is
+            # (None: 0.0), so a -0.0 or a NaN keeps its bits on all three axes
+            fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
+            plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
+        if plan is None:
+            kw = dict(padding=padding, fill_value=fill_value)
+            step = self.derivative if metric_weighted else self.diff
+            gx = self.interp(self.interp(step(arg, x_axis, **kw), x_axis, **kw), z_axis, to=to, **kw)
+            gy = self.interp(self.interp(step(arg, y_axis, **kw), y_axis, **kw), z_axis, to=to, **kw)
+            bz = step(arg, z_axis, to=to, **kw)
+            return -(gx / bz), -(gy / bz)
+        bcx, bcy, fvx, fvy, bcz, fvz = plan
+        host = not _is_tensor(b.data)
+        mx, my, mz = (None if m is None else _aligned_view(m, dims) for m, dims in zip(mets, m_dims))
+        outs = _dev.isopycnal_slope(b.data, mx, my, mz, to == "outer", bcx, bcy, bcz, fvx, fvy, fvz)
+
+        # dims, coords and names as the chain's, step by step over placeholders: each derivative (named after its quotient
+        # with the metric), the mean back to the centre, the mean at the faces, the quotient (the negation changes neither)
+        def named(g, m):
+            return g if m is None else g._replace(name=_name_after(g.name, m))
+
+        bz = named(self._labels_of_step(b, m_dims[2], zf, f_shape), mets[2])
+        res = []
+        for k, (dim_l, dim_c) in enumerate(((xl, xc), (yl, yc))):
+            g = named(self._labels_of_step(b, m_dims[k], dim_l), mets[k])
+            g = self._labels_of_step(self._labels_of_step(g, c_dims, dim_c), m_dims[2], zf, f_shape)
+            res.append(self._labels_of_binary(g, bz))
+        outs = tuple(r._replace(data=_dev.tohost(out) if host else out) for r, out in zip(res, outs))
+        return tuple(to_xarray(r) for r in outs) if was_xr else outs
+
     # ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---------------------
     def _c_grid_vector(self, u, v, x_axis, y_axis, what):
         """dims of a C-grid vector's points: (lead, at u, at v, centre, vorticity point); raises when u / v sit elsewhere"""
