@@ -55,6 +55,7 @@
  *                      b, u and v, one pass (one entry likewise)
  *   xg_isopycnal_slope  -interp(interp(derivative(b, X | Y), X | Y), Z) / derivative(b, Z): the slopes of the b-surfaces at
  *                      the faces of Z, one pass (one entry likewise)
+ *   xg_redi_tensor      kappa * taper * (sx, sy, sx^2 + sy^2) of those slopes, the taper min(1, m2 / s2): one pass (likewise)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -545,6 +546,19 @@ int xg_isopycnal_slope(int dtype, const void* b, const void* mx, const int64_t* 
                        const int64_t* my_strides, const void* mz, const int64_t* mz_strides, void* out_x, void* out_y,
                        const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
                        double fill_z, void* stream);
+/* The tapered Redi / Gent-McWilliams tensor column at the faces of Z, one pass: xg_isopycnal_slope's sx and sy (its
+ * arguments, positions, pads and metrics), then
+ *   s2 = sx * sx + sy * sy
+ *   taper = 1:  ex = s2 - slope_max2    den = slope_max2 + (ex + |ex|) * 0.5    kt = kappa * (slope_max2 / den)
+ *   taper = 0:  kt = kappa
+ *   out_x = kt * sx    out_y = kt * sy    out_z = kt * s2                       no fused multiply-add, IEEE quotients
+ * kappa and slope_max2 (the SQUARE of the largest slope) are cast to the element type once.  Where s2 <= slope_max2 the
+ * taper is exactly 1; an infinite slope gives 0 * inf = NaN in all three results.  XG_ERR_INVALID on xg_isopycnal_slope's
+ * conditions, on a NULL out_z, on taper not 0 or 1 and on results that overlap; the results are untouched then. */
+int xg_redi_tensor(int dtype, const void* b, const void* mx, const int64_t* mx_strides, const void* my,
+                   const int64_t* my_strides, const void* mz, const int64_t* mz_strides, double kappa, double slope_max2,
+                   int taper, void* out_x, void* out_y, void* out_z, const int64_t* shape, int ndim, int outer, int bc_x,
+                   double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
 
 /* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
 /* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).

@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only; 5pp: richardson_mixing against its chain, alone only; 5is: isopycnal_slope against its chain, alone only), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only; 5pp: richardson_mixing against its chain, alone only; 5is: isopycnal_slope against its chain, alone only; 5rt: redi_tensor against its chain, alone or after 5is), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -380,6 +380,59 @@ def run_isopycnal_slope(reps, nz=90, n=4320):
     rec(5, "isopycnal_slope as its chain (11 launches), one-pass-equivalent bytes", med(tc), cells, bpc)
     print(json.dumps({"config": 5, "check": "one-pass isopycnal_slope == chain bit for bit at full size, both results", "ok": ok,
                       "interior_faces_finite": interior_finite, "speedup": round(med(tc) / med(tf), 2),
+                      "rounds_ms_fused": [round(t, 3) for t in tf], "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_redi_tensor(reps, nz=90, n=4320):
+    """redi_tensor in one pass against its chain (isopycnal_slope's one pass, then thirteen launches of array arithmetic:
+    the squares, their sum, the taper min(1, m2 / s2) without a branch, the three products; dxC, dyC and a profile drC(Zp1);
+    periodic / extend / extend, to="outer", kappa 1000, slope_max 1e-2), timed in turns, every paired round reported.  The
+    field 13 GB, the six results of the comparison 82 GB, the chain's live temporaries (the expression frees each as it
+    goes) about 95 GB beside the one pass's three results: about 190 GB at the peak, all 90 levels.  Under `extend` the
+    outermost faces are 0 * inf: the comparison is of the bits, a NaN equal to a NaN."""
+    coords = {"XC": ("XC", np.arange(n) + 0.5), "XG": ("XG", np.arange(n) * 1.0), "YC": ("YC", np.arange(n) + 0.5),
+              "YG": ("YG", np.arange(n) * 1.0), "Z": ("Z", np.arange(nz) + 0.5), "Zp1": ("Zp1", np.arange(nz + 1) * 1.0)}
+    ds = Dataset({"dxC": DataArray(D.synthetic((n, n), 31, 0, 1000.0, 1000.0), ("YC", "XG")),
+                  "dyC": DataArray(D.synthetic((n, n), 32, 0, 1000.0, 1000.0), ("YG", "XC")),
+                  "drC": DataArray(D.synthetic((nz + 1,), 34, 0, 10.0, 10.0), ("Zp1",))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                            "Z": {"center": "Z", "outer": "Zp1"}},
+                padding={"X": "periodic", "Y": "extend", "Z": "extend"},
+                metrics={("X",): ["dxC"], ("Y",): ["dyC"], ("Z",): ["drC"]}, autoparse_metadata=False)
+    B = DataArray(D.synthetic((nz, n, n), 63), ("Z", "YC", "XC"))
+    cells = nz * n * n
+    kappa, slope_max = 1000.0, 1e-2   # (the operator's defaults)
+
+    def chain():
+        sx, sy = grid.isopycnal_slope(B, to="outer")
+        s2 = sx * sx + sy * sy
+        m2 = float(slope_max) * float(slope_max)
+        ex = s2 - m2
+        den = m2 + (ex + abs(ex)) * 0.5
+        kt = kappa * (m2 / den)
+        return kt * sx, kt * sy, kt * s2
+
+    def same(g, w):
+        eq = g.data.view(torch.int64) == w.data.view(torch.int64)
+        eq |= torch.isnan(g.data) & torch.isnan(w.data)
+        return bool(eq.all())
+
+    one = lambda: grid.redi_tensor(B, kappa, slope_max, to="outer")  # noqa: E731
+    got, want = one(), chain()
+    ok = all(same(g, w) for g, w in zip(got, want))
+    interior_finite = all(bool(torch.isfinite(g.data[1:nz]).all()) for g in got)
+    tapered = float((got[2].data[1:nz] > 0.999 * kappa * slope_max * slope_max).double().mean())   # faces above the limit
+    del got, want
+    torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(one, chain, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    bpc = 32   # b, kwx, kwy and kwz (the 91st face of the results is not counted)
+    rec(5, "redi_tensor one pass: kwx, kwy, kwz from b, to=outer, dxC, dyC, drC(Zp1), periodic/extend/extend: 1 read + 3 writes", med(tf), cells, bpc)
+    rec(5, "redi_tensor as its chain (isopycnal_slope + 13 launches), one-pass-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": "one-pass redi_tensor == chain bit for bit at full size, all three results", "ok": ok,
+                      "interior_faces_finite": interior_finite, "fraction_of_interior_faces_tapered": round(tapered, 4),
+                      "speedup": round(med(tc) / med(tf), 2),
                       "rounds_ms_fused": [round(t, 3) for t in tf], "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
 
@@ -1082,6 +1135,8 @@ def main():
         run_richardson_mixing(a.reps)
     if "5is" in cfgs:   # (not part of 5x: about 120 GB)
         run_isopycnal_slope(a.reps)
+    if "5rt" in cfgs:   # (not part of 5x: about 190 GB)
+        run_redi_tensor(a.reps)
     ranks.close()
 
 

@@ -1025,6 +1025,45 @@ int islope(const R* b, const R* const arr[3], const int64_t* const st[3], R* out
   return XG_OK;
 }
 
+// the tensor column of the header: the slopes of `islope` into two temporaries, then the stages of the chain after them, one
+// operation each
+template <typename R>
+int reditensor(const R* b, const R* const arr[3], const int64_t* const st[3], R kappa, R m2, int taper, R* out_x, R* out_y,
+               R* out_z, const int64_t* shape, int ndim, int outer, const int bc[3], const R fill[3]) {
+  const char* name = "redi tensor";
+  if (!b || !out_x || !out_y || !out_z || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (taper != 0 && taper != 1) return fail(XG_ERR_INVALID, "%s: taper %d is neither 0 nor 1", name, taper);
+  int64_t n = 0;
+  if (ndim >= 3 && ndim <= XG_MAX_NDIM && (outer == 0 || outer == 1) && shape[ndim - 3] > 0) {
+    n = shape[ndim - 3] + outer;
+    for (int d = 0; d < ndim; ++d)
+      if (d != ndim - 3) n *= shape[d];
+    const R* r[3] = {out_x, out_y, out_z};
+    for (int i = 0; i < 3; ++i)
+      for (int j = i + 1; j < 3; ++j)
+        if (n > 0 && (uintptr_t)r[i] < (uintptr_t)(r[j] + n) && (uintptr_t)r[j] < (uintptr_t)(r[i] + n))
+          return fail(XG_ERR_INVALID, "%s: the results overlap", name);
+  }
+  std::vector<R> sx((size_t)n), sy((size_t)n);
+  // (every other condition is `islope`'s, which writes nothing when it refuses; the temporaries are never NULL to it)
+  R dummy[1];
+  const int rc = islope<R>(b, arr, st, n ? sx.data() : dummy, n ? sy.data() : dummy, shape, ndim, outer, bc, fill);
+  if (rc != XG_OK) return rc;
+  for (int64_t c = 0; c < n; ++c) {
+    const R s2 = sx[c] * sx[c] + sy[c] * sy[c];
+    R kt = kappa;
+    if (taper) {
+      const R ex = s2 - m2;
+      const R den = m2 + (ex + std::fabs(ex)) * R(0.5);
+      kt = kappa * (m2 / den);
+    }
+    out_x[c] = kt * sx[c];
+    out_y[c] = kt * sy[c];
+    out_z[c] = kt * s2;
+  }
+  return XG_OK;
+}
+
 // kinetic energy (ke_only) and the vector-invariant momentum advection of the header: the stages of the chain one after
 // the other over whole planes, each read through `get`, which pads a plane by one cell on one axis at a time (periodic:
 // the plane's own value at the wrapped index, extend: at the clamped index, fill: the fill value of that axis).
@@ -1644,6 +1683,27 @@ int xg_isopycnal_slope(int dtype, const void* b, const void* mx, const int64_t* 
     return islope<float>((const float*)b, arr, st, (float*)out_x, (float*)out_y, shape, ndim, outer, bc, fill);
   }
   return fail(XG_ERR_INVALID, "isopycnal slope: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+
+int xg_redi_tensor(int dtype, const void* b, const void* mx, const int64_t* mxs, const void* my, const int64_t* mys,
+                   const void* mz, const int64_t* mzs, double kappa, double slope_max2, int taper, void* out_x, void* out_y,
+                   void* out_z, const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y,
+                   int bc_z, double fill_z, void*) {
+  const int64_t* const st[3] = {mxs, mys, mzs};
+  const int bc[3] = {bc_x, bc_y, bc_z};
+  if (dtype == XG_T_F64) {
+    const double* const arr[3] = {(const double*)mx, (const double*)my, (const double*)mz};
+    const double fill[3] = {fill_x, fill_y, fill_z};
+    return reditensor<double>((const double*)b, arr, st, kappa, slope_max2, taper, (double*)out_x, (double*)out_y,
+                              (double*)out_z, shape, ndim, outer, bc, fill);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const arr[3] = {(const float*)mx, (const float*)my, (const float*)mz};
+    const float fill[3] = {(float)fill_x, (float)fill_y, (float)fill_z};
+    return reditensor<float>((const float*)b, arr, st, (float)kappa, (float)slope_max2, taper, (float*)out_x, (float*)out_y,
+                             (float*)out_z, shape, ndim, outer, bc, fill);
+  }
+  return fail(XG_ERR_INVALID, "redi tensor: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 
 int xg_convert(const void* src, int st, void* dst, int dt, uint64_t n, int via, double scale, int flags, void*) {

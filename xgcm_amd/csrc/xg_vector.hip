@@ -2822,6 +2822,212 @@ __global__ __launch_bounds__(BLOCK) void k_islope(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7r: the tapered Redi / Gent-McWilliams tensor column at the flux faces of Z in ONE pass over (lead, Z, Y, X), one field
+// in, three out (nz faces at Z:left, nz + 1 at Z:outer): K7q's sx and sy, line by line in its order, then
+//   s2 = sx * sx + sy * sy
+//   ex = s2 - m2      den = m2 + (ex + |ex|) * 0.5      kt = kappa * (m2 / den)       (`taper`; else kt = kappa)
+//   Kwx = kt * sx     Kwy = kt * sy     Kwz = kt * s2                                   (no FMA, IEEE quotients)
+// as the epilogue of every face, and three stores.  den is max(s2, m2) (Gerdes, Koeberle and Willebrand 1991: the taper is
+// min(1, m2 / s2), no square root): where s2 <= m2, ex + |ex| is +0.0, den is m2 and the taper exactly 1; an infinite slope
+// gives taper 0 and 0 * inf = NaN; a NaN stays one.  K7q is untouched: this kernel is a COPY of it up to sx and sy -- fetch,
+// level, padded, the metrics and the march (but for WHEN a level's rows are asked for, see the march) -- as K7p is of K7n.
+// b is read once and each result written once, 32 B/cell in float64.  kappa and m2 arrive in `real`; `taper` is
+// wave-uniform.
+// ------------------------------------------------------------------------------------------
+struct RediScalars {
+  real kappa, m2;
+  int taper;
+};
+
+template <int V, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_reditensor(
+    const real* __restrict__ b, real* __restrict__ out_x, real* __restrict__ out_y, real* __restrict__ out_z, int64_t o0,
+    u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int bc_x, real fill_x,
+    int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mx, VolIdx my, VolIdx mz, int ntl, RediScalars c) {
+  typedef typename VecT<V>::type T;
+  typedef IsRows<T, SEG> Rows;
+  typedef IsLevel<T, SEG> L;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  const int64_t nf = nz + outer;       // faces
+  // X and Y as K7q's: the columns left and right of the lane's vector, the row below and the row above the segment
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);
+  const bool per_x = bc_x == XG_BC_PERIODIC, per_z = bc_z == XG_BC_PERIODIC;
+  const bool fill_l = e.edge_l && bc_x == XG_BC_FILL;
+  const bool pad_r = e.edge_r && !per_x;
+  const bool fill_b = j0 == 0 && bc_y == XG_BC_FILL;
+  const int64_t jb = (j0 > 0) ? j0 - 1 : ((bc_y == XG_BC_PERIODIC) ? ny - 1 : 0);
+  const int64_t q = j0 + nrow;
+  const bool pad_t = q >= ny && bc_y != XG_BC_PERIODIC;
+  const int64_t jt = (q < ny) ? q : ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1);
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+
+  // the rows of mx and my of a level, as K7q holds them
+  T mxr[SEG], myr[SEG], myt;
+  real mxrr[SEG];
+  int64_t mxo = 0, mro = 0, myo = 0, mto = 0, mzo = 0;
+  auto hmetrics = [&](int64_t k, bool first) {
+    if (mx.p && (first || mx.sz != 0)) {
+      load_rows<T, SEG>(mxr, mx.p, mxo + k * mx.sz, mx.sy, mx.sx, nrow, (ntl & 4) != 0);
+      if (e.own_r) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) mxrr[s_] = mx.p[mro + k * mx.sz + ((s_ < nrow) ? s_ : nrow - 1) * mx.sy];
+      }
+    }
+    if (my.p && (first || my.sz != 0)) {
+      load_rows<T, SEG>(myr, my.p, myo + k * my.sz, my.sy, my.sx, nrow, (ntl & 8) != 0);
+      T top[1];
+      load_rows<T, 1>(top, my.p, mto + k * my.sz, my.sy, my.sx, 1, (ntl & 8) != 0);
+      myt = top[0];
+    }
+  };
+  if (MET) {
+    const int64_t xo = mx.p ? area_outer_off(mx.ai, o) : 0, yo = my.p ? area_outer_off(my.ai, o) : 0;
+    mxo = xo + j0 * mx.sy + i0 * mx.sx;
+    mro = xo + j0 * mx.sy + e.ridx * mx.sx;
+    myo = yo + j0 * my.sy + i0 * my.sx;
+    mto = yo + jt * my.sy + i0 * my.sx;
+    if (mz.p) mzo = area_outer_off(mz.ai, o) + j0 * mz.sy + i0 * mz.sx;
+    hmetrics(0, true);
+  }
+
+  auto fetch = [&](int64_t k) -> Rows {  // (with the level's own mx and my rows: `level` is the only reader of both)
+    Rows x;
+    const int64_t lv = col + k * plane;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.bb[s_] = *reinterpret_cast<const T*>(b + lv + ro[s_] + i0);
+      x.bl[s_] = e.own_l ? b[lv + ro[s_] + e.lidx] : real(0);
+      x.br[s_] = e.own_r ? b[lv + ro[s_] + e.ridx] : real(0);
+    }
+    x.below = *reinterpret_cast<const T*>(b + lv + jb * nx + i0);
+    x.above = *reinterpret_cast<const T*>(b + lv + jt * nx + i0);
+    if (MET) hmetrics(k, false);
+    return x;
+  };
+  // G_x, G_y and b of the segment from the rows of a level
+  auto level = [&](const Rows& x) -> L {
+    L r;
+    T g[SEG], h[SEG];
+    real gr[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      real left = x.bl[s_];
+      if (e.shl) {
+        const real dpp = from_lane_below(vec_last(x.bb[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+        if (!e.own_l) left = dpp;
+      }
+      if (fill_l) left = fill_x;
+      g[s_] = dvdx_of(x.bb[s_], left);
+      gr[s_] = x.br[s_] - vec_last(x.bb[s_]);
+      const T lower = (s_ == 0) ? (fill_b ? splat<T>(fill_y) : x.below) : x.bb[(s_ > 0) ? s_ - 1 : 0];
+      h[s_] = x.bb[s_] - lower;
+    }
+    T top = x.above - x.bb[SEG - 1];  // (short tails repeat the last row: bb[SEG - 1] is row nrow - 1)
+    if (MET) {
+      if (mx.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) g[s_] = g[s_] / mxr[s_];
+        if (e.own_r) {
+#pragma unroll
+          for (int s_ = 0; s_ < SEG; ++s_) gr[s_] = gr[s_] / mxrr[s_];
+        }
+      }
+      if (my.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) h[s_] = h[s_] / myr[s_];
+        top = top / myt;
+      }
+    }
+    if (e.shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real right = from_lane_above(vec_first(g[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+        if (!e.own_r) gr[s_] = right;
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (pad_r) gr[s_] = (bc_x == XG_BC_FILL) ? fill_x : vec_last(g[s_]);
+      r.gx[s_] = interp_right_of(g[s_], gr[s_]);
+      T up = (s_ + 1 < nrow) ? h[(s_ + 1 < SEG) ? s_ + 1 : s_] : top;
+      if (s_ + 1 >= nrow && pad_t) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : h[s_];
+      r.gy[s_] = op2<XG_OP_INTERP>(h[s_], up);
+      r.bb[s_] = x.bb[s_];
+    }
+    return r;
+  };
+  auto padded = [&]() -> L {  // a level of the fill value: the pad of the level means and of b
+    L r;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) r.gx[s_] = r.gy[s_] = r.bb[s_] = splat<T>(fill_z);
+    return r;
+  };
+
+  // one face from the level above it (`lo`) and the level below it (`hi`): K7q's slopes, then the tensor column, one
+  // operation per line of the chain
+  const int64_t po = o * nf * plane + j0 * nx + i0;
+  const T minus = splat<T>(real(-1)), half = splat<T>(real(0.5)), m2 = splat<T>(c.m2), kappa = splat<T>(c.kappa);
+  const bool taper = c.taper != 0;
+  auto face = [&](int64_t k, const L& lo, const L& hi, const T (&mzr)[SEG]) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        const T gx = op2<XG_OP_INTERP>(lo.gx[s_], hi.gx[s_]);
+        const T gy = op2<XG_OP_INTERP>(lo.gy[s_], hi.gy[s_]);
+        T bz = op2<XG_OP_DIFF>(lo.bb[s_], hi.bb[s_]);
+        if (MET) {
+          if (mz.p) bz = bz / mzr[s_];
+        }
+        const T sx = minus * (gx / bz);
+        const T sy = minus * (gy / bz);
+        const T s2 = sx * sx + sy * sy;
+        T kt = kappa;
+        if (taper) {
+          const T ex = s2 - m2;
+          const T den = m2 + (ex + __builtin_elementwise_abs(ex)) * half;
+          kt = kappa * (m2 / den);
+        }
+        const int64_t at = po + k * plane + s_ * nx;
+        stg_s<T, NTS>(out_x + at, kt * sx);
+        stg_s<T, NTS>(out_y + at, kt * sy);
+        stg_s<T, NTS>(out_z + at, kt * s2);
+      }
+    }
+  };
+
+  // the march keeps the level above the face, as K7q's; the rows of the level below the NEXT face are asked for AFTER the
+  // face, not before it as in K7q: with a third product, a third quotient and s2 alive through the epilogue, rows in flight
+  // beside it cost the float64 metric instance its third wave per SIMD (171 VGPRs, 14.7 ms on 4320 x 4320 x 90); the rows
+  // ahead without the two edge elements keep it (162) at 13.0 - 13.2 ms, nothing ahead (144) runs in 11.5 ms
+  // (EXPERIMENTS.md "K7r").  The next face's mz rows are asked for after the face, as in K7q
+  T mzc[SEG];
+  auto zmetric = [&](T (&dst)[SEG], int64_t k, bool first) {
+    if (mz.p && (first || mz.sz != 0)) load_rows<T, SEG>(dst, mz.p, mzo + k * mz.sz, mz.sy, mz.sx, nrow, (ntl & 16) != 0);
+  };
+  L prev;
+  if (per_z) prev = level(fetch(nz - 1));
+  L cur = level(fetch(0));
+  if (bc_z == XG_BC_EXTEND) prev = cur;
+  else if (bc_z == XG_BC_FILL) prev = padded();
+  if (MET) zmetric(mzc, 0, true);
+  for (int64_t k = 0;;) {
+    const int64_t kn = k + 1;
+    const bool more = kn < nf, read = kn < nz || (more && per_z);  // (`outer`, the last face: the pad below level nz-1)
+    face(k, prev, cur, mzc);
+    if (!more) break;
+    if (MET) zmetric(mzc, kn, false);
+    prev = cur;
+    if (read) cur = level(fetch(kn < nz ? kn : 0));  // (extend: the level itself, which `cur` still holds)
+    else if (bc_z == XG_BC_FILL) cur = padded();
+    k = kn;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -3954,6 +4160,86 @@ int xg_isopycnal_slope(int dtype, const void* b, const void* mx, const int64_t* 
                                   (const float*)mz, mz_strides, (float*)out_x, (float*)out_y, shape, ndim, outer, bc_x,
                                   (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
   return fail(XG_ERR_INVALID, "isopycnal slope: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+
+// K7r's launcher: K7q's, with a third result and the two scalars of the tensor (already in `real`) and the taper flag
+__attribute__((visibility("hidden"))) int xg_internal_reditensor_f64(
+    const double* b, const double* mx, const int64_t* mx_strides, const double* my, const int64_t* my_strides,
+    const double* mz, const int64_t* mz_strides, double kappa, double slope_max2, int taper, double* out_x, double* out_y,
+    double* out_z, const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z,
+    double fill_z, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_reditensor_f32(
+    const float* b, const float* mx, const int64_t* mx_strides, const float* my, const int64_t* my_strides, const float* mz,
+    const int64_t* mz_strides, float kappa, float slope_max2, int taper, float* out_x, float* out_y, float* out_z,
+    const int64_t* shape, int ndim, int outer, int bc_x, float fill_x, int bc_y, float fill_y, int bc_z, float fill_z,
+    void* stream);
+
+int XG_FN(xg_internal_reditensor)(const real* b, const real* mx, const int64_t* mx_strides, const real* my,
+                                  const int64_t* my_strides, const real* mz, const int64_t* mz_strides, real kappa,
+                                  real slope_max2, int taper, real* out_x, real* out_y, real* out_z, const int64_t* shape,
+                                  int ndim, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z,
+                                  void* stream) {
+  const char* name = "redi tensor";
+  if (!b || !out_x || !out_y || !out_z || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (taper != 0 && taper != 1) return fail(XG_ERR_INVALID, "%s: taper %d is neither 0 nor 1", name, taper);
+  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  {  // the three results, (lead, nz + outer, ny, nx) each, may not overlap
+    int64_t n = shape[ndim - 3] + outer;
+    for (int d = 0; d < ndim; ++d)
+      if (d != ndim - 3) n *= shape[d];
+    const real* r[3] = {out_x, out_y, out_z};
+    for (int i = 0; i < 3; ++i)
+      for (int j = i + 1; j < 3; ++j)
+        if (n > 0 && (uintptr_t)r[i] < (uintptr_t)(r[j] + n) && (uintptr_t)r[j] < (uintptr_t)(r[i] + n))
+          return fail(XG_ERR_INVALID, "%s: the results overlap", name);
+  }
+  VolIdx mi[3];  // mx and my at the field's levels, mz at the faces
+  const real* mp[3] = {mx, my, mz};
+  const int64_t* ms[3] = {mx_strides, my_strides, mz_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  FusedPlan p;
+  const bool al = aligned16(b) && aligned16(out_x) && aligned16(out_y) && aligned16(out_z);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  // bit 0: the lane neighbours by DPP (K7c, K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
+  int vnt = vec_nt_bits(1);
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool met = mx != nullptr || my != nullptr || mz != nullptr;
+  const RediScalars c = {kappa, slope_max2, taper};
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_reditensor<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, out_x, out_y, out_z, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt, c); } while (0)
+#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument; the fills, kappa and
+// slope_max2 are cast to it here, once
+int xg_redi_tensor(int dtype, const void* b, const void* mx, const int64_t* mx_strides, const void* my,
+                   const int64_t* my_strides, const void* mz, const int64_t* mz_strides, double kappa, double slope_max2,
+                   int taper, void* out_x, void* out_y, void* out_z, const int64_t* shape, int ndim, int outer, int bc_x,
+                   double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream) {
+  if (dtype == XG_T_F64)
+    return xg_internal_reditensor_f64((const double*)b, (const double*)mx, mx_strides, (const double*)my, my_strides,
+                                      (const double*)mz, mz_strides, kappa, slope_max2, taper, (double*)out_x, (double*)out_y,
+                                      (double*)out_z, shape, ndim, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, stream);
+  if (dtype == XG_T_F32)
+    return xg_internal_reditensor_f32((const float*)b, (const float*)mx, mx_strides, (const float*)my, my_strides,
+                                      (const float*)mz, mz_strides, (float)kappa, (float)slope_max2, taper, (float*)out_x,
+                                      (float*)out_y, (float*)out_z, shape, ndim, outer, bc_x, (float)fill_x, bc_y,
+                                      (float)fill_y, bc_z, (float)fill_z, stream);
+  return fail(XG_ERR_INVALID, "redi tensor: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 #endif
 

@@ -1497,6 +1497,35 @@ def isopycnal_slope(b, mx, my, mz, outer: bool, bc_x: str, bc_y: str, bc_z: str,
     return sx, sy
 
 
+def redi_tensor(b, mx, my, mz, kappa: float, slope_max2, outer: bool, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0,
+                fill_y: float = 0.0, fill_z: float = 0.0):
+    """Fused tapered Redi / Gent-McWilliams tensor column at the faces of Z in one pass (xg_redi_tensor): the slopes sx and
+    sy of `isopycnal_slope` (its arguments), s2 = sx * sx + sy * sy, and kt * sx, kt * sy, kt * s2 with
+    kt = kappa * (slope_max2 / max(s2, slope_max2)), the maximum as m2 + (ex + |ex|) * 0.5 over ex = s2 - m2; `slope_max2`
+    (the SQUARE of the largest slope) None: kt = kappa, no taper.  Both scalars are cast to the fields' dtype once.
+    Returns (kwx, kwy, kwz)."""
+    lib = _MEM.lib()
+    dt, sfx = _common(b, mx, my, mz)
+    b = asdevice(b, dt)
+    if b.dim() < 3 or b.shape[-3] == 0:
+        raise ValueError("redi_tensor: the field needs (Z, Y, X) as its last three dims and a level along Z")
+    shape = list(b.shape)
+    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
+    mets = [_prep_metric(m, dt) for m in (mx, my, mz)]
+    outs = tuple(_empty(fshape, dtype=dt, device=b.device) for _ in range(3))
+    if outs[0].numel() == 0:
+        return outs
+    margs = []
+    for m, against, what in zip(mets, (shape, shape, fshape), ("X metric", "Y metric", "Z metric at the faces")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
+    taper = slope_max2 is not None
+    _check(lib.xg_redi_tensor(_hip.DTYPE["float32" if sfx == "f32" else "float64"], b.data_ptr(), *margs, float(kappa),
+                              float(slope_max2) if taper else 0.0, int(taper), *(o.data_ptr() for o in outs), _hip.i64(shape),
+                              len(shape), int(bool(outer)), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y),
+                              _hip.BC[bc_z], float(fill_z), _stream()))
+    return outs
+
+
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""

@@ -2275,7 +2275,57 @@ class Grid:
         a chunked input or chunked metrics, for a metric with dims its stage lacks, for a metric lookup that raises (the
         chain raises it), for an axis without a boundary, for a field without a level along Z, and with face connections
         or a fold along any of the three axes."""
-        arg = b
+        return self._isopycnal(b, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted)
+
+    def redi_tensor(self, b, kappa=1000.0, slope_max=1e-2, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", to=None,
+                    padding=None, fill_value=None, metric_weighted: bool = True):
+        """The tapered tensor column Kwx, Kwy, Kwz of Redi isoneutral diffusion and the Gent-McWilliams skew flux at the W
+        points, as MITgcm's `gmredi_calc_tensor` forms it -- Kwx = kappa taper Sx, Kwy = kappa taper Sy,
+        Kwz = kappa taper (Sx^2 + Sy^2), the last the diffusivity `implicit_vertical_diffusion` takes as its 3-D `kappa`, at
+        its position -- in ONE pass: b is read once and the three results written once (32 B/cell in float64, against about
+        300 for `isopycnal_slope` and the thirteen launches after it); the slopes and every other intermediate stay in
+        registers.
+
+        Positions, `to`, pads, metrics and leading dims are `isopycnal_slope`'s: b at the centre, Z third from last; all
+        three results have dims (lead, Z face, Y:center, X:center).  Returns (kwx, kwy, kwz), bit-identical, dims, coords
+        and names included, to the chain
+
+            kw = dict(padding=padding, fill_value=fill_value)
+            sx, sy = grid.isopycnal_slope(b, x_axis, y_axis, z_axis, to=to, metric_weighted=metric_weighted, **kw)
+            s2 = sx * sx + sy * sy
+            if slope_max is None:                    # untapered
+                kt = kappa
+            else:                                    # Gerdes-Koeberle-Willebrand 1991: taper = min(1, (Smax/|S|)^2), no sqrt
+                m2  = float(slope_max) * float(slope_max)   # one Python product, cast to the fields' dtype once
+                ex  = s2 - m2
+                den = m2 + (ex + abs(ex)) * 0.5      # max(s2, m2)
+                kt  = kappa * (m2 / den)
+            kwx, kwy, kwz = kt * sx, kt * sy, kt * s2
+
+        Every operation is in the fields' dtype; no fused multiply-add, IEEE quotients.  The defaults are MITgcm's usual GM
+        background diffusivity (m2/s) and `GM_maxSlope`: an interface choice, nothing measured.
+
+        Exact identity below the limit: where s2 <= m2, `ex + abs(ex)` is exactly +0.0, `den` is exactly m2 and the taper
+        exactly 1, so the results carry the bits of kappa * sx, kappa * sy and kappa * s2 -- those of `slope_max=None`.
+        Bound above the limit: where s2 > m2 the taper is at most 1 and kwz stays near kappa m2 for every finite s2,
+        kwz <= kappa m2 (1 + 4 eps): `den` is m2 + (s2 - m2), two roundings from s2, the quotient adds one and each of the
+        two products one.  No guard on db/dz == 0, as in `isopycnal_slope`: an infinite slope gives taper 0 and
+        0 * inf = NaN in all three results, so the outermost faces under `extend` with "outer" are NaN; the implicit solves
+        never read those faces.  A NaN stays NaN.  float32 range: sx * sx overflows above about 1.8e19; the operator does
+        what the chain does.
+
+        Out of scope: other tapers (`clipping`, `dm95`, `ldd97`: tanh cannot be held to numpy bit for bit) and the U- and
+        V-point tensor components.
+
+        The one pass serves the call when `isopycnal_slope`'s would (the list in its docstring) and `kappa` and `slope_max`
+        are each a Python int or float, or a numpy floating scalar that does not promote the fields' dtype (`slope_max` may
+        be None).  For anything else (an array-valued kappa, a numpy scalar of a wider type) the chain above itself runs,
+        the same calls in the same order, raising what it raises; neither scalar is validated beyond that."""
+        return self._isopycnal(b, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted, tensor=(kappa, slope_max))
+    def _isopycnal(self, b, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted, tensor=None):
+        """`isopycnal_slope`: one launch of K7q, or its chain.  `tensor` (kappa, slope_max): `redi_tensor`, one launch of
+        K7r, or its chain"""
+        arg, to_arg = b, to
         b, was_xr = self._wrap_in(b)
         zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
         if to is None:
@@ -2312,6 +2362,22 @@ class Grid:
             # (None: 0.0), so a -0.0 or a NaN keeps its bits on all three axes
             fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
             plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
+        if plan is not None and tensor is not None and not (_weak_scalar(tensor[0], b.data)
+                                                            and (tensor[1] is None or _weak_scalar(tensor[1], b.data))):
+            plan = None   # (an array, a wider numpy scalar: the chain's own promotion)
+        if plan is None and tensor is not None:
+            kappa, slope_max = tensor
+            kw = dict(padding=padding, fill_value=fill_value)
+            sx, sy = self.isopycnal_slope(arg, x_axis, y_axis, z_axis, to=to_arg, metric_weighted=metric_weighted, **kw)
+            s2 = sx * sx + sy * sy
+            if slope_max is None:
+                kt = kappa
+            else:
+                m2 = float(slope_max) * float(slope_max)
+                ex = s2 - m2
+                den = m2 + (ex + abs(ex)) * 0.5
+                kt = kappa * (m2 / den)
+            return kt * sx, kt * sy, kt * s2
         if plan is None:
             kw = dict(padding=padding, fill_value=fill_value)
             step = self.derivative if metric_weighted else self.diff
@@ -2322,7 +2388,11 @@ class Grid:
         bcx, bcy, fvx, fvy, bcz, fvz = plan
         host = not _is_tensor(b.data)
         mx, my, mz = (None if m is None else _aligned_view(m, dims) for m, dims in zip(mets, m_dims))
-        outs = _dev.isopycnal_slope(b.data, mx, my, mz, to == "outer", bcx, bcy, bcz, fvx, fvy, fvz)
+        if tensor is not None:
+            m2 = None if tensor[1] is None else float(tensor[1]) * float(tensor[1])
+            outs = _dev.redi_tensor(b.data, mx, my, mz, float(tensor[0]), m2, to == "outer", bcx, bcy, bcz, fvx, fvy, fvz)
+        else:
+            outs = _dev.isopycnal_slope(b.data, mx, my, mz, to == "outer", bcx, bcy, bcz, fvx, fvy, fvz)
 
         # dims, coords and names as the chain's, step by step over placeholders: each derivative (named after its quotient
         # with the metric), the mean back to the centre, the mean at the faces, the quotient (the negation changes neither)
@@ -2335,6 +2405,13 @@ class Grid:
             g = named(self._labels_of_step(b, m_dims[k], dim_l), mets[k])
             g = self._labels_of_step(self._labels_of_step(g, c_dims, dim_c), m_dims[2], zf, f_shape)
             res.append(self._labels_of_binary(g, bz))
+        if tensor is not None:
+            # sx * sx + sy * sy; every step with a scalar keeps coords and name, so kt (tapered) carries those of s2 and
+            # kappa (untapered) none of its own
+            lx, ly = res
+            s2 = self._labels_of_binary(self._labels_of_binary(lx, lx), self._labels_of_binary(ly, ly))
+            both = self._labels_of_binary
+            res = [lx, ly, s2] if tensor[1] is None else [both(s2, lx), both(s2, ly), both(s2, s2)]
         outs = tuple(r._replace(data=_dev.tohost(out) if host else out) for r, out in zip(res, outs))
         return tuple(to_xarray(r) for r in outs) if was_xr else outs
 
