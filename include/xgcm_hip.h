@@ -56,6 +56,8 @@
  *   xg_isopycnal_slope  -interp(interp(derivative(b, X | Y), X | Y), Z) / derivative(b, Z): the slopes of the b-surfaces at
  *                      the faces of Z, one pass (one entry likewise)
  *   xg_redi_tensor      kappa * taper * (sx, sy, sx^2 + sy^2) of those slopes, the taper min(1, m2 / s2): one pass (likewise)
+ *   xg_redi_vertical_flux_divergence  d/dz(kwx * gx + kwy * gy) of a tracer, gx and gy its level means at the faces: one
+ *                      pass (likewise)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -559,6 +561,20 @@ int xg_redi_tensor(int dtype, const void* b, const void* mx, const int64_t* mx_s
                    const int64_t* my_strides, const void* mz, const int64_t* mz_strides, double kappa, double slope_max2,
                    int taper, void* out_x, void* out_y, void* out_z, const int64_t* shape, int ndim, int outer, int bc_x,
                    double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
+/* The divergence of the off-diagonal vertical isoneutral flux of a tracer `a` of `shape` (.., Z, Y, X), one pass: with G_x,
+ * G_y the level means of xg_isopycnal_slope formed of `a` (its X and Y pads, mx and my),
+ *   gx = (G_x[k-1] + G_x[k]) * 0.5    gy = (G_y[k-1] + G_y[k]) * 0.5    f[k] = kwx[k] * gx + kwy[k] * gy
+ *   out[k] = (f[k+1] - f[k]) [/ mc[k]]                                      no fused multiply-add, IEEE quotients
+ * kwx and kwy are contiguous with nz faces (`outer` = 1: nz + 1), the results of xg_redi_tensor; mx, my and mc broadcast
+ * against `a`; out has `shape`.  closed = 1: f at face 0 and, `outer`, at face nz is +0.0 -- kwx, kwy and every pad along Z
+ * there are never read.  closed = 0: the level means above level 0 and, `outer`, below level nz-1 padded as
+ * xg_isopycnal_slope's.  outer = 0: the flux beyond level nz-1 padded as xg_vertical_diffusion's (periodic: f[0], extend:
+ * f[nz-1], fill: fill_z itself).  XG_ERR_INVALID on xg_isopycnal_slope's conditions, on a NULL kwx or kwy and on closed not
+ * 0 or 1; the result is untouched then. */
+int xg_redi_vertical_flux_divergence(int dtype, const void* a, const void* kwx, const void* kwy, const void* mx,
+                                     const int64_t* mx_strides, const void* my, const int64_t* my_strides, const void* mc,
+                                     const int64_t* mc_strides, void* out, const int64_t* shape, int ndim, int outer, int closed,
+                                     int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
 
 /* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
 /* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).

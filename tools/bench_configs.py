@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only; 5pp: richardson_mixing against its chain, alone only; 5is: isopycnal_slope against its chain, alone only; 5rt: redi_tensor against its chain, alone or after 5is), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only; 5pp: richardson_mixing against its chain, alone only; 5is: isopycnal_slope against its chain, alone only; 5rt: redi_tensor against its chain, alone or after 5is; 5rf: redi_vertical_flux_divergence against its chain, alone only), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -433,6 +433,65 @@ def run_redi_tensor(reps, nz=90, n=4320):
     print(json.dumps({"config": 5, "check": "one-pass redi_tensor == chain bit for bit at full size, all three results", "ok": ok,
                       "interior_faces_finite": interior_finite, "fraction_of_interior_faces_tapered": round(tapered, 4),
                       "speedup": round(med(tc) / med(tf), 2),
+                      "rounds_ms_fused": [round(t, 3) for t in tf], "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_redi_vertical_flux_divergence(reps, nz=90, n=4320):
+    """redi_vertical_flux_divergence in one pass against its chain (two derivatives, four interpolations, two products, their
+    sum, the copy that closes the top and the bottom faces, the derivative back to the centre: ten launches and the copy;
+    dxC, dyC, drF(Z); periodic / extend / extend, to="outer", closed=True), timed in turns, every paired round reported.
+    kwx and kwy are `redi_tensor(b)`'s at its defaults, as they are: their outermost faces are NaN (0 * inf), which a closed
+    call never reads; the tracer is a second synthetic field.  By the count of its launches the chain moves about 200 B/cell
+    (3 x 16 for each of gx and gy, 24 for each product and for the sum, 16 for the copy, 16 for the last derivative) against
+    the one pass's 32.  The tracer and the two tensor columns 40 GB, the two results of the comparison 27 GB, the chain's live
+    temporaries (the expression frees each as it goes) about 55 GB; b and kwz are freed before the timing: about 125 GB at the
+    peak, all 90 levels."""
+    coords = {"XC": ("XC", np.arange(n) + 0.5), "XG": ("XG", np.arange(n) * 1.0), "YC": ("YC", np.arange(n) + 0.5),
+              "YG": ("YG", np.arange(n) * 1.0), "Z": ("Z", np.arange(nz) + 0.5), "Zp1": ("Zp1", np.arange(nz + 1) * 1.0)}
+    ds = Dataset({"dxC": DataArray(D.synthetic((n, n), 31, 0, 1000.0, 1000.0), ("YC", "XG")),
+                  "dyC": DataArray(D.synthetic((n, n), 32, 0, 1000.0, 1000.0), ("YG", "XC")),
+                  "drC": DataArray(D.synthetic((nz + 1,), 34, 0, 10.0, 10.0), ("Zp1",)),
+                  "drF": DataArray(D.synthetic((nz,), 33, 0, 10.0, 10.0), ("Z",))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                            "Z": {"center": "Z", "outer": "Zp1"}},
+                padding={"X": "periodic", "Y": "extend", "Z": "extend"},
+                metrics={("X",): ["dxC"], ("Y",): ["dyC"], ("Z",): ["drC", "drF"]}, autoparse_metadata=False)
+    B = DataArray(D.synthetic((nz, n, n), 63), ("Z", "YC", "XC"))
+    kwx, kwy, kwz = grid.redi_tensor(B)
+    del B, kwz
+    torch.cuda.empty_cache()
+    A = DataArray(D.synthetic((nz, n, n), 64), ("Z", "YC", "XC"))
+    cells = nz * n * n
+
+    def chain():
+        gx = grid.interp(grid.interp(grid.derivative(A, "X"), "X"), "Z", to="outer")
+        gy = grid.interp(grid.interp(grid.derivative(A, "Y"), "Y"), "Z", to="outer")
+        f = kwx * gx + kwy * gy
+        del gx, gy
+        data = f.data.clone()     # the closed top and bottom: no flux
+        data[0] = 0.0
+        data[nz] = 0.0
+        return grid.derivative(f._replace(data=data), "Z")
+
+    one = lambda: grid.redi_vertical_flux_divergence(A, kwx, kwy)  # noqa: E731   (the defaults: to="outer", closed=True)
+    got, want = one(), chain()
+    eq = got.data.view(torch.int64) == want.data.view(torch.int64)
+    eq |= torch.isnan(got.data) & torch.isnan(want.data)
+    ok = bool(eq.all())
+    finite = bool(torch.isfinite(got.data).all())
+    nonzero = float((got.data != 0).double().mean())
+    nan_faces = bool(torch.isnan(kwx.data[0]).all() and torch.isnan(kwx.data[nz]).all())
+    del got, want, eq
+    torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(one, chain, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    bpc = 32   # a, kwx, kwy and the result (the 91st face of kwx and kwy is not counted)
+    rec(5, "redi_vertical_flux_divergence one pass: a, kwx, kwy in, to=outer, closed, dxC, dyC, drF(Z), periodic/extend/extend: 3 reads + 1 write", med(tf), cells, bpc)
+    rec(5, "redi_vertical_flux_divergence as its chain (10 launches and the closing copy), one-pass-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": "one-pass redi_vertical_flux_divergence == chain bit for bit at full size", "ok": ok,
+                      "result_finite_everywhere": finite, "fraction_of_cells_nonzero": round(nonzero, 4),
+                      "outermost_faces_of_kwx_are_nan": nan_faces, "speedup": round(med(tc) / med(tf), 2),
                       "rounds_ms_fused": [round(t, 3) for t in tf], "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
 
@@ -1137,6 +1196,8 @@ def main():
         run_isopycnal_slope(a.reps)
     if "5rt" in cfgs:   # (not part of 5x: about 190 GB)
         run_redi_tensor(a.reps)
+    if "5rf" in cfgs:   # (not part of 5x: about 125 GB)
+        run_redi_vertical_flux_divergence(a.reps)
     ranks.close()
 
 

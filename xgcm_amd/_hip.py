@@ -222,8 +222,11 @@ SIGNATURES["xg_isopycnal_slope"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i6
 SIGNATURES["xg_redi_tensor"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_double, C.c_double, C.c_int, _vp, _vp,
                                         _vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double,
                                         _vp])
+SIGNATURES["xg_redi_vertical_flux_divergence"] = (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p,
+                                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
+                                                          C.c_int, C.c_double, _vp])
 
-SUFFIX = {"float64": "f64", "float32": "f32", "int64": "i64", "int32": "i32"}
+SUFFIX ={"float64": "f64", "float32": "f32", "int64": "i64", "int32": "i32"}
 
 _lib: Optional[C.CDLL] = None
 

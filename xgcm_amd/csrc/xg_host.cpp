@@ -1064,6 +1064,105 @@ int reditensor(const R* b, const R* const arr[3], const int64_t* const st[3], R 
   return XG_OK;
 }
 
+// the divergence of the off-diagonal vertical isoneutral flux of the header as the stages of its chain over one (Z, Y, X)
+// volume at a time, each into a temporary: stages (1) and (2) of `islope` on `a`, the level means at the faces, the two
+// products, their sum, the closed faces, the difference of the flux to the next face's over the result's metric.
+// arr[] = {mx, my, mc}, all at the field's levels
+template <typename R>
+int rediflux(const R* a, const R* kwx, const R* kwy, const R* const arr[3], const int64_t* const st[3], R* out,
+             const int64_t* shape, int ndim, int outer, int closed, const int bc[3], const R fill[3]) {  // bc, fill: X, Y, Z
+  const char* name = "redi vertical flux divergence";
+  if (!a || !kwx || !kwy || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "%s: ndim %d not in [3,%d]", name, ndim, XG_MAX_NDIM);
+  for (int k = 0; k < 3; ++k)
+    if (bc[k] < XG_BC_PERIODIC || bc[k] > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "%s: boundary mode %d: periodic, fill or extend", name, bc[k]);
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (closed != 0 && closed != 1) return fail(XG_ERR_INVALID, "%s: closed %d is neither 0 nor 1", name, closed);
+  for (int k = 0; k < 3; ++k)
+    if (arr[k] && !st[k]) return fail(XG_ERR_INVALID, "%s: metric without strides", name);
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx, vol = nz * plane;
+  if (nz == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  const int64_t nf = nz + outer;  // faces
+  int64_t lead = 1;
+  for (int d = 0; d < ndim - 3; ++d) lead *= shape[d];
+  if (lead == 0 || vol == 0) return XG_OK;
+  const int64_t n[3] = {nx, ny, nz}, step[3] = {1, nx, plane};
+  std::vector<R> g((size_t)vol), G[2], gf((size_t)(nf * plane)), f((size_t)(nf * plane));
+  G[0].resize((size_t)vol);
+  G[1].resize((size_t)vol);
+  for (int64_t o = 0; o < lead; ++o) {
+    int64_t rem = o, off[3] = {0, 0, 0};  // the lead index decomposed for the broadcast strides
+    for (int dd = ndim - 4; dd >= 0; --dd) {
+      const int64_t i = rem % shape[dd];
+      rem /= shape[dd];
+      for (int k = 0; k < 3; ++k)
+        if (arr[k]) off[k] += i * st[k][dd];
+    }
+    auto met = [&](int k, int64_t z, int64_t j, int64_t i) -> R {
+      return arr[k][off[k] + z * st[k][ndim - 3] + j * st[k][ndim - 2] + i * st[k][ndim - 1]];
+    };
+    const R* p = a + o * vol;
+    // element q of `x` along axis `ax` (0: X, 1: Y, 2: Z) from the cell at `c` whose index there is `at`; beyond either end:
+    // the pad of that axis
+    auto get = [&](const R* x, int ax, int64_t c, int64_t at, int64_t q) -> R {
+      if (q < 0 || q >= n[ax]) {
+        if (bc[ax] == XG_BC_FILL) return fill[ax];
+        q = bc[ax] == XG_BC_PERIODIC ? (q < 0 ? n[ax] - 1 : 0) : (q < 0 ? 0 : n[ax] - 1);
+      }
+      return x[c + (q - at) * step[ax]];
+    };
+    for (int ax = 0; ax < 2; ++ax) {
+      // (1) the difference to the cell before, over the metric; (2) the mean with the difference after
+      for (int64_t z = 0; z < nz; ++z)
+        for (int64_t j = 0; j < ny; ++j)
+          for (int64_t i = 0; i < nx; ++i) {
+            const int64_t c = z * plane + j * nx + i, at = ax == 0 ? i : j;
+            R d = p[c] - get(p, ax, c, at, at - 1);
+            if (arr[ax]) d = d / met(ax, z, j, i);
+            g[c] = d;
+          }
+      for (int64_t z = 0; z < nz; ++z)
+        for (int64_t j = 0; j < ny; ++j)
+          for (int64_t i = 0; i < nx; ++i) {
+            const int64_t c = z * plane + j * nx + i, at = ax == 0 ? i : j;
+            G[ax][c] = (g[c] + get(g.data(), ax, c, at, at + 1)) * R(0.5);
+          }
+    }
+    // (3) the level means at the faces, the product with the tensor component; the second product is added to the first
+    for (int ax = 0; ax < 2; ++ax) {
+      const R* kw = (ax == 0 ? kwx : kwy) + o * nf * plane;
+      for (int64_t z = 0; z < nf; ++z) {
+        if (closed && (z == 0 || z == nz)) continue;  // (neither the pad level nor the tensor is read there)
+        for (int64_t c = 0; c < plane; ++c) {
+          gf[z * plane + c] = (get(G[ax].data(), 2, c, 0, z - 1) + get(G[ax].data(), 2, c, 0, z)) * R(0.5);
+          const R prod = kw[z * plane + c] * gf[z * plane + c];
+          f[z * plane + c] = ax == 0 ? prod : f[z * plane + c] + prod;
+        }
+      }
+    }
+    // (4) no flux through the top and the bottom
+    if (closed)
+      for (int64_t c = 0; c < plane; ++c) {
+        f[c] = R(0);
+        if (outer) f[nz * plane + c] = R(0);
+      }
+    // (5) the difference to the next face's; `left` pads the flux beyond its last face
+    for (int64_t z = 0; z < nz; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t c = j * nx + i;
+          R next;
+          if (z + 1 < nf) next = f[(z + 1) * plane + c];
+          else if (bc[2] == XG_BC_FILL) next = fill[2];
+          else next = f[((bc[2] == XG_BC_PERIODIC) ? 0 : nz - 1) * plane + c];
+          R d = next - f[z * plane + c];
+          if (arr[2]) d = d / met(2, z, j, i);
+          out[o * vol + z * plane + c] = d;
+        }
+  }
+  return XG_OK;
+}
+
 // kinetic energy (ke_only) and the vector-invariant momentum advection of the header: the stages of the chain one after
 // the other over whole planes, each read through `get`, which pads a plane by one cell on one axis at a time (periodic:
 // the plane's own value at the wrapped index, extend: at the clamped index, fill: the fill value of that axis).
@@ -1704,6 +1803,27 @@ int xg_redi_tensor(int dtype, const void* b, const void* mx, const int64_t* mxs,
                              (float*)out_z, shape, ndim, outer, bc, fill);
   }
   return fail(XG_ERR_INVALID, "redi tensor: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+
+int xg_redi_vertical_flux_divergence(int dtype, const void* a, const void* kwx, const void* kwy, const void* mx,
+                                     const int64_t* mxs, const void* my, const int64_t* mys, const void* mc, const int64_t* mcs,
+                                     void* out, const int64_t* shape, int ndim, int outer, int closed, int bc_x, double fill_x,
+                                     int bc_y, double fill_y, int bc_z, double fill_z, void*) {
+  const int64_t* const st[3] = {mxs, mys, mcs};
+  const int bc[3] = {bc_x, bc_y, bc_z};
+  if (dtype == XG_T_F64) {
+    const double* const arr[3] = {(const double*)mx, (const double*)my, (const double*)mc};
+    const double fill[3] = {fill_x, fill_y, fill_z};
+    return rediflux<double>((const double*)a, (const double*)kwx, (const double*)kwy, arr, st, (double*)out, shape, ndim, outer,
+                            closed, bc, fill);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const arr[3] = {(const float*)mx, (const float*)my, (const float*)mc};
+    const float fill[3] = {(float)fill_x, (float)fill_y, (float)fill_z};
+    return rediflux<float>((const float*)a, (const float*)kwx, (const float*)kwy, arr, st, (float*)out, shape, ndim, outer,
+                           closed, bc, fill);
+  }
+  return fail(XG_ERR_INVALID, "redi vertical flux divergence: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 
 int xg_convert(const void* src, int st, void* dst, int dt, uint64_t n, int via, double scale, int flags, void*) {

@@ -3028,6 +3028,231 @@ __global__ __launch_bounds__(BLOCK) void k_reditensor(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7s: the divergence of the off-diagonal vertical isoneutral flux of a tracer, d/dz(Kwx <da/dx> + Kwy <da/dy>), in ONE pass
+// over (lead, Z, Y, X): the tracer and the two tensor components of K7r in, one field out.  Per level K7q's G_x and G_y of
+// `a`, line by line in its order (fetch, level, the X and Y pads, mx and my); per face k (nz of them at Z:left, nz + 1 at
+// Z:outer, where kwx and kwy sit)
+//   gx = (G_x[k-1] + G_x[k]) * 0.5    gy = (G_y[k-1] + G_y[k]) * 0.5    f[k] = kwx[k] * gx + kwy[k] * gy     (no FMA)
+// and per level K7l's flux march
+//   out[k] = (f[k+1] - f[k]) [/ mc[k]]
+// with f[k] in registers.  `closed` (wave-uniform): no flux through the top and the bottom -- face 0 and, `outer`, face nz are
+// +0.0; their kwx and kwy rows are not loaded and no pad level is formed for them, so nothing there reaches the result.
+// Otherwise the level means above level 0 and (`outer`) below level nz-1 are padded as K7q's (periodic: the far level's,
+// extend: the level's own, fill: fill_z itself).  `left`: the FLUX beyond level nz-1 is padded as K7l's (periodic: f[0] --
+// closed: that +0.0 --, extend: f[nz-1], fill: fill_z itself).  The level stage is a COPY of K7q's without b, as K7r is of
+// K7q; a level's rows are asked for after the store of the level above, K7r's order, at ONE place in the march, and the two
+// tensor rows of the face after the level's means are formed.  a, kwx and kwy are read once and out written once: 32 B/cell
+// in float64.  mc follows K7l's rule: rows that do not vary along Z are loaded once per wave.
+// ------------------------------------------------------------------------------------------
+template <typename T, int SEG>
+struct RfLevel {  // what a face needs of a level
+  T gx[SEG], gy[SEG];
+};
+
+template <int V, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_rediflux(
+    const real* __restrict__ a, const real* __restrict__ kwx, const real* __restrict__ kwy, real* __restrict__ out, int64_t o0,
+    u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int closed, int bc_x,
+    real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mx, VolIdx my, VolIdx mc, int ntl) {
+  typedef typename VecT<V>::type T;
+  typedef IsRows<T, SEG> Rows;
+  typedef RfLevel<T, SEG> L;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
+  const int64_t nf = nz + outer;       // faces
+  // X and Y as K7q's: the columns left and right of the lane's vector, the row below and the row above the segment
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);
+  const bool per_x = bc_x == XG_BC_PERIODIC, per_z = bc_z == XG_BC_PERIODIC;
+  const bool fill_l = e.edge_l && bc_x == XG_BC_FILL;
+  const bool pad_r = e.edge_r && !per_x;
+  const bool fill_b = j0 == 0 && bc_y == XG_BC_FILL;
+  const int64_t jb = (j0 > 0) ? j0 - 1 : ((bc_y == XG_BC_PERIODIC) ? ny - 1 : 0);
+  const int64_t q = j0 + nrow;
+  const bool pad_t = q >= ny && bc_y != XG_BC_PERIODIC;
+  const int64_t jt = (q < ny) ? q : ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1);
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+
+  // the rows of mx and my of a level, as K7q holds them; the rows of mc as K7l holds them
+  T mxr[SEG], myr[SEG], myt, mcr[SEG];
+  real mxrr[SEG];
+  int64_t mxo = 0, mro = 0, myo = 0, mto = 0, mco = 0;
+  auto hmetrics = [&](int64_t k, bool first) {
+    if (mx.p && (first || mx.sz != 0)) {
+      load_rows<T, SEG>(mxr, mx.p, mxo + k * mx.sz, mx.sy, mx.sx, nrow, (ntl & 4) != 0);
+      if (e.own_r) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) mxrr[s_] = mx.p[mro + k * mx.sz + ((s_ < nrow) ? s_ : nrow - 1) * mx.sy];
+      }
+    }
+    if (my.p && (first || my.sz != 0)) {
+      load_rows<T, SEG>(myr, my.p, myo + k * my.sz, my.sy, my.sx, nrow, (ntl & 8) != 0);
+      T top[1];
+      load_rows<T, 1>(top, my.p, mto + k * my.sz, my.sy, my.sx, 1, (ntl & 8) != 0);
+      myt = top[0];
+    }
+  };
+  if (MET) {
+    const int64_t xo = mx.p ? area_outer_off(mx.ai, o) : 0, yo = my.p ? area_outer_off(my.ai, o) : 0;
+    mxo = xo + j0 * mx.sy + i0 * mx.sx;
+    mro = xo + j0 * mx.sy + e.ridx * mx.sx;
+    myo = yo + j0 * my.sy + i0 * my.sx;
+    mto = yo + jt * my.sy + i0 * my.sx;
+    if (mc.p) {
+      mco = area_outer_off(mc.ai, o) + j0 * mc.sy + i0 * mc.sx;
+      load_rows<T, SEG>(mcr, mc.p, mco, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
+    }
+    hmetrics(0, true);
+  }
+
+  auto fetch = [&](int64_t k) -> Rows {  // (with the level's own mx and my rows: `level` is the only reader of both)
+    Rows x;
+    const int64_t lv = col + k * plane;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      x.bb[s_] = *reinterpret_cast<const T*>(a + lv + ro[s_] + i0);
+      x.bl[s_] = e.own_l ? a[lv + ro[s_] + e.lidx] : real(0);
+      x.br[s_] = e.own_r ? a[lv + ro[s_] + e.ridx] : real(0);
+    }
+    x.below = *reinterpret_cast<const T*>(a + lv + jb * nx + i0);
+    x.above = *reinterpret_cast<const T*>(a + lv + jt * nx + i0);
+    if (MET) hmetrics(k, false);
+    return x;
+  };
+  // G_x and G_y of the segment from the rows of a level
+  auto level = [&](const Rows& x) -> L {
+    L r;
+    T g[SEG], h[SEG];
+    real gr[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      real left = x.bl[s_];
+      if (e.shl) {
+        const real dpp = from_lane_below(vec_last(x.bb[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+        if (!e.own_l) left = dpp;
+      }
+      if (fill_l) left = fill_x;
+      g[s_] = dvdx_of(x.bb[s_], left);
+      gr[s_] = x.br[s_] - vec_last(x.bb[s_]);
+      const T lower = (s_ == 0) ? (fill_b ? splat<T>(fill_y) : x.below) : x.bb[(s_ > 0) ? s_ - 1 : 0];
+      h[s_] = x.bb[s_] - lower;
+    }
+    T top = x.above - x.bb[SEG - 1];  // (short tails repeat the last row: bb[SEG - 1] is row nrow - 1)
+    if (MET) {
+      if (mx.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) g[s_] = g[s_] / mxr[s_];
+        if (e.own_r) {
+#pragma unroll
+          for (int s_ = 0; s_ < SEG; ++s_) gr[s_] = gr[s_] / mxrr[s_];
+        }
+      }
+      if (my.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) h[s_] = h[s_] / myr[s_];
+        top = top / myt;
+      }
+    }
+    if (e.shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real right = from_lane_above(vec_first(g[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+        if (!e.own_r) gr[s_] = right;
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (pad_r) gr[s_] = (bc_x == XG_BC_FILL) ? fill_x : vec_last(g[s_]);
+      r.gx[s_] = interp_right_of(g[s_], gr[s_]);
+      T up = (s_ + 1 < nrow) ? h[(s_ + 1 < SEG) ? s_ + 1 : s_] : top;
+      if (s_ + 1 >= nrow && pad_t) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : h[s_];
+      r.gy[s_] = op2<XG_OP_INTERP>(h[s_], up);
+    }
+    return r;
+  };
+  auto padded = [&]() -> L {  // a level of the fill value: the pad of the level means
+    L r;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) r.gx[s_] = r.gy[s_] = splat<T>(fill_z);
+    return r;
+  };
+
+  // the flux at face k from the level above it (`lo`) and the level below it (`hi`): the face's rows of kwx and kwy, 16-byte
+  // loads, once; two products, then the sum
+  const int64_t fo = o * nf * plane + i0;
+  auto flux = [&](int64_t k, const L& lo, const L& hi, T (&f)[SEG]) {
+    T kx[SEG], ky[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      kx[s_] = *reinterpret_cast<const T*>(kwx + fo + k * plane + ro[s_]);
+      ky[s_] = *reinterpret_cast<const T*>(kwy + fo + k * plane + ro[s_]);
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      const T gx = op2<XG_OP_INTERP>(lo.gx[s_], hi.gx[s_]);
+      const T gy = op2<XG_OP_INTERP>(lo.gy[s_], hi.gy[s_]);
+      const T px = kx[s_] * gx;
+      const T py = ky[s_] * gy;
+      f[s_] = px + py;
+    }
+  };
+
+  // face 0: closed, or from the pad above level 0
+  const bool shut = closed != 0;
+  T fc[SEG];
+  L prev;
+  if (!shut && per_z) prev = level(fetch(nz - 1));
+  L cur = level(fetch(0));
+  if (shut) {
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) fc[s_] = splat<T>(real(0));
+  } else {
+    if (bc_z == XG_BC_EXTEND) prev = cur;
+    else if (bc_z == XG_BC_FILL) prev = padded();
+    flux(0, prev, cur, fc);
+  }
+  real* po = out + col + j0 * nx + i0;
+  for (int64_t k = 0; k < nz; ++k) {
+    const bool more = k + 1 < nz;
+    // the flux below level k is formed from two levels: an interior face; the open last face of `outer` (the pad below
+    // level nz-1 -- extend: the level itself, which `cur` still holds); or, `left`, periodic and open, the pad beyond level
+    // nz-1, which is f[0]: formed AGAIN from level nz-1 and level 0, one more level read per column in that mode, instead of
+    // held through the march as K7l holds its f0 -- 8 VGPRs that the float64 metric instance does not have
+    // (EXPERIMENTS.md "K7s")
+    const bool form = more || (!shut && (outer || per_z));
+    T fn[SEG];
+    if (form) {
+      prev = cur;
+      if (more || per_z) cur = level(fetch(more ? k + 1 : 0));
+      else if (bc_z == XG_BC_FILL) cur = padded();
+      flux((more || outer) ? k + 1 : 0, prev, cur, fn);
+    } else {
+      // the closed bottom of `outer` and the closed f[0] of a periodic `left`: +0.0; else `left`'s pad of the flux
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_)
+        fn[s_] = (outer || per_z) ? splat<T>(real(0)) : ((bc_z == XG_BC_EXTEND) ? fc[s_] : splat<T>(fill_z));
+    }
+    if (MET && k > 0) {
+      if (mc.p && mc.sz != 0) load_rows<T, SEG>(mcr, mc.p, mco + k * mc.sz, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        T z = op2<XG_OP_DIFF>(fc[s_], fn[s_]);
+        if (MET) {
+          if (mc.p) z = z / mcr[s_];
+        }
+        stg_s<T, NTS>(po + k * plane + s_ * nx, z);
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) fc[s_] = fn[s_];
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -4240,6 +4465,71 @@ int xg_redi_tensor(int dtype, const void* b, const void* mx, const int64_t* mx_s
                                       (float*)out_y, (float*)out_z, shape, ndim, outer, bc_x, (float)fill_x, bc_y,
                                       (float)fill_y, bc_z, (float)fill_z, stream);
   return fail(XG_ERR_INVALID, "redi tensor: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+
+// K7s's launcher: K7q's plan and dispatch; `a` and the result of `shape`, kwx and kwy with nz (`outer`: nz + 1) faces, three
+// optional broadcast metrics, all at the field's levels (mx at u's columns, my at v's rows, mc at the centre)
+__attribute__((visibility("hidden"))) int xg_internal_rediflux_f64(
+    const double* a, const double* kwx, const double* kwy, const double* mx, const int64_t* mx_strides, const double* my,
+    const int64_t* my_strides, const double* mc, const int64_t* mc_strides, double* out, const int64_t* shape, int ndim,
+    int outer, int closed, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_rediflux_f32(
+    const float* a, const float* kwx, const float* kwy, const float* mx, const int64_t* mx_strides, const float* my,
+    const int64_t* my_strides, const float* mc, const int64_t* mc_strides, float* out, const int64_t* shape, int ndim, int outer,
+    int closed, int bc_x, float fill_x, int bc_y, float fill_y, int bc_z, float fill_z, void* stream);
+
+int XG_FN(xg_internal_rediflux)(const real* a, const real* kwx, const real* kwy, const real* mx, const int64_t* mx_strides,
+                                const real* my, const int64_t* my_strides, const real* mc, const int64_t* mc_strides, real* out,
+                                const int64_t* shape, int ndim, int outer, int closed, int bc_x, real fill_x, int bc_y,
+                                real fill_y, int bc_z, real fill_z, void* stream) {
+  const char* name = "redi vertical flux divergence";
+  if (!a || !kwx || !kwy || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (closed != 0 && closed != 1) return fail(XG_ERR_INVALID, "%s: closed %d is neither 0 nor 1", name, closed);
+  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  VolIdx mi[3];  // all three at the field's levels
+  const real* mp[3] = {mx, my, mc};
+  const int64_t* ms[3] = {mx_strides, my_strides, mc_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  FusedPlan p;
+  const bool al = aligned16(a) && aligned16(kwx) && aligned16(kwy) && aligned16(out);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  // bit 0: the lane neighbours by DPP (K7c, K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
+  int vnt = vec_nt_bits(1);
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool met = mx != nullptr || my != nullptr || mc != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_rediflux<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, a, kwx, kwy, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, closed, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt); } while (0)
+#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument, the fills are cast to it here
+int xg_redi_vertical_flux_divergence(int dtype, const void* a, const void* kwx, const void* kwy, const void* mx,
+                                     const int64_t* mx_strides, const void* my, const int64_t* my_strides, const void* mc,
+                                     const int64_t* mc_strides, void* out, const int64_t* shape, int ndim, int outer, int closed,
+                                     int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream) {
+  if (dtype == XG_T_F64)
+    return xg_internal_rediflux_f64((const double*)a, (const double*)kwx, (const double*)kwy, (const double*)mx, mx_strides,
+                                    (const double*)my, my_strides, (const double*)mc, mc_strides, (double*)out, shape, ndim,
+                                    outer, closed, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, stream);
+  if (dtype == XG_T_F32)
+    return xg_internal_rediflux_f32((const float*)a, (const float*)kwx, (const float*)kwy, (const float*)mx, mx_strides,
+                                    (const float*)my, my_strides, (const float*)mc, mc_strides, (float*)out, shape, ndim, outer,
+                                    closed, bc_x, (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
+  return fail(XG_ERR_INVALID, "redi vertical flux divergence: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 #endif
 

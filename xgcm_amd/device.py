@@ -1526,6 +1526,40 @@ def redi_tensor(b, mx, my, mz, kappa: float, slope_max2, outer: bool, bc_x: str,
     return outs
 
 
+def redi_vertical_flux_divergence(a, kwx, kwy, mx, my, mc, outer: bool, closed: bool, bc_x: str, bc_y: str, bc_z: str,
+                                  fill_x: float = 0.0, fill_y: float = 0.0, fill_z: float = 0.0) -> torch.Tensor:
+    """Fused divergence of the off-diagonal vertical isoneutral flux of `a` in one pass (xg_redi_vertical_flux_divergence):
+    the level means of `isopycnal_slope` formed of `a` (its `mx`, `my` and pads), their means at the faces of Z, the flux
+    kwx * gx + kwy * gy there, the difference of the flux to the next face's divided by `mc` (None = no division).  `kwx`
+    and `kwy` have the face shape, nz faces (`outer` False) or nz + 1 (True): the results of `redi_tensor`.  `closed`: the
+    flux at face 0 and, `outer`, at face nz is +0.0 and nothing is read there.  `mx`, `my` and `mc` broadcast against `a`.
+    Returns the result, of `a`'s shape."""
+    lib = _MEM.lib()
+    dt, sfx = _common(a, kwx, kwy, mx, my, mc)
+    a = asdevice(a, dt)
+    if a.dim() < 3 or a.shape[-3] == 0:
+        raise ValueError("redi_vertical_flux_divergence: the field needs (Z, Y, X) as its last three dims and a level along Z")
+    shape = list(a.shape)
+    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
+    kwx, kwy = asdevice(kwx, dt), asdevice(kwy, dt)
+    for k, what in ((kwx, "kwx"), (kwy, "kwy")):
+        if list(k.shape) != fshape:
+            raise ValueError(f"redi_vertical_flux_divergence: {what} has shape {tuple(k.shape)}, the faces have {tuple(fshape)}")
+    kwx, kwy = kwx.contiguous(), kwy.contiguous()
+    mets = [_prep_metric(m, dt) for m in (mx, my, mc)]
+    out = _empty(shape, dtype=dt, device=a.device)
+    if out.numel() == 0:
+        return out
+    margs = []
+    for m, what in zip(mets, ("X metric", "Y metric", "Z metric at the centre")):
+        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
+    _check(lib.xg_redi_vertical_flux_divergence(_hip.DTYPE["float32" if sfx == "f32" else "float64"], a.data_ptr(),
+                                                kwx.data_ptr(), kwy.data_ptr(), *margs, out.data_ptr(), _hip.i64(shape),
+                                                len(shape), int(bool(outer)), int(bool(closed)), _hip.BC[bc_x], float(fill_x),
+                                                _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z), _stream()))
+    return out
+
+
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""

@@ -2315,7 +2315,7 @@ class Grid:
         what the chain does.
 
         Out of scope: other tapers (`clipping`, `dm95`, `ldd97`: tanh cannot be held to numpy bit for bit) and the U- and
-        V-point tensor components.
+        V-point tensor components.  kwx and kwy are what `redi_vertical_flux_divergence` takes, as they are.
 
         The one pass serves the call when `isopycnal_slope`'s would (the list in its docstring) and `kappa` and `slope_max`
         are each a Python int or float, or a numpy floating scalar that does not promote the fields' dtype (`slope_max` may
@@ -2414,6 +2414,149 @@ class Grid:
             res = [lx, ly, s2] if tensor[1] is None else [both(s2, lx), both(s2, ly), both(s2, s2)]
         outs = tuple(r._replace(data=_dev.tohost(out) if host else out) for r, out in zip(res, outs))
         return tuple(to_xarray(r) for r in outs) if was_xr else outs
+
+    def redi_vertical_flux_divergence(self, a, kwx, kwy, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", to=None,
+                                      closed: bool = True, padding=None, fill_value=None, metric_weighted: bool = True):
+        """The explicit part of Redi isoneutral diffusion (and of the Gent-McWilliams skew flux) of a tracer along Z: the
+        divergence of the off-diagonal vertical flux, d/dz(Kwx <da/dx> + Kwy <da/dy>) -- what MITgcm's `gmredi_rtransport`
+        adds next to the implicit solve with Kwz -- in ONE pass: `a`, `kwx` and `kwy` are read once and the result written
+        once (32 B/cell in float64, against about 200 for the chain); the gradients and the flux stay in registers.  With it
+        the tracer side is `redi_tensor(b)` once per step, this operator once per tracer, and
+        `implicit_vertical_diffusion(a, kwz, dt)` once per tracer.
+
+        `a` at (Z:center, Y:center, X:center), any leading dims, Z third from last.  `kwx` and `kwy` at (lead, Z face,
+        Y:center, X:center): the dims and the position of `redi_tensor`'s results.  `to`: the face position, "left" or
+        "outer"; None: "outer" when the Z axis has one, else "left".  The result has `a`'s dims.  Bit-identical, dims,
+        coords and name included, to the chain
+
+            kw   = dict(padding=padding, fill_value=fill_value)
+            step = grid.derivative if metric_weighted else grid.diff
+            gx = grid.interp(grid.interp(step(a, x_axis, **kw), x_axis, **kw), z_axis, to=to, **kw)
+            gy = grid.interp(grid.interp(step(a, y_axis, **kw), y_axis, **kw), z_axis, to=to, **kw)
+            f  = kwx * gx + kwy * gy            # two products, one sum, in the fields' dtype, no fused multiply-add
+            if closed:                          # no flux through the top and the bottom
+                f = a copy of f with face 0 -- and with to="outer" also face nz -- set to +0.0
+            out = step(f, z_axis, **kw)         # faces -> centre: (f[k+1] - f[k]) [/ drF]
+
+        gx and gy are `isopycnal_slope`'s, formed of `a`; the copy keeps f's dims, coords and name.
+
+        `closed=True`, the default, is MITgcm's condition and makes the operator usable on `redi_tensor`'s results as they
+        are (their outermost faces are NaN under `extend` with "outer").  The closed faces are exactly +0.0: no value of
+        `kwx`, of `kwy` or of a pad of the level means there reaches the result, a NaN included.  With "outer" no pad along
+        Z is used at all.  With "left" face 0 is closed and the flux beyond level nz-1 is the chain's pad of f (periodic:
+        f[0], the closed +0.0; extend: f[nz-1]; fill: `fill_value` itself).  `closed=False` is the plain chain with every
+        pad along Z: the level means above level 0 and, "outer", below level nz-1 as in `isopycnal_slope`, the flux beyond
+        nz-1 ("left") as in `vertical_diffusion`.  The X and Y pads are `isopycnal_slope`'s in both modes.
+
+        Sign convention: `isopycnal_slope`'s, all derivatives run along increasing index.  With `a = b` the explicit flux
+        here and `kwz * db/dz` cancel up to rounding: there is no isoneutral flux of the field that defines the surfaces.
+        Under the skew-flux form with equal GM and Redi diffusivities the caller passes `2 * kwx, 2 * kwy`, an exact
+        scaling; nothing is built for it.  Out of scope: the U- and V-point components of the tensor (the horizontal
+        fluxes), other closures of the boundary, and `maskC`-style land masks.
+
+        The metrics are whatever `get_metric` returns for X at (lead, Z:center, Y:center, X:left), for Y at (lead,
+        Z:center, Y:left, X:center) and for Z at `a`'s dims (dxC, dyC, drF, or registered 3-D arrays), one broadcast array
+        each; each may be absent on its own terms.
+
+        The one pass serves the call exactly when `isopycnal_slope`'s would for `a` (the list in its docstring; float32 /
+        float64 only), `kwx` and `kwy` are unchunked labelled arrays of `a`'s dtype with exactly the flux' dims and shape,
+        and the Z metric at `a`'s dims passes the tests of the other two.  For everything else the chain above itself
+        runs, the same calls in the same order, raising what it raises.  Its closing step needs a materialised flux: a
+        chunked flux and one deferred under `grid.fused()` are computed first (a host array, or wherever the deferred
+        value lives), then copied and closed; a flux without the face dim is handed on as it is."""
+        args, to_arg = (a, kwx, kwy), to
+        (a, xr1), (kwx, xr2), (kwy, xr3) = self._wrap_in(a), self._wrap_in(kwx), self._wrap_in(kwy)
+        was_xr = xr1 or xr2 or xr3
+        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
+        if to is None:
+            to = "outer" if "outer" in zax.coords else "left"
+        plan = None
+        served = (isinstance(a, DataArray) and isinstance(kwx, DataArray) and isinstance(kwy, DataArray) and a.ndim >= 3
+                  and to in ("left", "outer") and to in zax.coords and all("center" in ax.coords for ax in (zax, yax, xax))
+                  and "left" in yax.coords and "left" in xax.coords and a.shape[-3] > 0
+                  and not gridops.complex_topology(self, z_axis))
+        if served:
+            tz, zf = zax.coords["center"], zax.coords[to]
+            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            lead = a.dims[:-3]
+            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
+            served = a.dims == lead + (tz, yc, xc) and not held & set(lead)
+        mets = [None, None, None]
+        if served:
+            f_shape = tuple(a.shape[:-3]) + (a.shape[-3] + (1 if to == "outer" else 0),) + tuple(a.shape[-2:])
+            c_dims, f_dims = lead + (tz, yc, xc), lead + (zf, yc, xc)
+            m_dims = [lead + (tz, yc, xl), lead + (tz, yl, xc), c_dims]   # the two derivatives' dims and the result's
+            served = all(k.dims == f_dims and tuple(k.shape) == f_shape for k in (kwx, kwy))
+        if served:
+            try:
+                if metric_weighted:
+                    for k, ax in enumerate((x_axis, y_axis, z_axis)):
+                        mets[k] = self._resident(self.get_metric(_DimsOnly(m_dims[k], a.name), (ax,), _layout=m_dims[k]), a.data)
+                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, m_dims))
+            except (KeyError, ValueError):
+                served = False  # (the chain raises it where the chain looks the metric up)
+        if served and not any(_is_chunked(k.data) for k in (kwx, kwy)):
+            dtype = _dt.np_dtype(a.data)
+            if all(_dt.np_dtype(k.data) == dtype for k in (kwx, kwy)):
+                plan = self._second_order_plan([a], x_axis, y_axis, padding, fill_value, [m for m in mets if m is not None])
+        if plan is not None:
+            bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
+            fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
+            # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as it is
+            # (None: 0.0), so a -0.0 or a NaN keeps its bits on all three axes
+            fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
+            plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
+        if plan is None:
+            a, kwx, kwy = args
+            kw = dict(padding=padding, fill_value=fill_value)
+            step = self.derivative if metric_weighted else self.diff
+            gx = self.interp(self.interp(step(a, x_axis, **kw), x_axis, **kw), z_axis, to=to, **kw)
+            gy = self.interp(self.interp(step(a, y_axis, **kw), y_axis, **kw), z_axis, to=to, **kw)
+            f = kwx * gx + kwy * gy
+            if closed:
+                f = self._closed_flux(f, zax.coords.get(to), to == "outer")
+            return step(f, z_axis, **kw)
+        bcx, bcy, fvx, fvy, bcz, fvz = plan
+        host = not any(_is_tensor(x.data) for x in (a, kwx, kwy))
+        mx, my, mc = (None if m is None else _aligned_view(m, dims) for m, dims in zip(mets, m_dims))
+        out = _dev.redi_vertical_flux_divergence(a.data, kwx.data, kwy.data, mx, my, mc, to == "outer", bool(closed), bcx, bcy,
+                                                 bcz, fvx, fvy, fvz)
+
+        # dims, coords and name as the chain's, step by step over placeholders: each derivative (named after its quotient
+        # with the metric), the mean back to the centre, the mean at the faces, the product with the tensor component; the
+        # sum (closing it changes neither coords nor name); the step back to the centre, named after its metric quotient
+        def named(g, m):
+            return g if m is None else g._replace(name=_name_after(g.name, m))
+
+        prods = []
+        for k, (dim_l, dim_c, kwk) in enumerate(((xl, xc, kwx), (yl, yc, kwy))):
+            g = named(self._labels_of_step(a, m_dims[k], dim_l), mets[k])
+            g = self._labels_of_step(self._labels_of_step(g, c_dims, dim_c), f_dims, zf, f_shape)
+            prods.append(self._labels_of_binary(kwk, g))
+        f = self._labels_of_binary(*prods)
+        res = named(self._labels_of_step(f, c_dims, tz, a.shape), mets[2])
+        res = res._replace(data=_dev.tohost(out) if host else out)
+        return to_xarray(res) if was_xr else res
+
+    def _closed_flux(self, f, face_dim, outer):
+        """a copy of the flux `f` with face 0 and (`outer`) its last face along `face_dim` set to +0.0; dims, coords and name
+        stay f's.  A deferred or chunked flux is computed first; a flux without that dim passes as it is"""
+        f, was_xr = self._wrap_in(f)
+        was_xr = was_xr or bool(getattr(f, "_xr", False))   # (a deferred result of xarray inputs)
+        with _lazy.suspended():  # (inside a `fused()` block the products behind a deferred flux must not defer themselves again)
+            f = _lazy.plain(f)
+        if not isinstance(f, DataArray) or face_dim not in f.dims:
+            return to_xarray(f) if was_xr else f
+        data = f.data
+        if _is_chunked(data):
+            data = np.asarray(data)
+        data = data.clone() if _is_tensor(data) else np.array(data, copy=True)
+        at = [slice(None)] * data.ndim
+        for face in (0, -1) if outer else (0,):
+            at[f.dims.index(face_dim)] = face
+            data[tuple(at)] = 0.0
+        f = f._replace(data=data)
+        return to_xarray(f) if was_xr else f
 
     # ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---------------------
     def _c_grid_vector(self, u, v, x_axis, y_axis, what):

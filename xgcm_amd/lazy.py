@@ -29,6 +29,7 @@ at the call, topology errors of connected axes are checked at the call by buildi
 
 from __future__ import annotations
 
+import contextlib
 import threading
 import weakref
 from collections import OrderedDict
@@ -500,6 +501,18 @@ def enter() -> None:
 
 def leave() -> None:
     _ACTIVE.depth = getattr(_ACTIVE, "depth", 1) - 1
+
+
+@contextlib.contextmanager
+def suspended():
+    """inside, this thread is outside every `grid.fused()` block: for a step that has to compute a deferred value now, whose
+    products must not defer themselves again"""
+    depth = getattr(_ACTIVE, "depth", 0)
+    _ACTIVE.depth = 0
+    try:
+        yield
+    finally:
+        _ACTIVE.depth = depth
 
 
 def _hook(self_operand, other, op, reflexive, dims_order):
