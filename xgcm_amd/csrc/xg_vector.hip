@@ -1048,7 +1048,13 @@ __global__ __launch_bounds__(BLOCK) void k_kinetic(
 //   ke   = 0.5 * (interp(u * u, X) + interp(v * v, Y))                             centre              K7g
 //   gu   = interp(zeta, Y) * interp(interp(v, X), Y) - (ke[j,i] - ke[j,i-1]) [/ dxC]         at u's points
 //   gv   = -(interp(zeta, X) * interp(interp(u, Y), X)) - (ke[j,i] - ke[j-1,i]) [/ dyC]      at v's points
-// in the chain's operation order (-ffp-contract=off, the compiler's IEEE quotients).  Per wave-task (SEG rows, one x-tile) a
+// in the chain's operation order (-ffp-contract=off, the compiler's IEEE quotients).
+// WHAT THIS IS: zeta is the curl of the RAW u, v in index space over the area -- not the relative vorticity, whose differences
+// are of the circulations u * dxC, v * dyC -- while the same u, v serve as velocities in ke and in the two means.  With the
+// metrics the result is (zeta v - d/dx KE, -zeta u - d/dy KE) only on a grid of unit spacing (dxC = dyC = 1, rAz = 1); on a
+// uniform grid of spacing h it is (zeta / h) v - d/dx KE, and without the metrics h times the term.  Measured against the
+// analytic term in tests/test_convergence.py (a strict expected failure there until the kernel takes circulations).
+// Per wave-task (SEG rows, one x-tile) a
 // lane holds the patch of u and v it needs: rows j0-1 .. j0+SEG, columns i0-1 .. i0+V -- the columns left and right of its
 // vector from the neighbouring lanes (DPP), lane 0 / lane 63 / the edge lanes load their own.  A periodic axis wraps the
 // patch's indices: every stage's periodic pad is then the stage's own value at the wrapped index.  At an extend / fill
@@ -1237,7 +1243,12 @@ __global__ __launch_bounds__(BLOCK) void k_momadv(
 }
 
 // ------------------------------------------------------------------------------------------
-// K7k: the vector-invariant harmonic viscosity (MITgcm's mom_vi_hdissip, harmonic part) in ONE pass, two fields in, two out:
+// K7k: the vector-invariant harmonic viscosity in the FORM of MITgcm's mom_vi_hdissip (harmonic part) in ONE pass, two fields
+// in, two out.  WHAT THIS IS: D and zeta are the divergence and the curl of the RAW u, v in index space over the area -- not
+// of the transports u * dyG, v * dxG and the circulations u * dxC, v * dyC, as mom_vi_hdissip's are.  With the metrics the
+// result is the named term only on a grid of unit spacing; on a uniform grid of spacing h it is the term over h, and without
+// the metrics h^2 times the term.  Measured against the analytic term in tests/test_convergence.py (a strict expected failure
+// there until the kernel takes transports and circulations).
 //   D    = ((u[j,i+1] - u[j,i]) + (v[j+1,i] - v[j,i])) [/ rA]  [* nu_d]              centre                K7b
 //   zeta = ((v[j,i] - v[j,i-1]) - (u[j,i] - u[j-1,i])) [/ rAz] [* nu_z]              (Y:left, X:left)      K7
 //   gu   = (D[j,i] - D[j,i-1]) [/ dxC] - (zeta[j+1,i] - zeta[j,i]) [/ dyG]           at u's points

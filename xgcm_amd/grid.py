@@ -420,6 +420,11 @@ class Grid:
     def get_metric(self, array, axes, _layout=None, _factors=False):
         """Metric that broadcasts against `array` for the given axes (conditions 1-4 of the reference).
 
+        Condition 4, the reference's rule kept for parity: when no product of registered metrics sits at the array's
+        position, the LAST product of the first candidate combination is interpolated there with `extend`, whatever else is
+        registered.  With MITgcm's set (dxC, dxG, drF, drC at ZL and ZO; no dxF) the (X, Z) metric of a cell-centre field is
+        dxG * drC(ZO) averaged to the levels -- about 3/4 of drF at the two end levels, the half cells -- not dxG * drF.
+
         `_layout` (internal, the operators pass the dims of the array they weight): a metric that has to be formed
         as a PRODUCT of registered metrics (a volume = area(Y,X) * thickness(Z)) is laid out with its dims in that
         order.  xarray's order -- first factor's dims, then the new ones: (Y, X, Z) -- made every use a transposed
@@ -922,7 +927,11 @@ class Grid:
         return to_xarray(data) if was_xr else data
 
     def integrate(self, da, axis, **kwargs):
-        """Finite-volume integral `(da * metric).sum(dims)` along one or more axes (grid.py:1580-1605)."""
+        """Finite-volume integral `(da * metric).sum(dims)` along one or more axes (grid.py:1580-1605).
+
+        The metric is `get_metric(da, axis)`'s.  Over several axes at a position where no product of registered metrics
+        sits (the cell centre along X with MITgcm's set, which has no dxF) that is its condition 4: an interpolated
+        product, dxG * drC(ZO) for (X, Z), first-order accurate on a closed column; integrate one axis at a time there."""
         da, was_xr = self._wrap_in(da)
         skipna = kwargs.pop("skipna", None)
         keep_attrs = kwargs.pop("keep_attrs", False)
@@ -2623,6 +2632,14 @@ class Grid:
         in float64 instead of about 400 for the twenty launches of the chain).  Returns `(gu, gv)`, gu at u's points,
         gv at v's.
 
+        What is computed: the chain below, in which `zeta` is `grid.vorticity` of the RAW u and v -- their curl in index
+        space over the area, (delta_x v - delta_y u) / rAz -- not the relative vorticity, which by `vorticity`'s own
+        convention needs the circulations u * dxC, v * dyC; the same u and v serve as velocities in ke, ubar and vbar.
+        With `metric_weighted` the result is the continuous term ((zeta + f) v - d/dx KE, -(zeta + f) u - d/dy KE) only on
+        a grid of unit spacing (dxC = dyC = 1, rAz = 1).  On a uniform grid of spacing h it is (zeta / h + f) v - d/dx KE;
+        with `metric_weighted=False` and no `coriolis` it is h times the term.  On a stretched grid it is neither.
+        `tests/test_convergence.py` measures this (a strict expected failure against the continuous term).
+
         u at (Y:center, X:left), v at (Y:left, X:center).  Bit-identical, coords and names included, to the chain
 
             kw = dict(padding=padding, fill_value=fill_value)
@@ -2699,10 +2716,19 @@ class Grid:
 
     def horizontal_viscosity(self, u, v, viscosity_d=None, viscosity_z=None, x_axis: str = "X", y_axis: str = "Y",
                              padding=None, fill_value=None, metric_weighted: bool = True):
-        """Vector-invariant harmonic viscosity, del2 u = d/dx(D) - d/dy(zeta) and del2 v = d/dy(D) + d/dx(zeta) with D the
-        horizontal divergence and zeta the relative vorticity (MITgcm's mom_vi_hdissip, harmonic part), in ONE pass: u and
-        v are read once and the two tendencies written once (32 B/cell in float64, against about 150-200 for the seven to
-        nine launches of the chain).  Returns `(gu, gv)`, gu at u's points, gv at v's.
+        """Vector-invariant harmonic viscosity in the form of MITgcm's mom_vi_hdissip (harmonic part), d/dx(D) - d/dy(zeta)
+        at u's points and d/dy(D) + d/dx(zeta) at v's, in ONE pass: u and v are read once and the two tendencies written
+        once (32 B/cell in float64, against about 150-200 for the seven to nine launches of the chain).  Returns
+        `(gu, gv)`, gu at u's points, gv at v's.
+
+        What is computed: the chain below, in which D and zeta are `grid.divergence` and `grid.vorticity` of the RAW u and
+        v -- their divergence and curl in index space over the area, (delta_x u + delta_y v) / rA and
+        (delta_x v - delta_y u) / rAz -- not the horizontal divergence and the relative vorticity, which by those
+        operators' own convention need the transports u * dyG, v * dxG and the circulations u * dxC, v * dyC.  With
+        `metric_weighted` the result is the continuous term (del2 u, del2 v for constant coefficients) only on a grid of
+        unit spacing; on a uniform grid of spacing h it is the term over h, and with `metric_weighted=False` h^2 times the
+        term.  On a stretched grid it is neither.  `tests/test_convergence.py` measures this (a strict expected failure
+        against the continuous term).
 
         u at (Y:center, X:left), v at (Y:left, X:center).  `viscosity_d` is a coefficient at the cell centre, where D
         lives, `viscosity_z` one at the vorticity point (Y:left, X:left) -- the Smagorinsky / Leith form; each may have any
