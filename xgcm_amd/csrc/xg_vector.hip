@@ -1917,9 +1917,10 @@ __global__ __launch_bounds__(BLOCK) void k_vdiff(
 }
 
 // ------------------------------------------------------------------------------------------
-// K7m: implicit (backward-Euler) vertical diffusion, (I - dt D) x = a with D = d/dz(kappa d/dz) under the no-flux condition
-// at the top and at the bottom, over (lead, Z, Y, X) in ONE launch: the Thomas algorithm per column, a forward and a backward
-// sweep over the same column.  Faces k = 1 .. nz-1 (face k between level k-1 and level k), in the field's type, no FMA:
+// K7m / K7o, the implicit sweeps: ONE kernel.  K7m: implicit (backward-Euler) vertical diffusion, (I - dt D) x = a with
+// D = d/dz(kappa d/dz) under the no-flux condition at the top and at the bottom, over (lead, Z, Y, X) in ONE launch: the
+// Thomas algorithm per column, a forward and a backward sweep over the same column.  Faces k = 1 .. nz-1 (face k between
+// level k-1 and level k), in the field's type, no FMA:
 //   w[k]  = dt * (kappa[k] [/ mf[k]])                  (kappa absent: 1)
 //   lo[k] = w[k] [/ mc[k]],  up[k-1] = w[k] [/ mc[k-1]]
 //   b     = 1 [+ lo[k], k > 0] [+ up[k], k < nz-1]
@@ -1940,12 +1941,31 @@ __global__ __launch_bounds__(BLOCK) void k_vdiff(
 // obeys `nt_store`.
 // float64 with a 3-D kappa: a 8 + kappa 8 + d out and back 16 + c out and back 16 + x 8 = 56 B/cell (48 with a profile
 // kappa(Z) or none); the read-backs may come from the L2 / the Infinity Cache.
+// K7o, implicit vertical viscosity of a C-grid velocity, is this kernel for u and for v with ONE viscosity nu at the centre
+// points: SRC says, at compile time, where the coefficient stage of face k takes kappa[k] from --
+//   VI_ONE:   1                                    VI_KAPPA: the array kappa, as above
+//   VI_NU_U (u, at X:left):   kappa[k] = (nu[k, j, i-1] + nu[k, j, i]) * 0.5       interp_left_of, K7j's neighbour
+//   VI_NU_V (v, at Y:left):   kappa[k] = (nu[k, j-1, i] + nu[k, j, i]) * 0.5       op2<XG_OP_INTERP>, K7j's row below
+// -- and everything after it is the one recurrence in the one order.  nu (as `kp`, required, loaded per face: it is a field
+// of the faces) is padded by `bc` / `fill` left of column 0 / below row 0 (periodic: column nx-1 / row ny-1, extend: column
+// 0 / row 0, fill: the fill value in place of the loaded value); there is no pad along Z and faces 0 and nz are never read.
+// A wave owns a column set of ONE component and the launcher starts the kernel once per component (both components in one
+// wave would keep two sets of the pipelined coefficients live).  u: nu left of the lane's vector comes from the lane below
+// by DPP where `ntl` bit 0 allows, the tile's first lane and the row's edge load their own; v: the row below the segment is
+// one more row per face (the segment before's last row: an L2 hit).  float64 per component: a 8 + nu 8 + d out and back 16 +
+// c out and back 16 + x 8 = 56 B/cell, 112 for both (nu read by each).
+// `bc` and `fill` stand LAST among the arguments: in front of `kp` they move the argument offsets of the VI_ONE / VI_KAPPA
+// instances, and the float64 V=2 instance with kappa and metrics came out with its blocks laid out otherwise and 0.07 ms
+// slower at 14.8 ms on 4320 x 4320 x 90 (EXPERIMENTS.md "Z-march families").
 // ------------------------------------------------------------------------------------------
-template <int V, bool KAP, bool MET, bool NTS, int SEG>
+enum { VI_ONE = 0, VI_KAPPA = 1, VI_NU_U = 2, VI_NU_V = 3 };  // k_vimpl's SRC
+
+template <int V, int SRC, bool MET, bool NTS, int SEG>
 __global__ __launch_bounds__(BLOCK) void k_vimpl(
     const real* __restrict__ a, real* __restrict__ cw, real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk, int64_t nz,
-    int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, real dt, VolIdx kp, VolIdx mf, VolIdx mc, int ntl) {
+    int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, real dt, VolIdx kp, VolIdx mf, VolIdx mc, int ntl, int bc, real fill) {
   typedef typename VecT<V>::type T;
+  constexpr bool NU = SRC == VI_NU_U || SRC == VI_NU_V;
   XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
   const int64_t plane = ny * nx;
   const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
@@ -1953,13 +1973,21 @@ __global__ __launch_bounds__(BLOCK) void k_vimpl(
 #pragma unroll
   for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = col + (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx + i0;
   const T one = splat<T>(real(1)), tdt = splat<T>(dt);
+  // nu, u: left of the lane's vector (periodic: column nx - 1, extend: column 0 itself); v: the row below the segment
+  // (periodic: row ny - 1 below row 0, extend: row 0 itself); a fill edge loads the clamped cell and replaces it
+  const LaneEdges e = lane_edges<V>(i0, nx, bc, ntl);
+  const bool fill_e = (SRC == VI_NU_U ? e.edge_l : j0 == 0) && bc == XG_BC_FILL;
+  const int64_t rb = j0 > 0 ? j0 - 1 : ((bc == XG_BC_PERIODIC) ? ny - 1 : 0);
 
   // the rows of kappa and of the two metrics: loaded per face / level only when the array varies along Z, else once (and
-  // not at all for a column of one level, which has no face)
+  // not at all for a column of one level, which has no face); nu per face
   T kr[SEG], mfr[SEG], mcr[SEG];
-  int64_t kpo = 0, mfo = 0, mco = 0;
-  if (KAP) {
-    kpo = area_outer_off(kp.ai, o) + j0 * kp.sy + i0 * kp.sx;
+  int64_t kpb = 0, kpo = 0, mfo = 0, mco = 0;
+  if (SRC != VI_ONE) {
+    kpb = area_outer_off(kp.ai, o);  // kappa's / nu's (Z, Y, X) volume of this lead index
+    kpo = kpb + j0 * kp.sy + i0 * kp.sx;
+  }
+  if (SRC == VI_KAPPA) {
     if (kp.sz == 0 && nz > 1) load_rows<T, SEG>(kr, kp.p, kpo, kp.sy, kp.sx, nrow, (ntl & 4) != 0);
   }
   if (MET) {
@@ -1994,174 +2022,11 @@ __global__ __launch_bounds__(BLOCK) void k_vimpl(
       }
     }
     if (k + 1 < nz) {
-      // face k + 1
-      if (KAP && kp.sz != 0) load_rows<T, SEG>(kr, kp.p, kpo + (k + 1) * kp.sz, kp.sy, kp.sx, nrow, (ntl & 4) != 0);
-      if (MET) {
-        if (mf.p && mf.sz != 0) load_rows<T, SEG>(mfr, mf.p, mfo + (k + 1) * mf.sz, mf.sy, mf.sx, nrow, (ntl & 8) != 0);
-      }
-#pragma unroll
-      for (int s_ = 0; s_ < SEG; ++s_) {
-        T g = KAP ? kr[s_] : one;
-        if (MET) {
-          if (mf.p) g = g / mfr[s_];
-        }
-        w[s_] = tdt * g;
-        T u = w[s_];
-        if (MET) {
-          if (mc.p) u = u / mcr[s_];
-        }
-        up_[s_] = u;
-        b_[s_] = b_[s_] + u;
-      }
-    }
-  };
-
-  // ---- forward: d into out, c into cw; the last level's d is x itself ----
-  T ac[SEG], lo[SEG], up[SEG], b[SEG], cp[SEG], dp[SEG];
-  coef(0, ac, lo, up, b);
-  for (int64_t k = 0; k < nz; ++k) {
-    const bool more = k + 1 < nz;
-    T an[SEG], lon[SEG], upn[SEG], bn[SEG];
-    if (more) coef(k + 1, an, lon, upn, bn);
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      T m = b[s_], d = ac[s_];
-      if (k > 0) {
-        m = m - lo[s_] * cp[s_];
-        d = d + lo[s_] * dp[s_];
-      }
-      const T r = one / m;
-      d = d * r;
-      dp[s_] = d;
-      if (more) {
-        cp[s_] = up[s_] * r;
-        if (s_ < nrow) {
-          stg<T, false>(out + ro[s_] + k * plane, d);
-          stg<T, false>(cw + ro[s_] + k * plane, cp[s_]);
-        }
-      } else if (s_ < nrow) {
-        stg_s<T, NTS>(out + ro[s_] + k * plane, d);
-      }
-    }
-    if (more) {
-#pragma unroll
-      for (int s_ = 0; s_ < SEG; ++s_) {
-        ac[s_] = an[s_];
-        lo[s_] = lon[s_];
-        up[s_] = upn[s_];
-        b[s_] = bn[s_];
-      }
-    }
-  }
-  if (nz < 2) return;
-
-  // ---- backward: x[k] = d[k] + c[k] * x[k+1], what this lane stored read back one level ahead of its use ----
-  T dk[SEG], ck[SEG];
-#pragma unroll
-  for (int s_ = 0; s_ < SEG; ++s_) {
-    dk[s_] = *reinterpret_cast<const T*>(out + ro[s_] + (nz - 2) * plane);
-    ck[s_] = *reinterpret_cast<const T*>(cw + ro[s_] + (nz - 2) * plane);
-  }
-  for (int64_t k = nz - 2; k >= 0; --k) {
-    T dn[SEG], cn[SEG];
-    if (k > 0) {
-#pragma unroll
-      for (int s_ = 0; s_ < SEG; ++s_) {
-        dn[s_] = *reinterpret_cast<const T*>(out + ro[s_] + (k - 1) * plane);
-        cn[s_] = *reinterpret_cast<const T*>(cw + ro[s_] + (k - 1) * plane);
-      }
-    }
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      dp[s_] = dk[s_] + ck[s_] * dp[s_];
-      if (s_ < nrow) stg_s<T, NTS>(out + ro[s_] + k * plane, dp[s_]);
-    }
-    if (k > 0) {
-#pragma unroll
-      for (int s_ = 0; s_ < SEG; ++s_) {
-        dk[s_] = dn[s_];
-        ck[s_] = cn[s_];
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// K7o: implicit vertical viscosity of a C-grid velocity, K7m for u and for v with ONE viscosity nu at the centre points:
-//   u (COMP 0, at X:left):   kappa[k] = (nu[k, j, i-1] + nu[k, j, i]) * 0.5       interp_left_of, K7j's neighbour
-//   v (COMP 1, at Y:left):   kappa[k] = (nu[k, j-1, i] + nu[k, j, i]) * 0.5       op2<XG_OP_INTERP>, K7j's row below
-// formed in the coefficient stage of face k, everything after it K7m's recurrence in K7m's order (see there; no FMA).  nu is
-// padded left of column 0 / below row 0 (periodic: column nx-1 / row ny-1, extend: column 0 / row 0, fill: the fill value in
-// place of the loaded value); there is no pad along Z and faces 0 and nz are never read.  K7m's geometry: a wave owns one
-// (lead, Y segment, X tile) column set of ONE component -- the component is a template parameter and the launcher starts the
-// kernel once per component (both components in one wave would keep two sets of K7m's pipelined coefficients live).  u: nu
-// left of the lane's vector comes from the lane below by DPP where `ntl` bit 0 allows, the tile's first lane and the row's
-// edge load their own; v: the row below the segment is one more row per face (the segment before's last row: an L2 hit).
-// d goes into `out`, c into the workspace `cw`; every lane reads back only what it stored itself (no barrier, LDS or atomic),
-// so both are stored plainly and only the final store of x obeys `nt_store`.
-// float64 per component: a 8 + nu 8 + d out and back 16 + c out and back 16 + x 8 = 56 B/cell, 112 for both (nu read by each).
-// ------------------------------------------------------------------------------------------
-template <int V, int COMP, bool MET, bool NTS, int SEG>
-__global__ __launch_bounds__(BLOCK) void k_vvisc(
-    const real* __restrict__ a, real* __restrict__ cw, real* __restrict__ out, int64_t o0, u32 nouter, u32 nblk, int64_t nz,
-    int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, real dt, int bc, real fill, VolIdx kp, VolIdx mf, VolIdx mc, int ntl) {
-  typedef typename VecT<V>::type T;
-  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
-  const int64_t plane = ny * nx;
-  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
-  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row, which this lane owns too)
-#pragma unroll
-  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = col + (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx + i0;
-  const T one = splat<T>(real(1)), tdt = splat<T>(dt);
-  // u: nu left of the lane's vector (periodic: column nx - 1, extend: column 0 itself); v: the row below the segment
-  // (periodic: row ny - 1 below row 0, extend: row 0 itself); a fill edge loads the clamped cell and replaces it
-  const LaneEdges e = lane_edges<V>(i0, nx, bc, ntl);
-  const bool fill_e = (COMP == 0 ? e.edge_l : j0 == 0) && bc == XG_BC_FILL;
-  const int64_t rb = j0 > 0 ? j0 - 1 : ((bc == XG_BC_PERIODIC) ? ny - 1 : 0);
-
-  // nu is loaded per face (it is a field of the faces); the two metrics per face / level only when they vary along Z, else
-  // once (and not at all for a column of one level, which has no face)
-  T kr[SEG], mfr[SEG], mcr[SEG];
-  int64_t mfo = 0, mco = 0;
-  const int64_t kpb = area_outer_off(kp.ai, o);                 // nu's (Z, Y, X) volume of this lead index
-  const int64_t kpo = kpb + j0 * kp.sy + i0 * kp.sx;
-  if (MET) {
-    if (mf.p) {
-      mfo = area_outer_off(mf.ai, o) + j0 * mf.sy + i0 * mf.sx;
-      if (mf.sz == 0 && nz > 1) load_rows<T, SEG>(mfr, mf.p, mfo, mf.sy, mf.sx, nrow, (ntl & 8) != 0);
-    }
-    if (mc.p) {
-      mco = area_outer_off(mc.ai, o) + j0 * mc.sy + i0 * mc.sx;
-      if (mc.sz == 0 && nz > 1) load_rows<T, SEG>(mcr, mc.p, mco, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
-    }
-  }
-  // w = w[k + 1] on return from coef(k) (k < nz-1), which needs w = w[k] on entry (k > 0): the coefficients of level k
-  T w[SEG];
-  auto coef = [&](int64_t k, T (&a_)[SEG], T (&lo_)[SEG], T (&up_)[SEG], T (&b_)[SEG]) {
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) a_[s_] = *reinterpret_cast<const T*>(a + ro[s_] + k * plane);
-    if (MET && nz > 1) {
-      if (mc.p && mc.sz != 0) load_rows<T, SEG>(mcr, mc.p, mco + k * mc.sz, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
-    }
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) b_[s_] = one;
-    if (k > 0) {
-#pragma unroll
-      for (int s_ = 0; s_ < SEG; ++s_) {
-        T l = w[s_];
-        if (MET) {
-          if (mc.p) l = l / mcr[s_];
-        }
-        lo_[s_] = l;
-        b_[s_] = b_[s_] + l;
-      }
-    }
-    if (k + 1 < nz) {
-      // face k + 1: nu's rows and its neighbour, every load before the first shuffle
+      // face k + 1; nu: its rows and its neighbour, every load before the first shuffle
       const int64_t fz = (k + 1) * kp.sz;
-      load_rows<T, SEG>(kr, kp.p, kpo + fz, kp.sy, kp.sx, nrow, (ntl & 4) != 0);
+      if (NU || (SRC == VI_KAPPA && kp.sz != 0)) load_rows<T, SEG>(kr, kp.p, kpo + fz, kp.sy, kp.sx, nrow, (ntl & 4) != 0);
       T kap[SEG];
-      if (COMP == 0) {
+      if (SRC == VI_NU_U) {
         real kl[SEG];
 #pragma unroll
         for (int s_ = 0; s_ < SEG; ++s_)
@@ -2175,12 +2040,15 @@ __global__ __launch_bounds__(BLOCK) void k_vvisc(
         }
 #pragma unroll
         for (int s_ = 0; s_ < SEG; ++s_) kap[s_] = interp_left_of(kr[s_], fill_e ? fill : kl[s_]);
-      } else {
+      } else if (SRC == VI_NU_V) {
         T kb[1];
         load_rows<T, 1>(kb, kp.p, kpb + fz + rb * kp.sy + i0 * kp.sx, kp.sy, kp.sx, 1, (ntl & 4) != 0);
         if (fill_e) kb[0] = splat<T>(fill);
 #pragma unroll
         for (int s_ = 0; s_ < SEG; ++s_) kap[s_] = op2<XG_OP_INTERP>(s_ == 0 ? kb[0] : kr[(s_ > 0) ? s_ - 1 : 0], kr[s_]);
+      } else {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) kap[s_] = (SRC == VI_KAPPA) ? kr[s_] : one;
       }
       if (MET) {
         if (mf.p && mf.sz != 0) load_rows<T, SEG>(mfr, mf.p, mfo + (k + 1) * mf.sz, mf.sy, mf.sx, nrow, (ntl & 8) != 0);
@@ -2273,13 +2141,20 @@ __global__ __launch_bounds__(BLOCK) void k_vvisc(
 }
 
 // ------------------------------------------------------------------------------------------
-// K7n: the squared vertical shear and the gradient Richardson number at the flux faces of Z in ONE pass over
-// (lead, Z, Y, X), two or three fields in, one out (nz faces at Z:left, nz + 1 at Z:outer):
+// K7n / K7p, the Richardson family: the squared vertical shear, the gradient Richardson number or the Pacanowski-Philander
+// (1981) mixing coefficients at the flux faces of Z in ONE pass over (lead, Z, Y, X), two or three fields in, one or two
+// out (nz faces at Z:left, nz + 1 at Z:outer).  ONE kernel; MODE chooses the epilogue of a face, at compile time:
 //   du[k] = (u[k] - u[k-1]) [/ mu[k]]    at u's points,     dv[k] = (v[k] - v[k-1]) [/ mv[k]]    at v's points
 //   S2[k] = uz * uz + vz * vz,   uz = (du[j,i] + du[j,i+1]) * 0.5,   vz = (dv[j,i] + dv[j+1,i]) * 0.5      (no FMA)
-//   Ri[k] = ((b[k] - b[k-1]) [/ mb[k]]) / S2[k]                                                  (RI; without it: S2)
+//   N2[k] = (b[k] - b[k-1]) [/ mb[k]]                                          (RI_S2: S2 is the result, b is not read)
+//   Ri[k] = N2[k] / S2[k]                                                                         (RI_RI: the result)
+//   ri = N2 / (S2 + shear_floor)      rp = (ri + |ri|) * 0.5      den = 1 + alpha * rp                      (RI_MIX)
+//   nu = nu0 / (den * den) + nu_b     kappa = nu / den + kappa_b                      (no FMA, IEEE quotients; K7p)
 // i.e. diff | derivative (Z, center -> left | outer) of u, v and b, interp (X / Y, left -> center) of the first two, the
-// squares, their sum, the quotient: MITgcm's form, the shear averaged to the centre first and squared then.  Pads as the
+// squares, their sum, the quotient: MITgcm's form, the shear averaged to the centre first and squared then; the closure one
+// operation per line of the chain and two stores.  rp is max(ri, 0) for every finite ri (+0.0 for -0.0); a NaN stays one,
+// -inf gives NaN.  The second result and the closure's five scalars (in `real`) are arguments of every instance and are
+// read by RI_MIX alone; `bb`, the rows of mb and their offset are never formed under RI_S2.  Pads as the
 // chain's: u, v and b above level 0 and (`outer`) below level nz-1 (periodic: the far level, extend: the level itself,
 // fill: fill_z), then the DERIVATIVES right of the last column / above the last row (periodic: the derivative at index 0,
 // extend: at n-1, fill: the fill value itself).  No guard on S2 == 0: the quotient is IEEE's.
@@ -2287,26 +2162,31 @@ __global__ __launch_bounds__(BLOCK) void k_vvisc(
 // of the level above in registers -- SEG rows of u with the element right of the lane's vector where the lane forms that
 // derivative itself (the tile's last lane, the row's edge; every other lane takes the finished derivative from the lane
 // above by DPP), SEG + 1 rows of v (the row above the segment: an L2 hit, the next segment's first row), SEG rows of b.
-// u, v and b are read once and the result written once: 32 B/cell in float64 (S2: 24).  The three metrics (the Z metric at
-// u's points, at v's points, at the centre, all at the faces) are one broadcast array each, each may be absent; rows that
+// u, v and b are read once and each result written once: 32 B/cell in float64 (S2: 24, K7p: 40).  The three metrics (the
+// Z metric at u's points, at v's points, at the centre, all at the faces) are one broadcast array each, each may be absent; rows that
 // do not vary along Z are loaded once per wave.  Periodic Z costs one more level read before the march (and, `outer`, one
 // after it).
-// K7p (k_rimix, below) is a COPY of this kernel up to N2 and S2 -- fetch, padded, metrics, face, the march -- with another
-// epilogue: whatever is fixed or changed in the march here has to be made there too.
 // ------------------------------------------------------------------------------------------
+enum { RI_S2 = 0, RI_RI = 1, RI_MIX = 2 };  // k_richardson's MODE: out = S2 | out = Ri | out = nu and out2 = kappa
+
 template <typename T, int SEG>
 struct RiLevel {  // what one level of a column brings: SEG rows of u and b, SEG + 1 rows of v, u right of the lane
   T uu[SEG], vv[SEG + 1], bb[SEG];
   real ur[SEG];
 };
+struct RimixScalars {
+  real nu0, alpha, nu_b, kappa_b, floor;
+};
 
-template <int V, bool RI, bool MET, bool NTS, int SEG>
+template <int V, int MODE, bool MET, bool NTS, int SEG>
 __global__ __launch_bounds__(BLOCK) void k_richardson(
     const real* __restrict__ b, const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ out,
-    int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int bc_x,
-    real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mu, VolIdx mv, VolIdx mb, int ntl) {
+    real* __restrict__ out2, int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile,
+    FastDiv nseg, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mu, VolIdx mv,
+    VolIdx mb, int ntl, RimixScalars c) {
   typedef typename VecT<V>::type T;
   typedef RiLevel<T, SEG> L;
+  constexpr bool RI = MODE != RI_S2;  // b and its metric are read
   XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
   const int64_t plane = ny * nx;
   const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
@@ -2386,166 +2266,6 @@ __global__ __launch_bounds__(BLOCK) void k_richardson(
   }
 
   // one face from the level above it (`lo`) and the level below it (`hi`)
-  real* po = out + o * nf * plane + j0 * nx + i0;
-  auto face = [&](int64_t k, const L& lo, const L& hi) {
-    T du[SEG], dv[SEG + 1];
-    real dr[SEG];
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      du[s_] = op2<XG_OP_DIFF>(lo.uu[s_], hi.uu[s_]);
-      dr[s_] = hi.ur[s_] - lo.ur[s_];
-    }
-#pragma unroll
-    for (int s_ = 0; s_ < SEG + 1; ++s_) dv[s_] = op2<XG_OP_DIFF>(lo.vv[s_], hi.vv[s_]);
-    if (MET) {
-      if (mu.p) {
-#pragma unroll
-        for (int s_ = 0; s_ < SEG; ++s_) du[s_] = du[s_] / mur[s_];
-        if (e.own_r) {
-#pragma unroll
-          for (int s_ = 0; s_ < SEG; ++s_) dr[s_] = dr[s_] / mrr[s_];
-        }
-      }
-      if (mv.p) {
-#pragma unroll
-        for (int s_ = 0; s_ < SEG + 1; ++s_) dv[s_] = dv[s_] / mvr[s_];
-      }
-    }
-    if (e.shl) {
-#pragma unroll
-      for (int s_ = 0; s_ < SEG; ++s_) {
-        const real right = from_lane_above(vec_first(du[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
-        if (!e.own_r) dr[s_] = right;
-      }
-    }
-    const T top = fill_t ? splat<T>(fill_y) : dv[SEG];
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      if (s_ < nrow) {
-        const T uz = interp_right_of(du[s_], fill_r ? fill_x : dr[s_]);
-        const T vz = op2<XG_OP_INTERP>(dv[s_], (s_ + 1 < nrow) ? dv[s_ + 1] : top);
-        T z = uz * uz + vz * vz;
-        if (RI) {
-          T db = op2<XG_OP_DIFF>(lo.bb[s_], hi.bb[s_]);
-          if (MET) {
-            if (mb.p) db = db / mbr[s_];
-          }
-          z = db / z;
-        }
-        stg_s<T, NTS>(po + k * plane + s_ * nx, z);
-      }
-    }
-  };
-
-  // face 0 lies between the pad above level 0 and level 0; the march keeps the level above the face
-  L cur = fetch(0), prev;
-  if (bc_z == XG_BC_PERIODIC) prev = fetch(nz - 1);
-  else if (bc_z == XG_BC_EXTEND) prev = cur;
-  else prev = padded();
-  for (int64_t k = 0;;) {
-    face(k, prev, cur);
-    if (++k >= nf) break;
-    prev = cur;
-    if (k < nz) cur = fetch(k);                           // (`outer`, the last face: the pad below level nz-1 --
-    else if (bc_z == XG_BC_PERIODIC) cur = fetch(0);      //  extend: the level itself, which `cur` still holds)
-    else if (bc_z == XG_BC_FILL) cur = padded();
-    if (MET) metrics(k, false);
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// K7p: the Pacanowski-Philander (1981) mixing coefficients at the flux faces of Z in ONE pass over (lead, Z, Y, X), three
-// fields in, two out (nz faces at Z:left, nz + 1 at Z:outer): K7n's N2 and S2, line by line in its order, then the closure
-//   ri = N2 / (S2 + shear_floor)      rp = (ri + |ri|) * 0.5      den = 1 + alpha * rp
-//   nu = nu0 / (den * den) + nu_b     kappa = nu / den + kappa_b                                  (no FMA, IEEE quotients)
-// as the epilogue of every face, and two stores.  rp is max(ri, 0) for every finite ri (+0.0 for -0.0); a NaN stays one,
-// -inf gives NaN.  K7n's march, neighbours, pads and metrics unchanged: b, u and v are read once and each result written
-// once, 40 B/cell in float64.  The five scalars arrive in `real`.
-// ------------------------------------------------------------------------------------------
-struct RimixScalars {
-  real nu0, alpha, nu_b, kappa_b, floor;
-};
-
-template <int V, bool MET, bool NTS, int SEG>
-__global__ __launch_bounds__(BLOCK) void k_rimix(
-    const real* __restrict__ b, const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ out_nu,
-    real* __restrict__ out_kappa, int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile,
-    FastDiv nseg, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mu, VolIdx mv,
-    VolIdx mb, int ntl, RimixScalars c) {
-  typedef typename VecT<V>::type T;
-  typedef RiLevel<T, SEG> L;
-  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
-  const int64_t plane = ny * nx;
-  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
-  const int64_t nf = nz + outer;       // faces
-  // X and Y as K7n's: the column right of the lane's vector, the row above the segment; a fill edge replaces the value
-  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);  // (the right side only)
-  const bool fill_r = e.edge_r && bc_x == XG_BC_FILL;
-  const int64_t q = j0 + nrow;
-  const bool fill_t = q >= ny && bc_y == XG_BC_FILL;
-  const int64_t jt = (q < ny) ? q : ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1);  // the row the top derivative is formed at
-  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
-#pragma unroll
-  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
-
-  auto fetch = [&](int64_t k) -> L {
-    L x;
-    const int64_t lv = col + k * plane;
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      x.uu[s_] = *reinterpret_cast<const T*>(u + lv + ro[s_] + i0);
-      x.ur[s_] = e.own_r ? u[lv + ro[s_] + e.ridx] : real(0);
-      x.vv[s_] = *reinterpret_cast<const T*>(v + lv + ro[s_] + i0);
-      x.bb[s_] = *reinterpret_cast<const T*>(b + lv + ro[s_] + i0);
-    }
-    x.vv[SEG] = *reinterpret_cast<const T*>(v + lv + jt * nx + i0);
-    return x;
-  };
-  auto padded = [&]() -> L {  // a level of the fill value
-    L x;
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      x.uu[s_] = x.vv[s_] = x.bb[s_] = splat<T>(fill_z);
-      x.ur[s_] = fill_z;
-    }
-    x.vv[SEG] = splat<T>(fill_z);
-    return x;
-  };
-
-  // the metric rows of a face, as K7n holds them
-  T mur[SEG], mvr[SEG + 1], mbr[SEG];
-  real mrr[SEG];
-  int64_t muo = 0, mro = 0, mvo = 0, mto = 0, mbo = 0;
-  auto metrics = [&](int64_t k, bool first) {
-    if (mu.p && (first || mu.sz != 0)) {
-      load_rows<T, SEG>(mur, mu.p, muo + k * mu.sz, mu.sy, mu.sx, nrow, (ntl & 4) != 0);
-      if (e.own_r) {
-#pragma unroll
-        for (int s_ = 0; s_ < SEG; ++s_) mrr[s_] = mu.p[mro + k * mu.sz + ((s_ < nrow) ? s_ : nrow - 1) * mu.sy];
-      }
-    }
-    if (mv.p && (first || mv.sz != 0)) {
-      T rows[SEG];
-      load_rows<T, SEG>(rows, mv.p, mvo + k * mv.sz, mv.sy, mv.sx, nrow, (ntl & 8) != 0);
-#pragma unroll
-      for (int s_ = 0; s_ < SEG; ++s_) mvr[s_] = rows[s_];
-      T top[1];
-      load_rows<T, 1>(top, mv.p, mto + k * mv.sz, mv.sy, mv.sx, 1, (ntl & 8) != 0);
-      mvr[SEG] = top[0];
-    }
-    if (mb.p && (first || mb.sz != 0)) load_rows<T, SEG>(mbr, mb.p, mbo + k * mb.sz, mb.sy, mb.sx, nrow, (ntl & 16) != 0);
-  };
-  if (MET) {
-    const int64_t uo = mu.p ? area_outer_off(mu.ai, o) : 0, vo = mv.p ? area_outer_off(mv.ai, o) : 0;
-    muo = uo + j0 * mu.sy + i0 * mu.sx;
-    mro = uo + j0 * mu.sy + e.ridx * mu.sx;
-    mvo = vo + j0 * mv.sy + i0 * mv.sx;
-    mto = vo + jt * mv.sy + i0 * mv.sx;
-    if (mb.p) mbo = area_outer_off(mb.ai, o) + j0 * mb.sy + i0 * mb.sx;
-    metrics(0, true);
-  }
-
-  // one face from the level above it (`lo`) and the level below it (`hi`)
   const int64_t po = o * nf * plane + j0 * nx + i0;
   const T one = splat<T>(real(1)), half = splat<T>(real(0.5));
   auto face = [&](int64_t k, const L& lo, const L& hi) {
@@ -2586,19 +2306,27 @@ __global__ __launch_bounds__(BLOCK) void k_rimix(
         const T uz = interp_right_of(du[s_], fill_r ? fill_x : dr[s_]);
         const T vz = op2<XG_OP_INTERP>(dv[s_], (s_ + 1 < nrow) ? dv[s_ + 1] : top);
         const T s2 = uz * uz + vz * vz;
-        T db = op2<XG_OP_DIFF>(lo.bb[s_], hi.bb[s_]);
-        if (MET) {
-          if (mb.p) db = db / mbr[s_];
+        T db;
+        if (RI) {
+          db = op2<XG_OP_DIFF>(lo.bb[s_], hi.bb[s_]);
+          if (MET) {
+            if (mb.p) db = db / mbr[s_];
+          }
         }
-        // the closure, one operation per line of the chain
-        const T ri = db / (s2 + splat<T>(c.floor));
-        const T rp = (ri + __builtin_elementwise_abs(ri)) * half;
-        const T den = one + splat<T>(c.alpha) * rp;
-        const T nu = splat<T>(c.nu0) / (den * den) + splat<T>(c.nu_b);
-        const T ka = nu / den + splat<T>(c.kappa_b);
         const int64_t at = po + k * plane + s_ * nx;
-        stg_s<T, NTS>(out_nu + at, nu);
-        stg_s<T, NTS>(out_kappa + at, ka);
+        if (MODE == RI_MIX) {  // the closure, one operation per line of the chain
+          const T ri = db / (s2 + splat<T>(c.floor));
+          const T rp = (ri + __builtin_elementwise_abs(ri)) * half;
+          const T den = one + splat<T>(c.alpha) * rp;
+          const T nu = splat<T>(c.nu0) / (den * den) + splat<T>(c.nu_b);
+          const T ka = nu / den + splat<T>(c.kappa_b);
+          stg_s<T, NTS>(out + at, nu);
+          stg_s<T, NTS>(out2 + at, ka);
+        } else if (MODE == RI_RI) {
+          stg_s<T, NTS>(out + at, db / s2);
+        } else {
+          stg_s<T, NTS>(out + at, s2);
+        }
       }
     }
   };
@@ -2620,42 +2348,70 @@ __global__ __launch_bounds__(BLOCK) void k_rimix(
 }
 
 // ------------------------------------------------------------------------------------------
-// K7q: the isopycnal slopes at the flux faces of Z in ONE pass over (lead, Z, Y, X), one field in, two out (nz faces at
-// Z:left, nz + 1 at Z:outer).  Per level
+// K7q / K7r / K7s, the isopycnal family: ONE kernel, one pass over (lead, Z, Y, X), around one column stage.  Per level of
+// the field b
 //   g[i] = (b[i] - b[i-1]) [/ mx[i]]      G_x[i] = (g[i] + g[i+1]) * 0.5        and the same along Y with my: G_y
-// per face
-//   gx = (G_x[k-1] + G_x[k]) * 0.5    gy = (G_y[k-1] + G_y[k]) * 0.5    bz = (b[k] - b[k-1]) [/ mz[k]]
-//   sx = -1 * (gx / bz)               sy = -1 * (gy / bz)                                  (no FMA, IEEE quotients)
-// i.e. diff | derivative (X / Y, center -> left), interp back (left -> center), interp (Z, center -> left | outer); diff |
-// derivative (Z) of b; the two quotients, negated.  Pads as the chain's: b left of column 0 / below row 0, then the
-// DERIVATIVE right of the last column / above the last row (periodic: the derivative at index 0, extend: at n-1, fill: the
-// fill value itself), then the LEVEL MEANS G above level 0 and (`outer`) below level nz-1 (periodic: the far level's,
-// extend: the level's own, fill: fill_z itself); b along Z as K7n's.  No guard on bz == 0.
+// per face (nz of them at Z:left, nz + 1 at Z:outer)
+//   gx = (G_x[k-1] + G_x[k]) * 0.5    gy = (G_y[k-1] + G_y[k]) * 0.5
+// i.e. diff | derivative (X / Y, center -> left), interp back (left -> center), interp (Z, center -> left | outer).  Pads as
+// the chain's: b left of column 0 / below row 0, then the DERIVATIVE right of the last column / above the last row (periodic:
+// the derivative at index 0, extend: at n-1, fill: the fill value itself), then the LEVEL MEANS G above level 0 and (`outer`)
+// below level nz-1 (periodic: the far level's, extend: the level's own, fill: fill_z itself).  MODE chooses, at compile
+// time, what a face does with gx and gy:
+// IS_SLOPE (K7q), the isopycnal slopes, one field in, two out at the faces:
+//   bz = (b[k] - b[k-1]) [/ mz[k]]    sx = -1 * (gx / bz)    sy = -1 * (gy / bz)           (no FMA, IEEE quotients)
+// diff | derivative (Z) of b, b along Z padded as K7n's; the two quotients, negated.  No guard on bz == 0.  24 B/cell in
+// float64.
+// IS_TENSOR (K7r), the tapered Redi / Gent-McWilliams tensor column, three out at the faces: sx and sy, then
+//   s2 = sx * sx + sy * sy
+//   ex = s2 - m2      den = m2 + (ex + |ex|) * 0.5      kt = kappa * (m2 / den)       (`taper`; else kt = kappa)
+//   Kwx = kt * sx     Kwy = kt * sy     Kwz = kt * s2                                   (no FMA, IEEE quotients)
+// as the epilogue of every face, and three stores.  den is max(s2, m2) (Gerdes, Koeberle and Willebrand 1991: the taper is
+// min(1, m2 / s2), no square root): where s2 <= m2, ex + |ex| is +0.0, den is m2 and the taper exactly 1; an infinite slope
+// gives taper 0 and 0 * inf = NaN; a NaN stays one.  32 B/cell in float64.  kappa and m2 arrive in `real`; `taper` is
+// wave-uniform.
+// IS_FLUX (K7s), the divergence of the off-diagonal vertical isoneutral flux of a tracer, d/dz(Kwx <da/dx> + Kwy <da/dy>):
+// the tracer (as `b`) and the two tensor components of K7r in (kwx and kwy, at the faces), one field out at the levels:
+//   f[k] = kwx[k] * gx + kwy[k] * gy                        out[k] = (f[k+1] - f[k]) [/ mc[k]]                (no FMA)
+// K7l's flux march with f[k] in registers; the level carries no b, and the third metric is mc at the LEVELS, held by K7l's
+// rule.  `closed` (wave-uniform): no flux through the top and the bottom -- face 0 and, `outer`, face nz are +0.0; their kwx
+// and kwy rows are not loaded and no pad level is formed for them, so nothing there reaches the result.  Otherwise the level
+// means are padded as above.  `left`: the FLUX beyond level nz-1 is padded as K7l's (periodic: f[0] -- closed: that +0.0 --,
+// extend: f[nz-1], fill: fill_z itself).  32 B/cell in float64.
 // K7n's wave-task and march: a wave owns one (lead, Y segment, X tile) column and keeps the level above the face in
-// registers -- not its rows but what the faces need of it, G_x, G_y and b of the segment.  A level brings SEG + 2 rows of b
-// (the row below and the row above the segment: L2 hits, the neighbouring segments' rows) and, for the segment's rows, the
-// element left of and right of the lane's vector: b left of it from the lane below by DPP, the finished derivative right of
-// it from the lane above by DPP; the tile's first / last lane and the row's edges load their own.  The rows of the level
-// below the next face are requested before a face's quotients.  b is read once and each result written once: 24 B/cell in float64.
-// mx at b's levels and u's columns, my at b's levels and v's rows, mz at the faces: one broadcast array each, each may be
-// absent; rows that do not vary along Z are loaded once per wave, mx also at the column right of the lane, my also at the
-// row above the segment.  Periodic Z costs one more level before the march (and, `outer`, one after it).
+// registers -- not its rows but what the faces need of it, G_x, G_y and (but IS_FLUX) b of the segment.  A level brings
+// SEG + 2 rows of b (the row below and the row above the segment: L2 hits, the neighbouring segments' rows) and, for the
+// segment's rows, the element left of and right of the lane's vector: b left of it from the lane below by DPP, the finished
+// derivative right of it from the lane above by DPP; the tile's first / last lane and the row's edges load their own.  WHEN
+// the rows of the level below the next face are asked for differs by MODE, for the registers: see the marches.  Every field
+// is read once and each result written once.  mx at b's levels and u's columns, my at b's levels and v's rows, mz at the
+// faces (IS_FLUX: mc at the levels): one broadcast array each, each may be absent; rows that do not vary along Z are loaded
+// once per wave, mx also at the column right of the lane, my also at the row above the segment.  Periodic Z costs one more
+// level before the march (and, `outer`, one after it).  The arguments are the union of the three: kwx, kwy and `closed` are
+// read by IS_FLUX alone, out_y not by it, out_z and `c` by IS_TENSOR alone.
 // ------------------------------------------------------------------------------------------
+enum { IS_SLOPE = 0, IS_TENSOR = 1, IS_FLUX = 2 };  // k_islope's MODE
+
 template <typename T, int SEG>
 struct IsRows {  // what one level of a column brings: the row below, SEG rows with b left and right of the lane, the row above
   T bb[SEG], below, above;
   real bl[SEG], br[SEG];
 };
 template <typename T, int SEG>
-struct IsLevel {  // what a face needs of a level
+struct IsLevel {  // what a face needs of a level (IS_FLUX: `bb` is never formed)
   T gx[SEG], gy[SEG], bb[SEG];
 };
+struct RediScalars {
+  real kappa, m2;
+  int taper;
+};
 
-template <int V, bool MET, bool NTS, int SEG>
+template <int V, int MODE, bool MET, bool NTS, int SEG>
 __global__ __launch_bounds__(BLOCK) void k_islope(
-    const real* __restrict__ b, real* __restrict__ out_x, real* __restrict__ out_y, int64_t o0, u32 nouter, u32 nblk,
-    int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int bc_x, real fill_x, int bc_y, real fill_y,
-    int bc_z, real fill_z, VolIdx mx, VolIdx my, VolIdx mz, int ntl) {
+    const real* __restrict__ b, const real* __restrict__ kwx, const real* __restrict__ kwy, real* __restrict__ out_x,
+    real* __restrict__ out_y, real* __restrict__ out_z, int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx,
+    FastDiv ntile, FastDiv nseg, int outer, int closed, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z,
+    VolIdx mx, VolIdx my, VolIdx mz, int ntl, RediScalars c) {
   typedef typename VecT<V>::type T;
   typedef IsRows<T, SEG> Rows;
   typedef IsLevel<T, SEG> L;
@@ -2681,205 +2437,14 @@ __global__ __launch_bounds__(BLOCK) void k_islope(
 #pragma unroll
   for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
 
-  // the rows of mx and my of a level: in registers, loaded again per level only when the array varies along Z
-  T mxr[SEG], myr[SEG], myt;
+  // the rows of mx and my of a level: in registers, loaded again per level only when the array varies along Z; the rows of
+  // the third metric likewise, of a face (IS_FLUX: of a level, as K7l holds them)
+  T mxr[SEG], myr[SEG], myt, mzc[SEG];
   real mxrr[SEG];
   int64_t mxo = 0, mro = 0, myo = 0, mto = 0, mzo = 0;
-  auto hmetrics = [&](int64_t k, bool first) {
-    if (mx.p && (first || mx.sz != 0)) {
-      load_rows<T, SEG>(mxr, mx.p, mxo + k * mx.sz, mx.sy, mx.sx, nrow, (ntl & 4) != 0);
-      if (e.own_r) {
-#pragma unroll
-        for (int s_ = 0; s_ < SEG; ++s_) mxrr[s_] = mx.p[mro + k * mx.sz + ((s_ < nrow) ? s_ : nrow - 1) * mx.sy];
-      }
-    }
-    if (my.p && (first || my.sz != 0)) {
-      load_rows<T, SEG>(myr, my.p, myo + k * my.sz, my.sy, my.sx, nrow, (ntl & 8) != 0);
-      T top[1];
-      load_rows<T, 1>(top, my.p, mto + k * my.sz, my.sy, my.sx, 1, (ntl & 8) != 0);
-      myt = top[0];
-    }
-  };
-  if (MET) {
-    const int64_t xo = mx.p ? area_outer_off(mx.ai, o) : 0, yo = my.p ? area_outer_off(my.ai, o) : 0;
-    mxo = xo + j0 * mx.sy + i0 * mx.sx;
-    mro = xo + j0 * mx.sy + e.ridx * mx.sx;
-    myo = yo + j0 * my.sy + i0 * my.sx;
-    mto = yo + jt * my.sy + i0 * my.sx;
-    if (mz.p) mzo = area_outer_off(mz.ai, o) + j0 * mz.sy + i0 * mz.sx;
-    hmetrics(0, true);
-  }
-
-  auto fetch = [&](int64_t k) -> Rows {  // (with the level's own mx and my rows: `level` is the only reader of both)
-    Rows x;
-    const int64_t lv = col + k * plane;
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      x.bb[s_] = *reinterpret_cast<const T*>(b + lv + ro[s_] + i0);
-      x.bl[s_] = e.own_l ? b[lv + ro[s_] + e.lidx] : real(0);
-      x.br[s_] = e.own_r ? b[lv + ro[s_] + e.ridx] : real(0);
-    }
-    x.below = *reinterpret_cast<const T*>(b + lv + jb * nx + i0);
-    x.above = *reinterpret_cast<const T*>(b + lv + jt * nx + i0);
-    if (MET) hmetrics(k, false);
-    return x;
-  };
-  // G_x, G_y and b of the segment from the rows of a level
-  auto level = [&](const Rows& x) -> L {
-    L r;
-    T g[SEG], h[SEG];
-    real gr[SEG];
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      real left = x.bl[s_];
-      if (e.shl) {
-        const real dpp = from_lane_below(vec_last(x.bb[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
-        if (!e.own_l) left = dpp;
-      }
-      if (fill_l) left = fill_x;
-      g[s_] = dvdx_of(x.bb[s_], left);
-      gr[s_] = x.br[s_] - vec_last(x.bb[s_]);
-      const T lower = (s_ == 0) ? (fill_b ? splat<T>(fill_y) : x.below) : x.bb[(s_ > 0) ? s_ - 1 : 0];
-      h[s_] = x.bb[s_] - lower;
-    }
-    T top = x.above - x.bb[SEG - 1];  // (short tails repeat the last row: bb[SEG - 1] is row nrow - 1)
-    if (MET) {
-      if (mx.p) {
-#pragma unroll
-        for (int s_ = 0; s_ < SEG; ++s_) g[s_] = g[s_] / mxr[s_];
-        if (e.own_r) {
-#pragma unroll
-          for (int s_ = 0; s_ < SEG; ++s_) gr[s_] = gr[s_] / mxrr[s_];
-        }
-      }
-      if (my.p) {
-#pragma unroll
-        for (int s_ = 0; s_ < SEG; ++s_) h[s_] = h[s_] / myr[s_];
-        top = top / myt;
-      }
-    }
-    if (e.shl) {
-#pragma unroll
-      for (int s_ = 0; s_ < SEG; ++s_) {
-        const real right = from_lane_above(vec_first(g[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
-        if (!e.own_r) gr[s_] = right;
-      }
-    }
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      if (pad_r) gr[s_] = (bc_x == XG_BC_FILL) ? fill_x : vec_last(g[s_]);
-      r.gx[s_] = interp_right_of(g[s_], gr[s_]);
-      T up = (s_ + 1 < nrow) ? h[(s_ + 1 < SEG) ? s_ + 1 : s_] : top;
-      if (s_ + 1 >= nrow && pad_t) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : h[s_];
-      r.gy[s_] = op2<XG_OP_INTERP>(h[s_], up);
-      r.bb[s_] = x.bb[s_];
-    }
-    return r;
-  };
-  auto padded = [&]() -> L {  // a level of the fill value: the pad of the level means and of b
-    L r;
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) r.gx[s_] = r.gy[s_] = r.bb[s_] = splat<T>(fill_z);
-    return r;
-  };
-
-  // one face from the level above it (`lo`) and the level below it (`hi`)
-  const int64_t po = o * nf * plane + j0 * nx + i0;
-  const T minus = splat<T>(real(-1));
-  auto face = [&](int64_t k, const L& lo, const L& hi, const T (&mzr)[SEG]) {
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      if (s_ < nrow) {
-        const T gx = op2<XG_OP_INTERP>(lo.gx[s_], hi.gx[s_]);
-        const T gy = op2<XG_OP_INTERP>(lo.gy[s_], hi.gy[s_]);
-        T bz = op2<XG_OP_DIFF>(lo.bb[s_], hi.bb[s_]);
-        if (MET) {
-          if (mz.p) bz = bz / mzr[s_];
-        }
-        const int64_t at = po + k * plane + s_ * nx;
-        stg_s<T, NTS>(out_x + at, minus * (gx / bz));
-        stg_s<T, NTS>(out_y + at, minus * (gy / bz));
-      }
-    }
-  };
-
-  // face 0 lies between the pad above level 0 and level 0; the march keeps the level above the face, and has the rows of
-  // the level below the NEXT face on their way while a face's quotients run.  The next face's mz rows are asked for after
-  // the face: a second set of them in flight beside the rows costs the float64 metric instance its third wave per SIMD
-  // (175 VGPRs against 167; 11.7 against 10.4 ms on 4320 x 4320 x 90 -- EXPERIMENTS.md "K7q")
-  T mzc[SEG];
   auto zmetric = [&](T (&dst)[SEG], int64_t k, bool first) {
     if (mz.p && (first || mz.sz != 0)) load_rows<T, SEG>(dst, mz.p, mzo + k * mz.sz, mz.sy, mz.sx, nrow, (ntl & 16) != 0);
   };
-  L prev;
-  if (per_z) prev = level(fetch(nz - 1));
-  L cur = level(fetch(0));
-  if (bc_z == XG_BC_EXTEND) prev = cur;
-  else if (bc_z == XG_BC_FILL) prev = padded();
-  if (MET) zmetric(mzc, 0, true);
-  for (int64_t k = 0;;) {
-    const int64_t kn = k + 1;
-    const bool more = kn < nf, read = kn < nz || (more && per_z);  // (`outer`, the last face: the pad below level nz-1)
-    Rows nxt;
-    if (read) nxt = fetch(kn < nz ? kn : 0);
-    face(k, prev, cur, mzc);
-    if (!more) break;
-    if (MET) zmetric(mzc, kn, false);
-    prev = cur;
-    if (read) cur = level(nxt);                      // (extend: the level itself, which `cur` still holds)
-    else if (bc_z == XG_BC_FILL) cur = padded();
-    k = kn;
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// K7r: the tapered Redi / Gent-McWilliams tensor column at the flux faces of Z in ONE pass over (lead, Z, Y, X), one field
-// in, three out (nz faces at Z:left, nz + 1 at Z:outer): K7q's sx and sy, line by line in its order, then
-//   s2 = sx * sx + sy * sy
-//   ex = s2 - m2      den = m2 + (ex + |ex|) * 0.5      kt = kappa * (m2 / den)       (`taper`; else kt = kappa)
-//   Kwx = kt * sx     Kwy = kt * sy     Kwz = kt * s2                                   (no FMA, IEEE quotients)
-// as the epilogue of every face, and three stores.  den is max(s2, m2) (Gerdes, Koeberle and Willebrand 1991: the taper is
-// min(1, m2 / s2), no square root): where s2 <= m2, ex + |ex| is +0.0, den is m2 and the taper exactly 1; an infinite slope
-// gives taper 0 and 0 * inf = NaN; a NaN stays one.  K7q is untouched: this kernel is a COPY of it up to sx and sy -- fetch,
-// level, padded, the metrics and the march (but for WHEN a level's rows are asked for, see the march) -- as K7p is of K7n.
-// b is read once and each result written once, 32 B/cell in float64.  kappa and m2 arrive in `real`; `taper` is
-// wave-uniform.
-// ------------------------------------------------------------------------------------------
-struct RediScalars {
-  real kappa, m2;
-  int taper;
-};
-
-template <int V, bool MET, bool NTS, int SEG>
-__global__ __launch_bounds__(BLOCK) void k_reditensor(
-    const real* __restrict__ b, real* __restrict__ out_x, real* __restrict__ out_y, real* __restrict__ out_z, int64_t o0,
-    u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int bc_x, real fill_x,
-    int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mx, VolIdx my, VolIdx mz, int ntl, RediScalars c) {
-  typedef typename VecT<V>::type T;
-  typedef IsRows<T, SEG> Rows;
-  typedef IsLevel<T, SEG> L;
-  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
-  const int64_t plane = ny * nx;
-  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
-  const int64_t nf = nz + outer;       // faces
-  // X and Y as K7q's: the columns left and right of the lane's vector, the row below and the row above the segment
-  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);
-  const bool per_x = bc_x == XG_BC_PERIODIC, per_z = bc_z == XG_BC_PERIODIC;
-  const bool fill_l = e.edge_l && bc_x == XG_BC_FILL;
-  const bool pad_r = e.edge_r && !per_x;
-  const bool fill_b = j0 == 0 && bc_y == XG_BC_FILL;
-  const int64_t jb = (j0 > 0) ? j0 - 1 : ((bc_y == XG_BC_PERIODIC) ? ny - 1 : 0);
-  const int64_t q = j0 + nrow;
-  const bool pad_t = q >= ny && bc_y != XG_BC_PERIODIC;
-  const int64_t jt = (q < ny) ? q : ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1);
-  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
-#pragma unroll
-  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
-
-  // the rows of mx and my of a level, as K7q holds them
-  T mxr[SEG], myr[SEG], myt;
-  real mxrr[SEG];
-  int64_t mxo = 0, mro = 0, myo = 0, mto = 0, mzo = 0;
   auto hmetrics = [&](int64_t k, bool first) {
     if (mx.p && (first || mx.sz != 0)) {
       load_rows<T, SEG>(mxr, mx.p, mxo + k * mx.sz, mx.sy, mx.sx, nrow, (ntl & 4) != 0);
@@ -2902,6 +2467,7 @@ __global__ __launch_bounds__(BLOCK) void k_reditensor(
     myo = yo + j0 * my.sy + i0 * my.sx;
     mto = yo + jt * my.sy + i0 * my.sx;
     if (mz.p) mzo = area_outer_off(mz.ai, o) + j0 * mz.sy + i0 * mz.sx;
+    if (MODE == IS_FLUX) zmetric(mzc, 0, true);
     hmetrics(0, true);
   }
 
@@ -2967,19 +2533,22 @@ __global__ __launch_bounds__(BLOCK) void k_reditensor(
       T up = (s_ + 1 < nrow) ? h[(s_ + 1 < SEG) ? s_ + 1 : s_] : top;
       if (s_ + 1 >= nrow && pad_t) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : h[s_];
       r.gy[s_] = op2<XG_OP_INTERP>(h[s_], up);
-      r.bb[s_] = x.bb[s_];
+      if (MODE != IS_FLUX) r.bb[s_] = x.bb[s_];
     }
     return r;
   };
   auto padded = [&]() -> L {  // a level of the fill value: the pad of the level means and of b
     L r;
 #pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) r.gx[s_] = r.gy[s_] = r.bb[s_] = splat<T>(fill_z);
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      r.gx[s_] = r.gy[s_] = splat<T>(fill_z);
+      if (MODE != IS_FLUX) r.bb[s_] = splat<T>(fill_z);
+    }
     return r;
   };
 
-  // one face from the level above it (`lo`) and the level below it (`hi`): K7q's slopes, then the tensor column, one
-  // operation per line of the chain
+  // IS_SLOPE, IS_TENSOR: one face from the level above it (`lo`) and the level below it (`hi`): the slopes, then (IS_TENSOR)
+  // the tensor column, one operation per line of the chain
   const int64_t po = o * nf * plane + j0 * nx + i0;
   const T minus = splat<T>(real(-1)), half = splat<T>(real(0.5)), m2 = splat<T>(c.m2), kappa = splat<T>(c.kappa);
   const bool taper = c.taper != 0;
@@ -2995,203 +2564,62 @@ __global__ __launch_bounds__(BLOCK) void k_reditensor(
         }
         const T sx = minus * (gx / bz);
         const T sy = minus * (gy / bz);
-        const T s2 = sx * sx + sy * sy;
-        T kt = kappa;
-        if (taper) {
-          const T ex = s2 - m2;
-          const T den = m2 + (ex + __builtin_elementwise_abs(ex)) * half;
-          kt = kappa * (m2 / den);
-        }
         const int64_t at = po + k * plane + s_ * nx;
-        stg_s<T, NTS>(out_x + at, kt * sx);
-        stg_s<T, NTS>(out_y + at, kt * sy);
-        stg_s<T, NTS>(out_z + at, kt * s2);
-      }
-    }
-  };
-
-  // the march keeps the level above the face, as K7q's; the rows of the level below the NEXT face are asked for AFTER the
-  // face, not before it as in K7q: with a third product, a third quotient and s2 alive through the epilogue, rows in flight
-  // beside it cost the float64 metric instance its third wave per SIMD (171 VGPRs, 14.7 ms on 4320 x 4320 x 90); the rows
-  // ahead without the two edge elements keep it (162) at 13.0 - 13.2 ms, nothing ahead (144) runs in 11.5 ms
-  // (EXPERIMENTS.md "K7r").  The next face's mz rows are asked for after the face, as in K7q
-  T mzc[SEG];
-  auto zmetric = [&](T (&dst)[SEG], int64_t k, bool first) {
-    if (mz.p && (first || mz.sz != 0)) load_rows<T, SEG>(dst, mz.p, mzo + k * mz.sz, mz.sy, mz.sx, nrow, (ntl & 16) != 0);
-  };
-  L prev;
-  if (per_z) prev = level(fetch(nz - 1));
-  L cur = level(fetch(0));
-  if (bc_z == XG_BC_EXTEND) prev = cur;
-  else if (bc_z == XG_BC_FILL) prev = padded();
-  if (MET) zmetric(mzc, 0, true);
-  for (int64_t k = 0;;) {
-    const int64_t kn = k + 1;
-    const bool more = kn < nf, read = kn < nz || (more && per_z);  // (`outer`, the last face: the pad below level nz-1)
-    face(k, prev, cur, mzc);
-    if (!more) break;
-    if (MET) zmetric(mzc, kn, false);
-    prev = cur;
-    if (read) cur = level(fetch(kn < nz ? kn : 0));  // (extend: the level itself, which `cur` still holds)
-    else if (bc_z == XG_BC_FILL) cur = padded();
-    k = kn;
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// K7s: the divergence of the off-diagonal vertical isoneutral flux of a tracer, d/dz(Kwx <da/dx> + Kwy <da/dy>), in ONE pass
-// over (lead, Z, Y, X): the tracer and the two tensor components of K7r in, one field out.  Per level K7q's G_x and G_y of
-// `a`, line by line in its order (fetch, level, the X and Y pads, mx and my); per face k (nz of them at Z:left, nz + 1 at
-// Z:outer, where kwx and kwy sit)
-//   gx = (G_x[k-1] + G_x[k]) * 0.5    gy = (G_y[k-1] + G_y[k]) * 0.5    f[k] = kwx[k] * gx + kwy[k] * gy     (no FMA)
-// and per level K7l's flux march
-//   out[k] = (f[k+1] - f[k]) [/ mc[k]]
-// with f[k] in registers.  `closed` (wave-uniform): no flux through the top and the bottom -- face 0 and, `outer`, face nz are
-// +0.0; their kwx and kwy rows are not loaded and no pad level is formed for them, so nothing there reaches the result.
-// Otherwise the level means above level 0 and (`outer`) below level nz-1 are padded as K7q's (periodic: the far level's,
-// extend: the level's own, fill: fill_z itself).  `left`: the FLUX beyond level nz-1 is padded as K7l's (periodic: f[0] --
-// closed: that +0.0 --, extend: f[nz-1], fill: fill_z itself).  The level stage is a COPY of K7q's without b, as K7r is of
-// K7q; a level's rows are asked for after the store of the level above, K7r's order, at ONE place in the march, and the two
-// tensor rows of the face after the level's means are formed.  a, kwx and kwy are read once and out written once: 32 B/cell
-// in float64.  mc follows K7l's rule: rows that do not vary along Z are loaded once per wave.
-// ------------------------------------------------------------------------------------------
-template <typename T, int SEG>
-struct RfLevel {  // what a face needs of a level
-  T gx[SEG], gy[SEG];
-};
-
-template <int V, bool MET, bool NTS, int SEG>
-__global__ __launch_bounds__(BLOCK) void k_rediflux(
-    const real* __restrict__ a, const real* __restrict__ kwx, const real* __restrict__ kwy, real* __restrict__ out, int64_t o0,
-    u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int closed, int bc_x,
-    real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mx, VolIdx my, VolIdx mc, int ntl) {
-  typedef typename VecT<V>::type T;
-  typedef IsRows<T, SEG> Rows;
-  typedef RfLevel<T, SEG> L;
-  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
-  const int64_t plane = ny * nx;
-  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64: a 4320^2 x 90 field has more than 2^32 cells)
-  const int64_t nf = nz + outer;       // faces
-  // X and Y as K7q's: the columns left and right of the lane's vector, the row below and the row above the segment
-  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);
-  const bool per_x = bc_x == XG_BC_PERIODIC, per_z = bc_z == XG_BC_PERIODIC;
-  const bool fill_l = e.edge_l && bc_x == XG_BC_FILL;
-  const bool pad_r = e.edge_r && !per_x;
-  const bool fill_b = j0 == 0 && bc_y == XG_BC_FILL;
-  const int64_t jb = (j0 > 0) ? j0 - 1 : ((bc_y == XG_BC_PERIODIC) ? ny - 1 : 0);
-  const int64_t q = j0 + nrow;
-  const bool pad_t = q >= ny && bc_y != XG_BC_PERIODIC;
-  const int64_t jt = (q < ny) ? q : ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1);
-  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
-#pragma unroll
-  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
-
-  // the rows of mx and my of a level, as K7q holds them; the rows of mc as K7l holds them
-  T mxr[SEG], myr[SEG], myt, mcr[SEG];
-  real mxrr[SEG];
-  int64_t mxo = 0, mro = 0, myo = 0, mto = 0, mco = 0;
-  auto hmetrics = [&](int64_t k, bool first) {
-    if (mx.p && (first || mx.sz != 0)) {
-      load_rows<T, SEG>(mxr, mx.p, mxo + k * mx.sz, mx.sy, mx.sx, nrow, (ntl & 4) != 0);
-      if (e.own_r) {
-#pragma unroll
-        for (int s_ = 0; s_ < SEG; ++s_) mxrr[s_] = mx.p[mro + k * mx.sz + ((s_ < nrow) ? s_ : nrow - 1) * mx.sy];
-      }
-    }
-    if (my.p && (first || my.sz != 0)) {
-      load_rows<T, SEG>(myr, my.p, myo + k * my.sz, my.sy, my.sx, nrow, (ntl & 8) != 0);
-      T top[1];
-      load_rows<T, 1>(top, my.p, mto + k * my.sz, my.sy, my.sx, 1, (ntl & 8) != 0);
-      myt = top[0];
-    }
-  };
-  if (MET) {
-    const int64_t xo = mx.p ? area_outer_off(mx.ai, o) : 0, yo = my.p ? area_outer_off(my.ai, o) : 0;
-    mxo = xo + j0 * mx.sy + i0 * mx.sx;
-    mro = xo + j0 * mx.sy + e.ridx * mx.sx;
-    myo = yo + j0 * my.sy + i0 * my.sx;
-    mto = yo + jt * my.sy + i0 * my.sx;
-    if (mc.p) {
-      mco = area_outer_off(mc.ai, o) + j0 * mc.sy + i0 * mc.sx;
-      load_rows<T, SEG>(mcr, mc.p, mco, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
-    }
-    hmetrics(0, true);
-  }
-
-  auto fetch = [&](int64_t k) -> Rows {  // (with the level's own mx and my rows: `level` is the only reader of both)
-    Rows x;
-    const int64_t lv = col + k * plane;
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      x.bb[s_] = *reinterpret_cast<const T*>(a + lv + ro[s_] + i0);
-      x.bl[s_] = e.own_l ? a[lv + ro[s_] + e.lidx] : real(0);
-      x.br[s_] = e.own_r ? a[lv + ro[s_] + e.ridx] : real(0);
-    }
-    x.below = *reinterpret_cast<const T*>(a + lv + jb * nx + i0);
-    x.above = *reinterpret_cast<const T*>(a + lv + jt * nx + i0);
-    if (MET) hmetrics(k, false);
-    return x;
-  };
-  // G_x and G_y of the segment from the rows of a level
-  auto level = [&](const Rows& x) -> L {
-    L r;
-    T g[SEG], h[SEG];
-    real gr[SEG];
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      real left = x.bl[s_];
-      if (e.shl) {
-        const real dpp = from_lane_below(vec_last(x.bb[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
-        if (!e.own_l) left = dpp;
-      }
-      if (fill_l) left = fill_x;
-      g[s_] = dvdx_of(x.bb[s_], left);
-      gr[s_] = x.br[s_] - vec_last(x.bb[s_]);
-      const T lower = (s_ == 0) ? (fill_b ? splat<T>(fill_y) : x.below) : x.bb[(s_ > 0) ? s_ - 1 : 0];
-      h[s_] = x.bb[s_] - lower;
-    }
-    T top = x.above - x.bb[SEG - 1];  // (short tails repeat the last row: bb[SEG - 1] is row nrow - 1)
-    if (MET) {
-      if (mx.p) {
-#pragma unroll
-        for (int s_ = 0; s_ < SEG; ++s_) g[s_] = g[s_] / mxr[s_];
-        if (e.own_r) {
-#pragma unroll
-          for (int s_ = 0; s_ < SEG; ++s_) gr[s_] = gr[s_] / mxrr[s_];
+        if (MODE == IS_TENSOR) {
+          const T s2 = sx * sx + sy * sy;
+          T kt = kappa;
+          if (taper) {
+            const T ex = s2 - m2;
+            const T den = m2 + (ex + __builtin_elementwise_abs(ex)) * half;
+            kt = kappa * (m2 / den);
+          }
+          stg_s<T, NTS>(out_x + at, kt * sx);
+          stg_s<T, NTS>(out_y + at, kt * sy);
+          stg_s<T, NTS>(out_z + at, kt * s2);
+        } else {
+          stg_s<T, NTS>(out_x + at, sx);
+          stg_s<T, NTS>(out_y + at, sy);
         }
       }
-      if (my.p) {
-#pragma unroll
-        for (int s_ = 0; s_ < SEG; ++s_) h[s_] = h[s_] / myr[s_];
-        top = top / myt;
-      }
     }
-    if (e.shl) {
-#pragma unroll
-      for (int s_ = 0; s_ < SEG; ++s_) {
-        const real right = from_lane_above(vec_first(g[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
-        if (!e.own_r) gr[s_] = right;
-      }
-    }
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) {
-      if (pad_r) gr[s_] = (bc_x == XG_BC_FILL) ? fill_x : vec_last(g[s_]);
-      r.gx[s_] = interp_right_of(g[s_], gr[s_]);
-      T up = (s_ + 1 < nrow) ? h[(s_ + 1 < SEG) ? s_ + 1 : s_] : top;
-      if (s_ + 1 >= nrow && pad_t) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : h[s_];
-      r.gy[s_] = op2<XG_OP_INTERP>(h[s_], up);
-    }
-    return r;
-  };
-  auto padded = [&]() -> L {  // a level of the fill value: the pad of the level means
-    L r;
-#pragma unroll
-    for (int s_ = 0; s_ < SEG; ++s_) r.gx[s_] = r.gy[s_] = splat<T>(fill_z);
-    return r;
   };
 
-  // the flux at face k from the level above it (`lo`) and the level below it (`hi`): the face's rows of kwx and kwy, 16-byte
-  // loads, once; two products, then the sum
+  if (MODE != IS_FLUX) {
+    // face 0 lies between the pad above level 0 and level 0; the march keeps the level above the face.  IS_SLOPE has the
+    // rows of the level below the NEXT face on their way while a face's quotients run.  The next face's mz rows are asked
+    // for after the face: a second set of them in flight beside the rows costs the float64 metric instance its third wave
+    // per SIMD (175 VGPRs against 167; 11.7 against 10.4 ms on 4320 x 4320 x 90 -- EXPERIMENTS.md "K7q").
+    // IS_TENSOR asks for the rows of the level below the next face AFTER the face, not before it: with a third product, a
+    // third quotient and s2 alive through the epilogue, rows in flight beside it cost the float64 metric instance its third
+    // wave per SIMD (171 VGPRs, 14.7 ms on 4320 x 4320 x 90); the rows ahead without the two edge elements keep it (162) at
+    // 13.0 - 13.2 ms, nothing ahead (144) runs in 11.5 ms (EXPERIMENTS.md "K7r")
+    L prev;
+    if (per_z) prev = level(fetch(nz - 1));
+    L cur = level(fetch(0));
+    if (bc_z == XG_BC_EXTEND) prev = cur;
+    else if (bc_z == XG_BC_FILL) prev = padded();
+    if (MET) zmetric(mzc, 0, true);
+    for (int64_t k = 0;;) {
+      const int64_t kn = k + 1;
+      const bool more = kn < nf, read = kn < nz || (more && per_z);  // (`outer`, the last face: the pad below level nz-1)
+      Rows nxt;
+      if (MODE == IS_SLOPE && read) nxt = fetch(kn < nz ? kn : 0);
+      face(k, prev, cur, mzc);
+      if (!more) break;
+      if (MET) zmetric(mzc, kn, false);
+      prev = cur;
+      if (read) {                                      // (extend: the level itself, which `cur` still holds)
+        if (MODE == IS_TENSOR) nxt = fetch(kn < nz ? kn : 0);
+        cur = level(nxt);
+      } else if (bc_z == XG_BC_FILL) cur = padded();
+      k = kn;
+    }
+    return;
+  }
+
+  // IS_FLUX: a level's rows are asked for after the store of the level above, IS_TENSOR's order, at ONE place in the march,
+  // and the two tensor rows of the face after the level's means are formed.  The flux at face k from the level above it
+  // (`lo`) and the level below it (`hi`): the face's rows of kwx and kwy, 16-byte loads, once; two products, then the sum
   const int64_t fo = o * nf * plane + i0;
   auto flux = [&](int64_t k, const L& lo, const L& hi, T (&f)[SEG]) {
     T kx[SEG], ky[SEG];
@@ -3224,7 +2652,7 @@ __global__ __launch_bounds__(BLOCK) void k_rediflux(
     else if (bc_z == XG_BC_FILL) prev = padded();
     flux(0, prev, cur, fc);
   }
-  real* po = out + col + j0 * nx + i0;
+  real* pc = out_x + col + j0 * nx + i0;
   for (int64_t k = 0; k < nz; ++k) {
     const bool more = k + 1 < nz;
     // the flux below level k is formed from two levels: an interior face; the open last face of `outer` (the pad below
@@ -3245,17 +2673,15 @@ __global__ __launch_bounds__(BLOCK) void k_rediflux(
       for (int s_ = 0; s_ < SEG; ++s_)
         fn[s_] = (outer || per_z) ? splat<T>(real(0)) : ((bc_z == XG_BC_EXTEND) ? fc[s_] : splat<T>(fill_z));
     }
-    if (MET && k > 0) {
-      if (mc.p && mc.sz != 0) load_rows<T, SEG>(mcr, mc.p, mco + k * mc.sz, mc.sy, mc.sx, nrow, (ntl & 16) != 0);
-    }
+    if (MET && k > 0) zmetric(mzc, k, false);  // (the rows of mc of level k)
 #pragma unroll
     for (int s_ = 0; s_ < SEG; ++s_) {
       if (s_ < nrow) {
         T z = op2<XG_OP_DIFF>(fc[s_], fn[s_]);
         if (MET) {
-          if (mc.p) z = z / mcr[s_];
+          if (mz.p) z = z / mzc[s_];
         }
-        stg_s<T, NTS>(po + k * plane + s_ * nx, z);
+        stg_s<T, NTS>(pc + k * plane + s_ * nx, z);
       }
     }
 #pragma unroll
@@ -4040,6 +3466,25 @@ int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int
 }
 #endif
 
+// The launches of K7m / K7o, the implicit sweeps: one field, its workspace and its result, the coefficient's source `src`
+// (k_vimpl's SRC) with its array `kp` (kappa or nu; `bc` and `fill` pad nu), the metric of the flux and of the result.
+static int vimpl_launch(const FusedPlan& p, int src, const real* a, real* work, real* out, real dt, int bc, real fill,
+                        const VolIdx& kp, const VolIdx& mf, const VolIdx& mc, int vnt) {
+  const bool met = mf.p != nullptr || mc.p != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, K_, M_, NTS) do { hipLaunchKernelGGL((k_vimpl<V_, K_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, a, work, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, dt, kp, mf, mc, vnt, bc, fill); } while (0)
+#define XG_N(V_, K_, M_) do { if (p.nts) XG_GO(V_, K_, M_, true); else XG_GO(V_, K_, M_, false); } while (0)
+#define XG_M(V_, K_) do { if (met) XG_N(V_, K_, true); else XG_N(V_, K_, false); } while (0)
+#define XG_V(V_) do { if (src == VI_NU_V) XG_M(V_, VI_NU_V); else if (src == VI_NU_U) XG_M(V_, VI_NU_U); else if (src == VI_KAPPA) XG_M(V_, VI_KAPPA); else XG_M(V_, VI_ONE); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_M
+#undef XG_N
+#undef XG_GO
+  });
+}
+
 // K7m's launcher: K7l's arguments without a boundary (the solve is the no-flux one) and with a workspace of the field's shape
 // for the forward sweep's c.  `outer` only says how many faces kappa and mf have (nz or nz + 1): faces 1 .. nz-1 are read
 // either way, at the same strides.  One ABI entry for both element types (xg_implicit_vertical_diffusion, below).
@@ -4074,19 +3519,7 @@ int XG_FN(xg_internal_vimpl)(const real* a, const real* kappa, const int64_t* ka
   int vnt = 0;
   for (int k = 0; k < 3; ++k)
     if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
-  const bool kap = kappa != nullptr, met = mf != nullptr || mc != nullptr;
-  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
-#define XG_GO(V_, K_, M_, NTS) do { hipLaunchKernelGGL((k_vimpl<V_, K_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, a, work, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, dt, mi[0], mi[1], mi[2], vnt); } while (0)
-#define XG_N(V_, K_, M_) do { if (p.nts) XG_GO(V_, K_, M_, true); else XG_GO(V_, K_, M_, false); } while (0)
-#define XG_M(V_, K_) do { if (met) XG_N(V_, K_, true); else XG_N(V_, K_, false); } while (0)
-#define XG_V(V_) do { if (kap) XG_M(V_, true); else XG_M(V_, false); } while (0)
-    if (p.V > 1) XG_V(NV);
-    else XG_V(1);
-#undef XG_V
-#undef XG_M
-#undef XG_N
-#undef XG_GO
-  });
+  return vimpl_launch(p, kappa ? VI_KAPPA : VI_ONE, a, work, out, dt, XG_BC_EXTEND, real(0), mi[0], mi[1], mi[2], vnt);
 }
 
 #ifdef XG_PRIMARY
@@ -4109,7 +3542,8 @@ int xg_implicit_vertical_diffusion(int dtype, const void* a, const void* kappa, 
 // K7o's launcher: K7m's arguments twice -- u and v, a workspace and a result each, the metric of the flux and of the result at
 // u's and at v's points -- with ONE nu at the centre points of the faces and the boundaries that pad it along X and Y.  One
 // plan for both components (same shape; the lane width is NV only when all six field pointers are 16-byte aligned), one launch
-// per component.  One ABI entry for both element types (xg_implicit_vertical_viscosity, below).
+// of k_vimpl per component (SRC VI_NU_U, then VI_NU_V).  One ABI entry for both element types
+// (xg_implicit_vertical_viscosity, below).
 __attribute__((visibility("hidden"))) int xg_internal_vvisc_f64(
     const double* u, const double* v, const double* nu, const int64_t* nu_strides, const double* const met[4],
     const int64_t* const met_strides[4], double* work_u, double* work_v, double* out_u, double* out_v, const int64_t* shape,
@@ -4149,19 +3583,7 @@ int XG_FN(xg_internal_vvisc)(const real* u, const real* v, const real* nu, const
     // bit 0: the lane neighbour by DPP (K7j; u only), bits 2 / 3 / 4: the rows of nu / the flux metric / the result's metric
     // are aligned vectors
     const int vnt = (c == 0 ? vec_nt_bits(1) : 0) | (vec(ni) ? 4 : 0) | (vec(mf) ? 8 : 0) | (vec(mc) ? 16 : 0);
-    const bool met_ = mf.p != nullptr || mc.p != nullptr;
-    rc = fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
-#define XG_GO(V_, C_, M_, NTS) do { hipLaunchKernelGGL((k_vvisc<V_, C_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, fa[c], fw[c], fo[c], o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, dt, fbc[c], ffill[c], ni, mf, mc, vnt); } while (0)
-#define XG_N(V_, C_, M_) do { if (p.nts) XG_GO(V_, C_, M_, true); else XG_GO(V_, C_, M_, false); } while (0)
-#define XG_M(V_, C_) do { if (met_) XG_N(V_, C_, true); else XG_N(V_, C_, false); } while (0)
-#define XG_V(V_) do { if (c == 0) XG_M(V_, 0); else XG_M(V_, 1); } while (0)
-      if (p.V > 1) XG_V(NV);
-      else XG_V(1);
-#undef XG_V
-#undef XG_M
-#undef XG_N
-#undef XG_GO
-    });
+    rc = vimpl_launch(p, c == 0 ? VI_NU_U : VI_NU_V, fa[c], fw[c], fo[c], dt, fbc[c], ffill[c], ni, mf, mc, vnt);
     if (rc) return rc;
   }
   return XG_OK;
@@ -4194,9 +3616,50 @@ int xg_implicit_vertical_viscosity(int dtype, const void* u, const void* v, cons
 }
 #endif
 
-// K7n's launcher: (lead, Z, Y, X) fields of `shape`, the result with nz (`outer`: nz + 1) faces, three optional broadcast
-// metrics at the faces (the Z metric at u's points, at v's points, at the centre), one wave per column.  b NULL: the squared
-// shear alone, and `mb` is not looked at.  One ABI entry for both element types (xg_richardson_number, below).
+// The Richardson family's launcher, K7n and K7p: (lead, Z, Y, X) fields of `shape`, the results with nz (`outer`: nz + 1)
+// faces, three optional broadcast metrics at the faces (the Z metric at u's points, at v's points, at the centre), one wave
+// per column.  `mode` RI_MIX: b and both results required, `c` the closure's scalars.  Otherwise one result, and b NULL
+// gives the squared shear alone (`mb` is not looked at).
+static int richardson_family(int mode, const char* name, const real* b, const real* u, const real* v, const real* mu,
+                             const int64_t* mu_strides, const real* mv, const int64_t* mv_strides, const real* mb,
+                             const int64_t* mb_strides, const RimixScalars& c, real* out, real* out2, const int64_t* shape,
+                             int ndim, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z,
+                             void* stream) {
+  if (!u || !v || !out || !shape || (mode == RI_MIX && (!b || !out2))) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  if (!b) mb = nullptr;
+  if (mode != RI_MIX) mode = b ? RI_RI : RI_S2;
+  FusedPlan p;
+  const bool al = aligned16(u) && aligned16(v) && aligned16(b) && aligned16(out) && aligned16(out2);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  VolIdx mi[3];  // the Z metric at u's points, at v's points, at the centre
+  const real* mp[3] = {mu, mv, mb};
+  const int64_t* ms[3] = {mu_strides, mv_strides, mb_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  // bit 0: the lane neighbour by DPP (K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
+  int vnt = vec_nt_bits(1);
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool met = mu != nullptr || mv != nullptr || mb != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, R_, M_, NTS) do { hipLaunchKernelGGL((k_richardson<V_, R_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, u, v, out, out2, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt, c); } while (0)
+#define XG_N(V_, R_, M_) do { if (p.nts) XG_GO(V_, R_, M_, true); else XG_GO(V_, R_, M_, false); } while (0)
+#define XG_M(V_, R_) do { if (met) XG_N(V_, R_, true); else XG_N(V_, R_, false); } while (0)
+#define XG_V(V_) do { if (mode == RI_MIX) XG_M(V_, RI_MIX); else if (mode == RI_RI) XG_M(V_, RI_RI); else XG_M(V_, RI_S2); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_M
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+// One ABI entry for both element types each (xg_richardson_number, xg_richardson_mixing, below).
 __attribute__((visibility("hidden"))) int xg_internal_richardson_f64(
     const double* b, const double* u, const double* v, const double* mu, const int64_t* mu_strides, const double* mv,
     const int64_t* mv_strides, const double* mb, const int64_t* mb_strides, double* out, const int64_t* shape, int ndim,
@@ -4210,38 +3673,8 @@ int XG_FN(xg_internal_richardson)(const real* b, const real* u, const real* v, c
                                   const real* mv, const int64_t* mv_strides, const real* mb, const int64_t* mb_strides,
                                   real* out, const int64_t* shape, int ndim, int outer, int bc_x, real fill_x, int bc_y,
                                   real fill_y, int bc_z, real fill_z, void* stream) {
-  const char* name = "richardson number";
-  if (!u || !v || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  int rc;
-  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
-  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
-  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
-  if (!b) mb = nullptr;
-  FusedPlan p;
-  const bool al = aligned16(u) && aligned16(v) && aligned16(b) && aligned16(out);
-  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
-  VolIdx mi[3];  // the Z metric at u's points, at v's points, at the centre
-  const real* mp[3] = {mu, mv, mb};
-  const int64_t* ms[3] = {mu_strides, mv_strides, mb_strides};
-  for (int k = 0; k < 3; ++k)
-    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
-  // bit 0: the lane neighbour by DPP (K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
-  int vnt = vec_nt_bits(1);
-  for (int k = 0; k < 3; ++k)
-    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
-  const bool ri = b != nullptr, met = mu != nullptr || mv != nullptr || mb != nullptr;
-  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
-#define XG_GO(V_, R_, M_, NTS) do { hipLaunchKernelGGL((k_richardson<V_, R_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, u, v, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt); } while (0)
-#define XG_N(V_, R_, M_) do { if (p.nts) XG_GO(V_, R_, M_, true); else XG_GO(V_, R_, M_, false); } while (0)
-#define XG_M(V_, R_) do { if (met) XG_N(V_, R_, true); else XG_N(V_, R_, false); } while (0)
-#define XG_V(V_) do { if (ri) XG_M(V_, true); else XG_M(V_, false); } while (0)
-    if (p.V > 1) XG_V(NV);
-    else XG_V(1);
-#undef XG_V
-#undef XG_M
-#undef XG_N
-#undef XG_GO
-  });
+  return richardson_family(RI_RI, "richardson number", b, u, v, mu, mu_strides, mv, mv_strides, mb, mb_strides,
+                           RimixScalars{}, out, nullptr, shape, ndim, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, stream);
 }
 
 #ifdef XG_PRIMARY
@@ -4262,8 +3695,6 @@ int xg_richardson_number(int dtype, const void* b, const void* u, const void* v,
 }
 #endif
 
-// K7p's launcher: K7n's with b required, the closure's five scalars in `real` and two results.  One ABI entry for both
-// element types (xg_richardson_mixing, below).
 __attribute__((visibility("hidden"))) int xg_internal_rimix_f64(
     const double* b, const double* u, const double* v, const double* mu, const int64_t* mu_strides, const double* mv,
     const int64_t* mv_strides, const double* mb, const int64_t* mb_strides, double nu0, double alpha, double nu_b,
@@ -4280,36 +3711,9 @@ int XG_FN(xg_internal_rimix)(const real* b, const real* u, const real* v, const 
                              real alpha, real nu_b, real kappa_b, real shear_floor, real* out_nu, real* out_kappa,
                              const int64_t* shape, int ndim, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
                              real fill_z, void* stream) {
-  const char* name = "richardson mixing";
-  if (!b || !u || !v || !out_nu || !out_kappa || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  int rc;
-  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
-  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
-  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
-  FusedPlan p;
-  const bool al = aligned16(u) && aligned16(v) && aligned16(b) && aligned16(out_nu) && aligned16(out_kappa);
-  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
-  VolIdx mi[3];  // the Z metric at u's points, at v's points, at the centre
-  const real* mp[3] = {mu, mv, mb};
-  const int64_t* ms[3] = {mu_strides, mv_strides, mb_strides};
-  for (int k = 0; k < 3; ++k)
-    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
-  // bit 0: the lane neighbour by DPP (K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
-  int vnt = vec_nt_bits(1);
-  for (int k = 0; k < 3; ++k)
-    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
-  const bool met = mu != nullptr || mv != nullptr || mb != nullptr;
-  const RimixScalars c = {nu0, alpha, nu_b, kappa_b, shear_floor};
-  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
-#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_rimix<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, u, v, out_nu, out_kappa, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt, c); } while (0)
-#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
-#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
-    if (p.V > 1) XG_V(NV);
-    else XG_V(1);
-#undef XG_V
-#undef XG_N
-#undef XG_GO
-  });
+  return richardson_family(RI_MIX, "richardson mixing", b, u, v, mu, mu_strides, mv, mv_strides, mb, mb_strides,
+                           RimixScalars{nu0, alpha, nu_b, kappa_b, shear_floor}, out_nu, out_kappa, shape, ndim, outer, bc_x,
+                           fill_x, bc_y, fill_y, bc_z, fill_z, stream);
 }
 
 #ifdef XG_PRIMARY
@@ -4334,9 +3738,61 @@ int xg_richardson_mixing(int dtype, const void* b, const void* u, const void* v,
 }
 #endif
 
-// K7q's launcher: a (lead, Z, Y, X) field of `shape`, both results with nz (`outer`: nz + 1) faces, three optional
-// broadcast metrics (mx and my at the field's levels, mz at the faces), one wave per column.  One ABI entry for both
-// element types (xg_isopycnal_slope, below).
+// The isopycnal family's launcher, K7q, K7r and K7s: a (lead, Z, Y, X) field of `shape`, three optional broadcast metrics
+// (mx and my at the field's levels; the third at the faces, IS_FLUX: mc at the levels), one wave per column.  IS_SLOPE:
+// out_x and out_y with nz (`outer`: nz + 1) faces.  IS_TENSOR: out_z too, and the tensor's scalars in `c` (already in
+// `real`).  IS_FLUX: kwx and kwy at the faces, `closed`, and out_x, the one result, of `shape`.
+static int isopycnal_family(int mode, const char* name, const real* b, const real* kwx, const real* kwy, const real* mx,
+                            const int64_t* mx_strides, const real* my, const int64_t* my_strides, const real* mz,
+                            const int64_t* mz_strides, const RediScalars& c, real* out_x, real* out_y, real* out_z,
+                            const int64_t* shape, int ndim, int outer, int closed, int bc_x, real fill_x, int bc_y,
+                            real fill_y, int bc_z, real fill_z, void* stream) {
+  if (!b || !out_x || !shape || (mode == IS_FLUX ? (!kwx || !kwy) : !out_y) || (mode == IS_TENSOR && !out_z))
+    return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (c.taper != 0 && c.taper != 1) return fail(XG_ERR_INVALID, "%s: taper %d is neither 0 nor 1", name, c.taper);
+  if (closed != 0 && closed != 1) return fail(XG_ERR_INVALID, "%s: closed %d is neither 0 nor 1", name, closed);
+  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  if (mode == IS_TENSOR) {  // the three results, (lead, nz + outer, ny, nx) each, may not overlap
+    int64_t n = shape[ndim - 3] + outer;
+    for (int d = 0; d < ndim; ++d)
+      if (d != ndim - 3) n *= shape[d];
+    const real* r[3] = {out_x, out_y, out_z};
+    for (int i = 0; i < 3; ++i)
+      for (int j = i + 1; j < 3; ++j)
+        if (n > 0 && (uintptr_t)r[i] < (uintptr_t)(r[j] + n) && (uintptr_t)r[j] < (uintptr_t)(r[i] + n))
+          return fail(XG_ERR_INVALID, "%s: the results overlap", name);
+  }
+  VolIdx mi[3];
+  const real* mp[3] = {mx, my, mz};
+  const int64_t* ms[3] = {mx_strides, my_strides, mz_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  FusedPlan p;
+  const bool al = aligned16(b) && aligned16(kwx) && aligned16(kwy) && aligned16(out_x) && aligned16(out_y) && aligned16(out_z);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  // bit 0: the lane neighbours by DPP (K7c, K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
+  int vnt = vec_nt_bits(1);
+  for (int k = 0; k < 3; ++k)
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
+  const bool met = mx != nullptr || my != nullptr || mz != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, O_, M_, NTS) do { hipLaunchKernelGGL((k_islope<V_, O_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, kwx, kwy, out_x, out_y, out_z, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, closed, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt, c); } while (0)
+#define XG_N(V_, O_, M_) do { if (p.nts) XG_GO(V_, O_, M_, true); else XG_GO(V_, O_, M_, false); } while (0)
+#define XG_M(V_, O_) do { if (met) XG_N(V_, O_, true); else XG_N(V_, O_, false); } while (0)
+#define XG_V(V_) do { if (mode == IS_FLUX) XG_M(V_, IS_FLUX); else if (mode == IS_TENSOR) XG_M(V_, IS_TENSOR); else XG_M(V_, IS_SLOPE); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_M
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+// One ABI entry for both element types each (xg_isopycnal_slope, xg_redi_tensor, xg_redi_vertical_flux_divergence, below).
 __attribute__((visibility("hidden"))) int xg_internal_islope_f64(
     const double* b, const double* mx, const int64_t* mx_strides, const double* my, const int64_t* my_strides,
     const double* mz, const int64_t* mz_strides, double* out_x, double* out_y, const int64_t* shape, int ndim, int outer,
@@ -4350,35 +3806,9 @@ int XG_FN(xg_internal_islope)(const real* b, const real* mx, const int64_t* mx_s
                               const int64_t* my_strides, const real* mz, const int64_t* mz_strides, real* out_x, real* out_y,
                               const int64_t* shape, int ndim, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
                               real fill_z, void* stream) {
-  const char* name = "isopycnal slope";
-  if (!b || !out_x || !out_y || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  int rc;
-  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
-  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
-  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
-  VolIdx mi[3];  // mx and my at the field's levels, mz at the faces
-  const real* mp[3] = {mx, my, mz};
-  const int64_t* ms[3] = {mx_strides, my_strides, mz_strides};
-  for (int k = 0; k < 3; ++k)
-    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
-  FusedPlan p;
-  const bool al = aligned16(b) && aligned16(out_x) && aligned16(out_y);
-  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
-  // bit 0: the lane neighbours by DPP (K7c, K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
-  int vnt = vec_nt_bits(1);
-  for (int k = 0; k < 3; ++k)
-    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
-  const bool met = mx != nullptr || my != nullptr || mz != nullptr;
-  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
-#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_islope<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, out_x, out_y, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt); } while (0)
-#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
-#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
-    if (p.V > 1) XG_V(NV);
-    else XG_V(1);
-#undef XG_V
-#undef XG_N
-#undef XG_GO
-  });
+  return isopycnal_family(IS_SLOPE, "isopycnal slope", b, nullptr, nullptr, mx, mx_strides, my, my_strides, mz, mz_strides,
+                          RediScalars{}, out_x, out_y, nullptr, shape, ndim, outer, 0, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z,
+                          stream);
 }
 
 #ifdef XG_PRIMARY
@@ -4399,7 +3829,6 @@ int xg_isopycnal_slope(int dtype, const void* b, const void* mx, const int64_t* 
 }
 #endif
 
-// K7r's launcher: K7q's, with a third result and the two scalars of the tensor (already in `real`) and the taper flag
 __attribute__((visibility("hidden"))) int xg_internal_reditensor_f64(
     const double* b, const double* mx, const int64_t* mx_strides, const double* my, const int64_t* my_strides,
     const double* mz, const int64_t* mz_strides, double kappa, double slope_max2, int taper, double* out_x, double* out_y,
@@ -4416,47 +3845,9 @@ int XG_FN(xg_internal_reditensor)(const real* b, const real* mx, const int64_t* 
                                   real slope_max2, int taper, real* out_x, real* out_y, real* out_z, const int64_t* shape,
                                   int ndim, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z,
                                   void* stream) {
-  const char* name = "redi tensor";
-  if (!b || !out_x || !out_y || !out_z || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  int rc;
-  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
-  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
-  if (taper != 0 && taper != 1) return fail(XG_ERR_INVALID, "%s: taper %d is neither 0 nor 1", name, taper);
-  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
-  {  // the three results, (lead, nz + outer, ny, nx) each, may not overlap
-    int64_t n = shape[ndim - 3] + outer;
-    for (int d = 0; d < ndim; ++d)
-      if (d != ndim - 3) n *= shape[d];
-    const real* r[3] = {out_x, out_y, out_z};
-    for (int i = 0; i < 3; ++i)
-      for (int j = i + 1; j < 3; ++j)
-        if (n > 0 && (uintptr_t)r[i] < (uintptr_t)(r[j] + n) && (uintptr_t)r[j] < (uintptr_t)(r[i] + n))
-          return fail(XG_ERR_INVALID, "%s: the results overlap", name);
-  }
-  VolIdx mi[3];  // mx and my at the field's levels, mz at the faces
-  const real* mp[3] = {mx, my, mz};
-  const int64_t* ms[3] = {mx_strides, my_strides, mz_strides};
-  for (int k = 0; k < 3; ++k)
-    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
-  FusedPlan p;
-  const bool al = aligned16(b) && aligned16(out_x) && aligned16(out_y) && aligned16(out_z);
-  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
-  // bit 0: the lane neighbours by DPP (K7c, K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
-  int vnt = vec_nt_bits(1);
-  for (int k = 0; k < 3; ++k)
-    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
-  const bool met = mx != nullptr || my != nullptr || mz != nullptr;
-  const RediScalars c = {kappa, slope_max2, taper};
-  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
-#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_reditensor<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, out_x, out_y, out_z, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt, c); } while (0)
-#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
-#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
-    if (p.V > 1) XG_V(NV);
-    else XG_V(1);
-#undef XG_V
-#undef XG_N
-#undef XG_GO
-  });
+  return isopycnal_family(IS_TENSOR, "redi tensor", b, nullptr, nullptr, mx, mx_strides, my, my_strides, mz, mz_strides,
+                          RediScalars{kappa, slope_max2, taper}, out_x, out_y, out_z, shape, ndim, outer, 0, bc_x, fill_x, bc_y,
+                          fill_y, bc_z, fill_z, stream);
 }
 
 #ifdef XG_PRIMARY
@@ -4479,8 +3870,6 @@ int xg_redi_tensor(int dtype, const void* b, const void* mx, const int64_t* mx_s
 }
 #endif
 
-// K7s's launcher: K7q's plan and dispatch; `a` and the result of `shape`, kwx and kwy with nz (`outer`: nz + 1) faces, three
-// optional broadcast metrics, all at the field's levels (mx at u's columns, my at v's rows, mc at the centre)
 __attribute__((visibility("hidden"))) int xg_internal_rediflux_f64(
     const double* a, const double* kwx, const double* kwy, const double* mx, const int64_t* mx_strides, const double* my,
     const int64_t* my_strides, const double* mc, const int64_t* mc_strides, double* out, const int64_t* shape, int ndim,
@@ -4494,36 +3883,9 @@ int XG_FN(xg_internal_rediflux)(const real* a, const real* kwx, const real* kwy,
                                 const real* my, const int64_t* my_strides, const real* mc, const int64_t* mc_strides, real* out,
                                 const int64_t* shape, int ndim, int outer, int closed, int bc_x, real fill_x, int bc_y,
                                 real fill_y, int bc_z, real fill_z, void* stream) {
-  const char* name = "redi vertical flux divergence";
-  if (!a || !kwx || !kwy || !out || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
-  int rc;
-  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
-  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
-  if (closed != 0 && closed != 1) return fail(XG_ERR_INVALID, "%s: closed %d is neither 0 nor 1", name, closed);
-  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
-  VolIdx mi[3];  // all three at the field's levels
-  const real* mp[3] = {mx, my, mc};
-  const int64_t* ms[3] = {mx_strides, my_strides, mc_strides};
-  for (int k = 0; k < 3; ++k)
-    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
-  FusedPlan p;
-  const bool al = aligned16(a) && aligned16(kwx) && aligned16(kwy) && aligned16(out);
-  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
-  // bit 0: the lane neighbours by DPP (K7c, K7g), bits 2 / 3 / 4: the rows of the three metrics are aligned vectors
-  int vnt = vec_nt_bits(1);
-  for (int k = 0; k < 3; ++k)
-    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= 4 << k;
-  const bool met = mx != nullptr || my != nullptr || mc != nullptr;
-  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
-#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_rediflux<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, a, kwx, kwy, out, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, closed, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt); } while (0)
-#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
-#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
-    if (p.V > 1) XG_V(NV);
-    else XG_V(1);
-#undef XG_V
-#undef XG_N
-#undef XG_GO
-  });
+  return isopycnal_family(IS_FLUX, "redi vertical flux divergence", a, kwx, kwy, mx, mx_strides, my, my_strides, mc,
+                          mc_strides, RediScalars{}, out, nullptr, nullptr, shape, ndim, outer, closed, bc_x, fill_x, bc_y,
+                          fill_y, bc_z, fill_z, stream);
 }
 
 #ifdef XG_PRIMARY
