@@ -79,7 +79,8 @@ typedef enum xg_status {
   XG_OK = 0,
   XG_ERR_INVALID = -1,     /* bad argument (shape/axis/widths inconsistent, NULL pointer ...) */
   XG_ERR_UNSUPPORTED = -2, /* valid request this build cannot serve (ndim > XG_MAX_NDIM ...)  */
-  XG_ERR_HIP = -3          /* HIP runtime error; text in xg_last_error                        */
+  XG_ERR_HIP = -3,         /* HIP runtime error; text in xg_last_error                        */
+  XG_DECLINED = 1          /* xg_stencil_multi only: nothing was launched, use the single-operator entries */
 } xg_status;
 
 /* raw two-point bodies, xgcm/gridops.py:23-24,76-77,123-126,172-175 */
@@ -868,6 +869,28 @@ typedef enum xg_dtype {
  * when the element sizes agree. */
 int xg_convert(const void* src, int src_type, void* dst, int dst_type, uint64_t n, int via_type,
                double scale, int flags, void* stream);
+
+/* ---- up to four two-point stencils of ONE field in one pass ------------------------------- */
+/* One descriptor per result: out = OP(P[i], P[i+1]), P = pad(in, (pad_lo, pad_hi), bc, fill) along `axis` -- what
+ * xg_stencil1d_f64 / _f32 computes without metrics, bit for bit.  `out` has the shape of `in`. */
+typedef struct xg_multi_desc {
+  int op;            /* XG_OP_DIFF .. XG_OP_MAX */
+  int axis;          /* ndim - 1 (the contiguous dim) or ndim - 2 */
+  int pad_lo, pad_hi; /* (1,0) or (0,1) */
+  int bc;            /* XG_BC_PERIODIC, XG_BC_FILL or XG_BC_EXTEND */
+  double fill;       /* cast to the element type (-0.0 and NaN keep their bits) */
+  void* out;
+} xg_multi_desc;
+/* `in` (ndim 2 or 3, element type `dtype`: XG_T_F64 or XG_T_F32) is read ONCE and the n (1 to 4) results are written by one
+ * kernel: 8 + 8 n bytes per cell instead of 16 n for n calls of xg_stencil1d (f64).  One entry for both element types, as
+ * the one-pass operators above.  XG_ERR_INVALID: a NULL pointer, n outside [1, 4], an unknown op or element type.  Every
+ * other request this kernel does not serve -- ndim other than 2 or 3, another axis, other pads, XG_BC_NONE / XG_BC_HALO,
+ * rows whose byte length or whose addresses are no multiple of 16, an empty array, 2^31 cells or more, an `out` that
+ * overlaps `in` or another `out` -- returns XG_DECLINED: nothing was launched, nothing is wrong, and the caller runs
+ * xg_stencil1d_* once per descriptor.  A decline DOES set the text of xg_last_error ("declined: <which condition>"), so that
+ * a caller can tell why; like every text there it describes the last non-zero status only. */
+int xg_stencil_multi(int dtype, const void* in, const int64_t* shape, int ndim, int n,
+                     const xg_multi_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -226,6 +226,18 @@ SIGNATURES["xg_redi_vertical_flux_divergence"] = (C.c_int, [C.c_int, _vp, _vp, _
                                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
                                                           C.c_int, C.c_double, _vp])
 
+
+
+class MultiDesc(C.Structure):
+    """struct xg_multi_desc: one result of xg_stencil_multi"""
+
+    _fields_ = [("op", C.c_int), ("axis", C.c_int), ("pad_lo", C.c_int), ("pad_hi", C.c_int), ("bc", C.c_int),
+                ("fill", C.c_double), ("out", _vp)]
+
+
+DECLINED = 1  # XG_DECLINED: xg_stencil_multi launched nothing; the caller runs the single-operator entries
+SIGNATURES["xg_stencil_multi"] = (C.c_int, [C.c_int, _vp, _i64p, C.c_int, C.c_int, C.POINTER(MultiDesc), _vp])
+
 SUFFIX ={"float64": "f64", "float32": "f32", "int64": "i64", "int32": "i32"}
 
 _lib: Optional[C.CDLL] = None

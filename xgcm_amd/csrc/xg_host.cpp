@@ -1331,6 +1331,61 @@ int hvisc(const R* u, const R* v, const R* const pl[8], const int64_t* const ps[
   return XG_OK;
 }
 
+// xg_stencil_multi: up to four plain two-point results of one (outer, ny, nx) field, one cell at a time; what is declined is
+// what the header lists (the kernel's conditions: the device layer then behaves alike over both builds)
+template <typename R>
+int stencil_multi(const R* in, const int64_t* shape, int ndim, int n, const xg_multi_desc* desc) {
+  if (!in || !shape || !desc) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (n < 1 || n > 4) return fail(XG_ERR_INVALID, "%d results asked of one pass (1 to 4)", n);
+  for (int i = 0; i < n; ++i) {
+    if (!desc[i].out) return fail(XG_ERR_INVALID, "NULL array argument");
+    if (desc[i].op < XG_OP_DIFF || desc[i].op > XG_OP_MAX) return fail(XG_ERR_INVALID, "unknown op %d", desc[i].op);
+  }
+  if (ndim != 2 && ndim != 3) return fail(XG_DECLINED, "declined: %d dims", ndim);
+  const int64_t nx = shape[ndim - 1], ny = shape[ndim - 2], outer = (ndim == 3) ? shape[0] : 1;
+  if (nx < 1 || ny < 1 || outer < 1) return fail(XG_DECLINED, "declined: an empty array");
+  const int64_t nv = 16 / (int64_t)sizeof(R);
+  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  if (nx % nv || !aligned(in)) return fail(XG_DECLINED, "declined: rows are not whole 16-byte lane vectors");
+  const int64_t lim = 0x7fffffffll;
+  if (nx > lim || ny > lim || outer > lim || nx * ny > lim || nx * ny * outer > lim) return fail(XG_DECLINED, "declined: 2^31 cells or more");
+  const uint64_t bytes = (uint64_t)(nx * ny * outer) * sizeof(R);
+  auto overlap = [bytes](const void* a, const void* b) {
+    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
+    return p < q + bytes && q < p + bytes;
+  };
+  for (int i = 0; i < n; ++i) {
+    const xg_multi_desc& d = desc[i];
+    if (d.axis != ndim - 1 && d.axis != ndim - 2) return fail(XG_DECLINED, "declined: axis %d", d.axis);
+    if (!((d.pad_lo == 1 && d.pad_hi == 0) || (d.pad_lo == 0 && d.pad_hi == 1))) return fail(XG_DECLINED, "declined: pads (%d,%d)", d.pad_lo, d.pad_hi);
+    if (d.bc != XG_BC_PERIODIC && d.bc != XG_BC_FILL && d.bc != XG_BC_EXTEND) return fail(XG_DECLINED, "declined: boundary mode %d", d.bc);
+    if (!aligned(d.out)) return fail(XG_DECLINED, "declined: a result is not 16-byte aligned");
+    if (overlap(d.out, in)) return fail(XG_DECLINED, "declined: a result overlaps the input");
+    for (int k = 0; k < i; ++k)
+      if (overlap(d.out, desc[k].out)) return fail(XG_DECLINED, "declined: two results overlap");
+  }
+  for (int64_t o = 0; o < outer; ++o)
+    for (int64_t j = 0; j < ny; ++j)
+      for (int64_t x = 0; x < nx; ++x)  // the cell is read here, every result of it formed below
+        for (int i = 0; i < n; ++i) {
+          const xg_multi_desc& d = desc[i];
+          const bool along_y = d.axis == ndim - 2;
+          const int64_t len = along_y ? ny : nx, at = along_y ? j : x;
+          R side[2];
+          for (int s = 0; s < 2; ++s) {
+            int64_t q = at + s - d.pad_lo;
+            bool filled = false;
+            if (q < 0 || q >= len) {
+              filled = d.bc == XG_BC_FILL;
+              q = (d.bc == XG_BC_PERIODIC) ? (q < 0 ? len - 1 : 0) : (q < 0 ? 0 : len - 1);
+            }
+            side[s] = filled ? (R)d.fill : in[(o * ny + (along_y ? q : j)) * nx + (along_y ? x : q)];
+          }
+          ((R*)d.out)[(o * ny + j) * nx + x] = op2<R>(d.op, side[0], side[1]);
+        }
+  return XG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1673,6 +1728,11 @@ static double half_to_double(uint16_t h) {
   else if (e == 31) v = m ? NAN : INFINITY;
   else v = std::ldexp((double)(m | 0x400), e - 25);
   return (h & 0x8000) ? -v : v;
+}
+int xg_stencil_multi(int dtype, const void* in, const int64_t* shape, int ndim, int n, const xg_multi_desc* desc, void*) {
+  if (dtype == XG_T_F64) return stencil_multi<double>((const double*)in, shape, ndim, n, desc);
+  if (dtype == XG_T_F32) return stencil_multi<float>((const float*)in, shape, ndim, n, desc);
+  return fail(XG_ERR_INVALID, "stencil multi: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 int xg_vertical_diffusion(int dtype, const void* a, const void* kappa, const int64_t* ks, const void* mf, const int64_t* mfs,
                           const void* mc, const int64_t* mcs, void* out, const int64_t* shape, int ndim, int outer, int bc_z,

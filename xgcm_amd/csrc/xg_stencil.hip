@@ -1709,8 +1709,217 @@ static int stencil2d_impl(int op, const real* in, real* out, const int64_t* shap
 }
 #endif  // !XG_INT
 
+#ifndef XG_INT
+namespace {
+// ------------------------------------------------------------------------------------------
+// K2M: up to four plain two-point operators of ONE (outer, Y, X) field in one pass (xg_stencil_multi): the field is read
+// once and every requested result written once -- 8 + 8 n bytes per f64 cell instead of 16 n for n launches of K1 / K2Sy.
+// K2Sy's shape: the NW waves of a workgroup are NW consecutive rows of one x-tile, one 16-B vector per lane, workgroups in
+// 8 XCD bands; (row, x-tile) is wave-uniform, so row bases are scalar and a lane carries one 32-bit offset.
+//   Y results: every wave puts its row into LDS; the row below / above comes from the neighbouring wave, and only the lowest /
+//     highest wave of a workgroup loads it (an L2 hit: the neighbouring workgroup's own row).  At the array's first / last row
+//     the boundary row is the wrap row (loaded there only), the wave's own row (extend) or the fill -- chosen per result.
+//   X results: the cell beside a lane's vector is the neighbouring lane's (DPP, as K1); the one lane without such a lane takes
+//     a scalar load per result: the cell beside the tile, or at the row's end the wrap cell / the clamp cell / the fill.
+// op, pad side and boundary mode are run-time values, wave-uniform; MASK (bit 0: X results, bit 1: Y results) decides at
+// compile time whether the kernel has the lane shifts and the LDS row exchange at all.  Every result is formed by the same
+// op2<OP>(l, r) on the same operands as K1 / K2Sy form it, so the bits agree.
+// Barrier discipline (as K2Sy): only whole workgroups beyond the work leave early; rows beyond the array and lanes beyond
+// the row stay, with their loads and stores masked, until after the one barrier.
+// ------------------------------------------------------------------------------------------
+constexpr int MULTI_NW = 4;  // rows per workgroup
+constexpr int MULTI_MAX = 4; // results per launch
+
+struct MultiOut {
+  real* out;
+  real fill;
+  int op, pad_lo, bc, y;  // y: 1 = along the second-last dim
+};
+struct MultiArgs {
+  MultiOut d[MULTI_MAX];
+  int n;
+  int yflags;  // bit 0: some Y result needs the row below, 1: the row above, 2: some of the first wrap, 3: of the second
+};
+
+__device__ __forceinline__ dv op2_rt(int op, dv l, dv r) {
+  switch (op) {
+    case XG_OP_DIFF: return op2<XG_OP_DIFF>(l, r);
+    case XG_OP_INTERP: return op2<XG_OP_INTERP>(l, r);
+    case XG_OP_MIN: return op2<XG_OP_MIN>(l, r);
+    default: return op2<XG_OP_MAX>(l, r);
+  }
+}
+
+template <int MASK>
+__global__ __launch_bounds__(MULTI_NW * WAVE) void k_stencil_multi(const real* __restrict__ in, MultiArgs m, u32 ny, u32 nx,
+                                                                   u32 nblk, FastDiv ntile, FastDiv ngrp) {
+  constexpr int NW = MULTI_NW;
+  constexpr bool HX = (MASK & 1) != 0, HY = (MASK & 2) != 0;
+  __shared__ dv s_row[HY ? NW : 1][WAVE];
+  const u32 pb = (nblk + 7) >> 3;
+  const u32 lb = (blockIdx.x & 7) * pb + (blockIdx.x >> 3);
+  if (lb >= nblk) return;  // (whole workgroups, before the barrier)
+  const u32 wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const u32 r = fdiv(lb, ntile);
+  const u32 tile = lb - r * ntile.d;
+  const u32 o = fdiv(r, ngrp);                  // < outer: nblk is exactly outer * ngrp * ntile
+  const u32 j = (r - o * ngrp.d) * NW + wib;    // this wave's row
+  const u32 x0 = tile * (u32)(WAVE * NV);       // first cell of the tile, < nx
+  const u32 xl = (u32)lane * NV;
+  const bool rowok = j < ny;                    // (wave-uniform)
+  const bool active = rowok && x0 + xl < nx;    // nx % NV == 0: a lane's vector is inside the row or outside it
+  const u32 tend = (x0 + (u32)(WAVE * NV) < nx) ? x0 + (u32)(WAVE * NV) : nx;  // one past the tile's last cell
+  const int last_lane = (int)((tend - x0) / NV) - 1;
+  const u64 row = (u64)o * ny + (rowok ? j : 0u);  // (a row that exists, whatever j is)
+  const real* prow = in + row * nx;
+  const int yf = m.yflags;
+
+  // every load first: the wave's own vector, the rows only an edge wave needs, the scalar cells beside the tile
+  const dv zero = splat<dv>(real(0));
+  dv a = zero, lo = zero, hi = zero, wlo = zero, whi = zero;
+  if (active) a = *reinterpret_cast<const dv*>(prow + x0 + xl);
+  if (HY && active) {
+    if ((yf & 1) && wib == 0 && j > 0) lo = *reinterpret_cast<const dv*>(prow - nx + x0 + xl);
+    if ((yf & 2) && wib == NW - 1 && j + 1 < ny) hi = *reinterpret_cast<const dv*>(prow + nx + x0 + xl);
+    if ((yf & 4) && j == 0) wlo = *reinterpret_cast<const dv*>(prow + (u64)(ny - 1) * nx + x0 + xl);
+    if ((yf & 8) && j == ny - 1) whi = *reinterpret_cast<const dv*>(prow - (u64)(ny - 1) * nx + x0 + xl);
+  }
+  real nb[MULTI_MAX];
+#pragma unroll
+  for (int i = 0; i < MULTI_MAX; ++i) {
+    nb[i] = real(0);
+    if (HX && i < m.n && !m.d[i].y && rowok) {
+      const int bc = m.d[i].bc;
+      bool edge;
+      u32 idx;
+      if (m.d[i].pad_lo) { edge = (x0 == 0); idx = edge ? (bc == XG_BC_PERIODIC ? nx - 1 : 0u) : x0 - 1; }
+      else { edge = (tend == nx); idx = edge ? (bc == XG_BC_PERIODIC ? 0u : nx - 1) : tend; }
+      nb[i] = prow[idx];
+      if (edge && bc == XG_BC_FILL) nb[i] = m.d[i].fill;
+    }
+  }
+  real below = real(0), above = real(0);
+  if (HX) {  // (all 64 lanes are here: a lane beyond the row holds zeros, and no lane that counts reads it)
+    below = from_lane_below(a[NV - 1]);
+    above = from_lane_above(a[0]);
+  }
+  if (HY) {
+    s_row[wib][lane] = a;
+    __syncthreads();
+    if ((yf & 1) && wib > 0) lo = s_row[wib - 1][lane];
+    if ((yf & 2) && wib < NW - 1) hi = s_row[wib + 1][lane];  // (a row beyond the array: zeros, replaced below)
+  }
+  const u64 off = row * nx + x0 + xl;
+#pragma unroll
+  for (int i = 0; i < MULTI_MAX; ++i) {
+    if (i >= m.n) break;
+    const MultiOut& d = m.d[i];
+    dv l = a, rr = a;
+    if (!d.y) {
+      if (HX) {
+        if (d.pad_lo) {
+          const real n = (lane == 0) ? nb[i] : below;
+          l[0] = n;
+#pragma unroll
+          for (int k = 1; k < NV; ++k) l[k] = a[k - 1];
+        } else {
+          const real n = (lane == last_lane) ? nb[i] : above;
+#pragma unroll
+          for (int k = 0; k < NV - 1; ++k) rr[k] = a[k + 1];
+          rr[NV - 1] = n;
+        }
+      }
+    } else if (HY) {
+      if (d.pad_lo) l = (j == 0) ? (d.bc == XG_BC_PERIODIC ? wlo : (d.bc == XG_BC_EXTEND ? a : splat<dv>(d.fill))) : lo;
+      else rr = (j == ny - 1) ? (d.bc == XG_BC_PERIODIC ? whi : (d.bc == XG_BC_EXTEND ? a : splat<dv>(d.fill))) : hi;
+    }
+    const dv res = op2_rt(d.op, l, rr);
+    if (active) stg_drop<dv>(d.out + off, res);  // `sc1 nt`, as the plain stencils store
+  }
+}
+
+inline bool multi_overlap(const void* a, const void* b, u64 bytes) {
+  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
+  return p < q + bytes && q < p + bytes;
+}
+
+int stencil_multi_impl(const real* in, const int64_t* shape, int ndim, int n, const xg_multi_desc* desc, void* stream) {
+  if (!in || !shape || !desc) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (n < 1 || n > MULTI_MAX) return fail(XG_ERR_INVALID, "%d results asked of one pass (1 to %d)", n, MULTI_MAX);
+  for (int i = 0; i < n; ++i) {
+    if (!desc[i].out) return fail(XG_ERR_INVALID, "NULL array argument");
+    if (desc[i].op < XG_OP_DIFF || desc[i].op > XG_OP_MAX) return fail(XG_ERR_INVALID, "unknown op %d", desc[i].op);
+  }
+  if (ndim != 2 && ndim != 3) return fail(XG_DECLINED, "declined: %d dims", ndim);
+  const int64_t nx = shape[ndim - 1], ny = shape[ndim - 2], outer = (ndim == 3) ? shape[0] : 1;
+  if (nx < 1 || ny < 1 || outer < 1) return fail(XG_DECLINED, "declined: an empty array");
+  if (nx % NV || !aligned16(in)) return fail(XG_DECLINED, "declined: rows are not whole 16-byte lane vectors");
+  if (nx > 0x7fffffffll || ny > 0x7fffffffll || outer > 0x7fffffffll || (u64)nx * (u64)ny > 0x7fffffffull ||
+      (u64)nx * (u64)ny * (u64)outer > 0x7fffffffull)
+    return fail(XG_DECLINED, "declined: 2^31 cells or more");
+  const u64 bytes = (u64)nx * (u64)ny * (u64)outer * sizeof(real);
+  MultiArgs m;
+  memset(&m, 0, sizeof(m));
+  m.n = n;
+  int mask = 0;
+  for (int i = 0; i < n; ++i) {
+    const xg_multi_desc& d = desc[i];
+    if (d.axis != ndim - 1 && d.axis != ndim - 2) return fail(XG_DECLINED, "declined: axis %d", d.axis);
+    if (!((d.pad_lo == 1 && d.pad_hi == 0) || (d.pad_lo == 0 && d.pad_hi == 1))) return fail(XG_DECLINED, "declined: pads (%d,%d)", d.pad_lo, d.pad_hi);
+    if (d.bc != XG_BC_PERIODIC && d.bc != XG_BC_FILL && d.bc != XG_BC_EXTEND) return fail(XG_DECLINED, "declined: boundary mode %d", d.bc);
+    if (!aligned16(d.out)) return fail(XG_DECLINED, "declined: a result is not 16-byte aligned");
+    if (multi_overlap(d.out, in, bytes)) return fail(XG_DECLINED, "declined: a result overlaps the input");
+    for (int k = 0; k < i; ++k)
+      if (multi_overlap(d.out, desc[k].out, bytes)) return fail(XG_DECLINED, "declined: two results overlap");
+    MultiOut& q = m.d[i];
+    q.out = (real*)d.out;
+    q.fill = (real)d.fill;
+    q.op = d.op;
+    q.pad_lo = d.pad_lo;
+    q.bc = d.bc;
+    q.y = (d.axis == ndim - 2) ? 1 : 0;
+    mask |= q.y ? 2 : 1;
+    if (q.y) m.yflags |= (d.pad_lo ? 1 : 2) | (d.bc == XG_BC_PERIODIC ? (d.pad_lo ? 4 : 8) : 0);
+  }
+  const u64 ntile = ((u64)nx + (u64)WAVE * NV - 1) / ((u64)WAVE * NV), ngrp = ((u64)ny + MULTI_NW - 1) / MULTI_NW;
+  const u64 nblk64 = (u64)outer * ngrp * ntile;
+  if (nblk64 > MAX_ITEMS) return fail(XG_DECLINED, "declined: 2^31 cells or more");
+  const u32 nblk = (u32)nblk64, grid = ((nblk + 7) / 8) * 8;
+  const FastDiv fnt = make_fastdiv(ntile), fng = make_fastdiv(ngrp);
+  hipStream_t st = (hipStream_t)stream;
+  switch (mask) {
+    case 1: hipLaunchKernelGGL((k_stencil_multi<1>), dim3(grid), dim3(MULTI_NW * WAVE), 0, st, in, m, (u32)ny, (u32)nx, nblk, fnt, fng); break;
+    case 2: hipLaunchKernelGGL((k_stencil_multi<2>), dim3(grid), dim3(MULTI_NW * WAVE), 0, st, in, m, (u32)ny, (u32)nx, nblk, fnt, fng); break;
+    default: hipLaunchKernelGGL((k_stencil_multi<3>), dim3(grid), dim3(MULTI_NW * WAVE), 0, st, in, m, (u32)ny, (u32)nx, nblk, fnt, fng);
+  }
+  XG_LAUNCH_CHECK();
+  return XG_OK;
+}
+}  // namespace
+#endif  // !XG_INT
+
 
 extern "C" {
+
+#ifndef XG_INT
+// one exported entry for both element types (xg_stencil_multi, below); each float build defines its own implementation, hidden
+__attribute__((visibility("hidden"))) int xg_internal_stencil_multi_f64(const double* in, const int64_t* shape, int ndim, int n,
+                                                                        const xg_multi_desc* desc, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_stencil_multi_f32(const float* in, const int64_t* shape, int ndim, int n,
+                                                                        const xg_multi_desc* desc, void* stream);
+int XG_FN(xg_internal_stencil_multi)(const real* in, const int64_t* shape, int ndim, int n, const xg_multi_desc* desc,
+                                     void* stream) {
+  return stencil_multi_impl(in, shape, ndim, n, desc, stream);
+}
+#ifdef XG_PRIMARY
+int xg_stencil_multi(int dtype, const void* in, const int64_t* shape, int ndim, int n, const xg_multi_desc* desc, void* stream) {
+  if (dtype == XG_T_F64) return xg_internal_stencil_multi_f64((const double*)in, shape, ndim, n, desc, stream);
+  if (dtype == XG_T_F32) return xg_internal_stencil_multi_f32((const float*)in, shape, ndim, n, desc, stream);
+  return fail(XG_ERR_INVALID, "stencil multi: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+#endif  // !XG_INT
 
 static int stencil1d_impl(int op, const real* in, const real* halo, real* out, const int64_t* shape, int ndim,
                           int axis, int64_t n_out, int pad_lo, int pad_hi, int bc, real fill, const real* m_in,

@@ -18,6 +18,11 @@ for `da * metric` (reference xgcm/grid.py:806-808,830-832).
 
 from __future__ import annotations
 
+import contextlib
+import os
+import threading
+import weakref
+from collections import OrderedDict
 from typing import Optional, Sequence
 
 import numpy as np
@@ -33,6 +38,8 @@ __all__ = [
     "is_device_array",
     "stencil1d",
     "stencil1d_halo",
+    "drop_sibling_plans",
+    "SIBLING_STATS",
     "cumsum1d",
     "reduce1d",
     "pad_nd",
@@ -259,6 +266,7 @@ def copy_into(dst: torch.Tensor, src) -> torch.Tensor:
     src = _raw_device(src)
     if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
         raise ValueError(f"copy_into: source {tuple(src.shape)} {src.dtype} does not match destination {tuple(dst.shape)} {dst.dtype}")
+    _sibling_written(dst)
     _copy_nd(src.data_ptr(), src.stride(), dst, dst.shape)
     return dst
 
@@ -568,6 +576,238 @@ def _int_stencil1d(plan, op: str, x, halo, axis: int, pad_lo: int, pad_hi: int, 
     return _divide(res, m_out, plan.divide_as)
 
 
+# ---- learned sibling plans: the plain two-point operators a caller asks of one field, round after round, in ONE pass ------
+# Model code asks the same operators of the same kind of field every step: interp and diff along X, then along Y -- four
+# passes that each read the whole field.  An eager call cannot know what comes next, but it can remember: per thread and
+# per KIND of input (device, stream, dtype, shape, strides -- not the tensor: every step brings a new one) the requests
+# are logged in rounds, a round ending when its first request comes again.  Two equal rounds of 2 to 4 different requests
+# make a plan; from then on the round's first request runs xg_stencil_multi for the whole set (one read of the field), and the
+# other results wait -- held against THAT tensor's identity and version -- until they are asked for.  Only the pattern is
+# remembered, never a value: every round is computed from the tensor it is asked of.  The first deviation (another tensor in
+# mid round, a changed `_version`, a request outside the set) drops what is held and retires the plan; the call then runs
+# as it always did, and learning starts over.  XG_SIBLING_PLAN=0 switches all of it off.
+SIBLING_MAX_KEYS = 8  # kinds of input remembered per thread, least recently used evicted
+SIBLING_MAX_SET = 4   # results of one pass (xg_stencil_multi)
+
+
+class _Counters:
+    """one-pass launches, results served from a held set, held results dropped unused, plans retired -- of ONE thread"""
+
+    __slots__ = ("launches", "served", "dropped", "retired")
+
+    def __init__(self):
+        self.launches = self.served = self.dropped = self.retired = 0
+
+
+_SIB = threading.local()  # .table: OrderedDict field key -> _Siblings; .off: depth of sibling_plans_off(); .stats: _Counters
+
+
+def _stats() -> _Counters:
+    c = getattr(_SIB, "stats", None)
+    if c is None:
+        c = _SIB.stats = _Counters()
+    return c
+
+
+class _SiblingStats:
+    """`device.SIBLING_STATS`: the calling thread's counters (each thread has its own table and its own counts)"""
+
+    def reset(self) -> None:
+        _SIB.stats = _Counters()
+
+    def __getitem__(self, name: str) -> int:
+        return self.as_dict()[name]
+
+    def as_dict(self) -> dict:
+        c = _stats()
+        return {"launches": c.launches, "served": c.served, "dropped": c.dropped, "retired": c.retired}
+
+
+SIBLING_STATS = _SiblingStats()
+
+
+class _Siblings:
+    """what one thread has learnt about, and holds for, one kind of input"""
+
+    __slots__ = ("log", "first", "last", "plan", "held", "ref", "ident", "declined", "stats")
+
+    def __init__(self):
+        self.stats = _stats()  # the OWNER's counters: the weak-reference callback may run on whichever thread frees the input
+        self.log, self.last, self.plan = [], None, None  # this round so far, the last complete round, the live plan
+        self.first = None                                   # weak reference to the tensor this round is asked of
+        self.held, self.ref, self.ident = None, None, None  # request -> result, weak reference and identity of their input
+        self.declined = False                               # the native entry refused this kind once: not asked again
+
+    def held_bytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.held or {}).values())
+
+    def drop(self) -> None:
+        if self.held:
+            self.stats.dropped += len(self.held)
+        self.held = self.ref = self.ident = None
+
+    def forget(self) -> None:
+        """drop what is held, retire a live plan, learn from scratch"""
+        self.drop()
+        if self.plan is not None:
+            self.stats.retired += 1
+        self.log, self.first, self.last, self.plan = [], None, None, None
+
+
+def _sib_table() -> OrderedDict:
+    table = getattr(_SIB, "table", None)
+    if table is None:
+        table = _SIB.table = OrderedDict()
+    return table
+
+
+def drop_sibling_plans() -> None:
+    """forget every plan of the calling thread and release the results it holds"""
+    table = _sib_table()
+    for st in table.values():
+        st.forget()
+    table.clear()
+
+
+@contextlib.contextmanager
+def sibling_plans_off():
+    """inside, the calling thread neither learns nor serves: for callers with exact knowledge of what is needed (the deferred
+    results of `grid.fused()` have their own sibling rules)"""
+    _SIB.off = getattr(_SIB, "off", 0) + 1
+    try:
+        yield
+    finally:
+        _SIB.off -= 1
+
+
+def _free_bytes() -> int:
+    """free memory where the results live (HBM: torch.cuda.mem_get_info)"""
+    if _MEM.device == "cuda":
+        return int(torch.cuda.mem_get_info()[0])
+    return int(os.sysconf("SC_AVPHYS_PAGES")) * int(os.sysconf("SC_PAGE_SIZE"))
+
+
+def _sibling_identity(x: torch.Tensor):
+    return (x.data_ptr(), x.untyped_storage().data_ptr(), x._version, _stream())
+
+
+def _sibling_enabled() -> bool:
+    if os.environ.get("XG_SIBLING_PLAN", "1") == "0" or getattr(_SIB, "off", 0) > 0:
+        return False
+    from . import lazy as _lazy
+
+    if getattr(_lazy._ACTIVE, "depth", 0) > 0:  # inside `with grid.fused():`
+        return False
+    # a capture must record every kernel it is given: nothing learnt before it is served or held across its start
+    return not (_MEM.device == "cuda" and torch.cuda.is_current_stream_capturing())
+
+
+def _multi_launch(x: torch.Tensor, requests):
+    """xg_stencil_multi: one result per (op, axis, pad_lo, pad_hi, bc, fill) of the resident float tensor `x`, all from one
+    read of it; None when the native entry declines (nothing was launched)"""
+    n = len(requests)
+    outs = [_empty(x.shape, x.dtype, x.device) for _ in range(n)]
+    desc = (_hip.MultiDesc * n)()
+    for d, (op, axis, pad_lo, pad_hi, bc, fill), out in zip(desc, requests, outs):
+        d.op, d.axis, d.pad_lo, d.pad_hi, d.bc, d.fill, d.out = (_hip.OP[op], axis % x.dim(), pad_lo, pad_hi, _hip.BC[bc], float(fill),
+                                                                  out.data_ptr())
+    status = _MEM.lib().xg_stencil_multi(_hip.DTYPE[_dt.np_dtype(x).name], x.data_ptr(), _hip.i64(list(x.shape)), x.dim(), n,
+                                         desc, _stream())
+    if status == _hip.DECLINED:
+        return None
+    _check(status)
+    return outs
+
+
+SIBLING_MAX_CELLS = 2 ** 31 - 1  # xg_stencil_multi declines 2^31 cells or more
+
+
+def _sibling_form(x, axis: int, pad_lo: int, pad_hi: int, bc) -> bool:
+    """is this a plain operator in a form xg_stencil_multi takes (include/xgcm_hip.h)?  Only such calls are requests."""
+    return (2 <= x.dim() <= 3 and axis >= x.dim() - 2 and (pad_lo, pad_hi) in ((1, 0), (0, 1)) and bc in ("periodic", "fill", "extend")
+            and x.is_contiguous() and 0 < x.numel() <= SIBLING_MAX_CELLS and (x.shape[-1] * x.element_size()) % 16 == 0
+            and x.data_ptr() % 16 == 0)
+
+
+def _sibling_written(t) -> None:
+    """the library itself is about to write into `t` through its address, which `_version` does not see: results held for a
+    tensor of that storage are dropped"""
+    if isinstance(t, torch.Tensor) and getattr(_SIB, "table", None):
+        base = t.untyped_storage().data_ptr()
+        for st in _SIB.table.values():
+            if st.held is not None and st.ident[1] == base:
+                st.forget()
+
+
+def _sibling_launch(st: _Siblings, x: torch.Tensor, req) -> Optional[torch.Tensor]:
+    """the whole set of the live plan from one read of `x`; None: not this time (memory, or the native entry declines)"""
+    n = len(st.plan)
+    each = x.numel() * x.element_size()
+    held_elsewhere = sum(s.held_bytes() for s in _sib_table().values() if s is not st)
+    if held_elsewhere + (n - 1) * each >= _free_bytes() // 4:
+        return None
+    outs = _multi_launch(x, [r[:5] + (float(np.uint64(r[5]).view(np.float64)),) for r in st.plan])  # (requests carry the fill's bits)
+    if outs is None:
+        st.declined = True
+        return None
+    st.stats.launches += 1
+    results = dict(zip(st.plan, outs))
+    first = results.pop(req)
+    st.held, st.ident = results, _sibling_identity(x)
+    st.ref = weakref.ref(x, lambda _r, st=st: st.drop())  # the input dies: so do the results nobody asked for
+    return first
+
+
+def _sibling_stencil(op: str, x: torch.Tensor, axis: int, pad_lo: int, pad_hi: int, bc: str, fill: float) -> Optional[torch.Tensor]:
+    """one eligible `stencil1d` request passes here: its result when a learnt plan serves it, else None (and the caller
+    runs the single-operator kernel as ever) -- either way the request is part of what is learnt"""
+    if not _sibling_enabled():
+        if getattr(_SIB, "table", None):
+            drop_sibling_plans()
+        return None
+    # (the fill keeps its bits -- -0.0 is not 0.0, NaN is itself -- so requests compare by them)
+    req = (op, axis, pad_lo, pad_hi, bc, np.float64(fill).view(np.uint64).item() if bc == "fill" else 0)
+    key = (str(x.device), _stream(), x.dtype, tuple(x.shape), tuple(x.stride()))
+    table = _sib_table()
+    st = table.get(key)
+    if st is None:
+        st = table[key] = _Siblings()
+        while len(table) > SIBLING_MAX_KEYS:
+            table.popitem(last=False)[1].forget()
+    table.move_to_end(key)
+    if st.held is not None:
+        if st.ref() is x and st.ident == _sibling_identity(x) and req in st.held:
+            out = st.held.pop(req)
+            st.stats.served += 1
+            if not st.held:
+                st.held = st.ref = st.ident = None
+            st.log.append(req)
+            return out
+        st.forget()  # another tensor in mid round, new values in this one, a request outside the set
+    if st.plan is not None and req not in st.plan:
+        st.forget()  # (the same with nothing held any more)
+    if st.log and req != st.log[0] and (st.first is None or st.first() is not x):
+        st.forget()  # a round is what is asked of ONE tensor: two fields of one kind taking turns (diff(v, X) - diff(u, Y)) make no plan
+    if st.log and req == st.log[0]:  # the round is complete
+        done = frozenset(st.log)
+        valid = 2 <= len(st.log) <= SIBLING_MAX_SET and len(done) == len(st.log)
+        if valid and done == st.last:
+            if st.plan is None or frozenset(st.plan) != done:
+                st.plan = tuple(st.log)
+        elif st.plan is not None:
+            st.plan = None
+            st.stats.retired += 1
+        st.last, st.log = (done if valid else None), []
+    elif len(st.log) >= SIBLING_MAX_SET:  # a fifth request before the first came again: no round of this kind makes a plan
+        st.forget()
+    st.log.append(req)
+    if len(st.log) == 1:
+        st.first = weakref.ref(x)
+    if st.plan is not None and len(st.log) == 1 and req == st.plan[0] and not st.declined:
+        return _sibling_launch(st, x, req)
+    return None
+
+
 def stencil1d(op: str, x, axis: int, pad_lo: int, pad_hi: int, bc: Optional[str], fill: float = 0.0,
               m_in=None, m_out=None) -> torch.Tensor:
     """Fused pad + diff/interp/min/max along `axis` (xg_stencil1d_f64)."""
@@ -589,8 +829,14 @@ def stencil1d(op: str, x, axis: int, pad_lo: int, pad_hi: int, bc: Optional[str]
         return binary("div", stencil1d(op, x, axis, pad_lo, pad_hi, bc, fill, m_in, None), m_out)
     half = _half(x, m_in, m_out)
     dt, sfx = _common(x, m_in, m_out)
+    given = x
     x = asdevice(x, dt)
     axis = axis % x.dim()
+    if x is given and m_in is None and m_out is None and not half and _sibling_form(x, axis, pad_lo, pad_hi, bc):
+        # a plain operator on a resident field, in a form xg_stencil_multi takes: the learned sibling plan may have it ready
+        served = _sibling_stencil(op, x, axis, int(pad_lo), int(pad_hi), bc, float(fill))
+        if served is not None:
+            return served
     shape = list(x.shape)
     n_out = shape[axis] + pad_lo + pad_hi - 1
     oshape = list(shape)
@@ -903,6 +1149,7 @@ def put_halo(out: torch.Tensor, halo, axis: int, pad_lo: int, pad_hi: int) -> to
     """Write the pre-gathered halo slab `halo` (shaped like `out` with `axis` shortened to pad_lo + pad_hi, low halo first)
     into the halo cells of `out` IN PLACE (xg_halo_put): `Grid.cumsum` on a connected axis scans straight into the padded
     layout and fills the halo cells of the cumulative field afterwards -- no padded copy."""
+    _sibling_written(out)
     lib = _MEM.lib()
     if not (isinstance(out, torch.Tensor) and _MEM.holds(out) and out.is_contiguous()):
         raise ValueError("put_halo writes in place: `out` must be a contiguous HBM tensor")
@@ -1706,6 +1953,7 @@ def synthetic(shape, seed: int, offset: int = 0, scale: float = 1.0, shift: floa
         out = (_empty if os.environ.get("XG_SCATTER_INPUTS") == "1" else torch.empty)(tuple(shape), dtype=dtype, device=_MEM.device)
     if out.numel() == 0:
         return out
+    _sibling_written(out)
     sfx = "f32" if out.dtype == torch.float32 else "f64"
     _check(getattr(lib, "xg_fill_synthetic_" + sfx)(out.data_ptr(), out.numel(), int(seed), int(offset), float(scale),
                                          float(shift), _stream()))

@@ -191,6 +191,9 @@ class HipGridUFunc(GridUFunc):
         if self.funcname == "cumsum":
             _, _, _, drop_last = _CUMSUM_TABLE[(self.from_pos, self.to_pos)]
             data = _cumsum(da.data, num, 0, 1 if drop_last else 0, lo, hi, bc, fv, False, False, m_in, m_out)
+        elif getattr(grid, "_fusing", False):  # `fuse=True` / `grid.fused()`: exact knowledge, no learned sibling plan
+            with _dev.sibling_plans_off():
+                data = _stencil(da.data, self.funcname, num, lo, hi, bc, fv, m_in, m_out)
         else:
             data = _stencil(da.data, self.funcname, num, lo, hi, bc, fv, m_in, m_out)
         res = DataArray(data, out_dims, name=da.name)

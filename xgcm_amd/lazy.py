@@ -328,8 +328,9 @@ class StencilNode(Node):
             assert m_out is None
             m_out = extra_m_out
             _count("stencil_m_out")
-        res = self.ufunc(self.grid, plain(arg), axis=[(self.ax_name,)], other_component=plain(self.other_component),
-                         metric_in=m_in, metric_out=m_out, **self.remaining)
+        with _dev.sibling_plans_off():  # a deferred result knows what is needed of it: nothing is learnt from, or guessed for, it
+            res = self.ufunc(self.grid, plain(arg), axis=[(self.ax_name,)], other_component=plain(self.other_component),
+                             metric_in=m_in, metric_out=m_out, **self.remaining)
         return res.data
 
     def _product_as_metric(self):
