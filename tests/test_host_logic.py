@@ -220,6 +220,50 @@ def test_c_abi_library_exports_every_declared_symbol():
     assert lib.xg_version() == 1
 
 
+def header_prototypes():
+    """name -> (return type, [(type, parameter name), ...]) of every prototype of include/xgcm_hip.h, `const` and blanks dropped"""
+    text = open(os.path.join(ROOT, "include", "xgcm_hip.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    protos = {}
+    for ret, name, params in re.findall(r"^\s*((?:int|void)\s*\*?)\s*(xg_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        pairs = []
+        for p in [p.strip() for p in params.split(",") if p.strip() not in ("", "void")]:
+            ctype, pname = re.fullmatch(r"(.*?)(\w+)", p, flags=re.S).groups()
+            pairs.append((re.sub(r"\bconst\b|\bstruct\b|\s+", "", ctype), pname))
+        protos[name] = (ret.replace(" ", ""), pairs)
+    return protos
+
+
+def test_c_abi_signatures_match_the_header_parameter_by_parameter():
+    """Every entry of _hip.SIGNATURES against its prototype in include/xgcm_hip.h: the count, each scalar's exact ctypes type,
+    a pointer type for every `*` parameter (a typed POINTER's pointee as the header has it), and the return type."""
+    import ctypes as C
+
+    scalars = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "ssize_t": C.c_ssize_t,
+               "double": C.c_double, "float": C.c_float}
+    pointees = dict(scalars, **{"void*": C.c_void_p, "xg_multi_desc": _hip.MultiDesc})
+    protos = header_prototypes()
+    assert len(protos) == len(_hip.SIGNATURES) == 117
+    wrong = []
+    for name, (ret, params) in protos.items():
+        res, args = _hip.SIGNATURES[name]
+        if res is not {"int": C.c_int, "void*": C.c_void_p, "void": None}[ret]:
+            wrong.append(f"{name}: returns {ret}, bound as {res}")
+        if len(args) != len(params):
+            wrong.append(f"{name}: {len(params)} parameters, {len(args)} argtypes")
+            continue
+        for i, ((ctype, pname), a) in enumerate(zip(params, args)):
+            if not ctype.endswith("*"):
+                ok = a is scalars[ctype]
+            elif isinstance(a, type) and issubclass(a, C._Pointer):
+                ok = a._type_ is pointees[ctype[:-1]]
+            else:
+                ok = a in (C.c_void_p, C.c_char_p) and (a is C.c_char_p) == (ctype == "char*")
+            if not ok:
+                wrong.append(f"{name}: parameter {i} `{ctype} {pname}` bound as {a}")
+    assert not wrong, "\n".join(wrong)
+
+
 def test_c_abi_header_compiles_as_c_and_links():
     """The header is plain C and the demo links against the library without a GPU present."""
     import subprocess

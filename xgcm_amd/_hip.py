@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # XG_HIP_LIB points at another build of the same ABI (A/B measurements of kernel variants on one GPU)
@@ -91,81 +91,6 @@ SIGNATURES = {
         C.c_int, [_vp, _vp, _i64p, _vp, C.c_int64, _vp, _i64p, C.c_int, C.c_int, _vp],
     ),
     "xg_binary_f64": (C.c_int, [C.c_int, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_int, _vp]),
-    "xg_vorticity_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp],
-    ),
-    "xg_divergence_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp],
-    ),
-    "xg_vorticity_halo_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _vp, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp],
-    ),
-    "xg_divergence_halo_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _vp, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp],
-    ),
-    "xg_gradient_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp, _i64p, _vp, _i64p, _vp],
-    ),
-    "xg_flux_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp],
-    ),
-    "xg_gradient_halo_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp, _i64p, _vp, _i64p, _vp],
-    ),
-    "xg_flux_halo_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp],
-    ),
-    "xg_flux_divergence_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp],
-    ),
-    "xg_flux_divergence3d_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
-         C.c_int, C.c_double, _vp],
-    ),
-    "xg_vertical_velocity_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int, C.c_double,
-         C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _vp],
-    ),
-    "xg_hydrostatic_pressure_gradient_f64": (
-        C.c_int,
-        [_vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
-         C.c_int, C.c_double, _vp],
-    ),
-    "xg_vertical_momentum_advection_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
-         C.c_int, C.c_double, _vp],
-    ),
-    "xg_kinetic_energy_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _vp],
-    ),
-    "xg_momentum_advection_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double,
-         C.c_int, C.c_double, _vp],
-    ),
-    "xg_horizontal_viscosity_f64": (
-        C.c_int,
-        [_vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp,
-         _i64p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, _vp],
-    ),
-    "xg_laplacian_f64": (
-        C.c_int,
-        [_vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int, C.c_double,
-         C.c_int, C.c_double, _vp],
-    ),
     "xg_stencil2d_f64": (
         C.c_int,
         [C.c_int, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
@@ -181,8 +106,7 @@ SIGNATURES = {
 
 # float32 twins of the compute entry points: same argument order, `float` fill values
 # (xg_fill_synthetic_f32 keeps double scale/shift: the value is formed in f64 and rounded once)
-for _name in ["xg_stencil1d", "xg_stencil1d_halo", "xg_stencil1d_halo_w", "xg_cumsum1d", "xg_reduce1d", "xg_pad", "xg_gather", "xg_halo_put", "xg_transform_linear", "xg_transform_conservative", "xg_binary", "xg_vorticity", "xg_divergence", "xg_vorticity_halo", "xg_divergence_halo", "xg_gradient", "xg_flux", "xg_gradient_halo", "xg_flux_halo", "xg_flux_divergence", "xg_flux_divergence3d", "xg_vertical_velocity", "xg_hydrostatic_pressure_gradient", "xg_vertical_momentum_advection", "xg_kinetic_energy", "xg_momentum_advection", "xg_horizontal_viscosity", "xg_laplacian", "xg_stencil2d", "xg_stencil2d_metric",
-              "xg_fill_synthetic"]:
+for _name in ["xg_stencil1d", "xg_stencil1d_halo", "xg_stencil1d_halo_w", "xg_cumsum1d", "xg_reduce1d", "xg_pad", "xg_gather", "xg_halo_put", "xg_transform_linear", "xg_transform_conservative", "xg_binary", "xg_stencil2d", "xg_stencil2d_metric", "xg_fill_synthetic"]:
     _res, _args = SIGNATURES[_name + "_f64"]
     SIGNATURES[_name + "_f32"] = (_res, list(_args) if _name == "xg_fill_synthetic" else
                                   [C.c_float if a is C.c_double else (C.POINTER(C.c_float) if a is _f64p else a) for a in _args])
@@ -204,28 +128,122 @@ DTYPE = {"bool": 0, "int8": 1, "int16": 2, "int32": 3, "int64": 4, "uint8": 5, "
          "float32": 9, "float64": 10, "float16": 11}
 SIGNATURES["xg_copy_nd"] = (C.c_int, [_vp, _i64p, _vp, _i64p, _i64p, C.c_int, C.c_int, _vp])
 SIGNATURES["xg_convert"] = (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int, _vp])
-# one entry for float64 and float32 (the element type, a DTYPE code, comes first): no _f64 / _f32 twins
-SIGNATURES["xg_vertical_diffusion"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_int, C.c_int,
-                                               C.c_int, C.c_double, _vp])
-SIGNATURES["xg_implicit_vertical_diffusion"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _i64p,
-                                                        C.c_int, C.c_int, C.c_double, _vp])
-SIGNATURES["xg_implicit_vertical_viscosity"] = (C.c_int, [C.c_int, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p,
-                                                        _vp, _vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
-                                                        C.c_double, C.c_double, _vp])
-SIGNATURES["xg_richardson_number"] = (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_int,
-                                              C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, _vp])
-SIGNATURES["xg_richardson_mixing"] = (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p] + [C.c_double] * 5
-                                      + [_vp, _vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int,
-                                         C.c_double, _vp])
-SIGNATURES["xg_isopycnal_slope"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _i64p, C.c_int, C.c_int,
-                                            C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, _vp])
-SIGNATURES["xg_redi_tensor"] = (C.c_int, [C.c_int, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, C.c_double, C.c_double, C.c_int, _vp, _vp,
-                                        _vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double,
-                                        _vp])
-SIGNATURES["xg_redi_vertical_flux_divergence"] = (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p,
-                                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
-                                                          C.c_int, C.c_double, _vp])
+# ---- the fused entry points: ONE description each, read here (SIGNATURES) and by the marshaller (device._fused) -------------
+class Slot(NamedTuple):
+    """one named argument slot of a fused entry point; its name is the parameter's in include/xgcm_hip.h"""
 
+    kind: str            # field | halo | metric | work | result | shape | flag | real | bc | stream
+    name: str
+    at: str = "shape"    # field / metric / result: it has (broadcasts against) the fields' "shape" or the "faces" of Z
+    what: str = ""       # metric (a pointer plus broadcast strides): what a stride error calls it
+    null: bool = False   # field: the header takes NULL
+    dim: int = 0         # halo (a field that only the `_halo` form has, NULL off a halo axis): the dim of the last two it keeps
+    fills: tuple = ()    # bc (a code plus its fills): the names of the fills
+
+
+class Row(NamedTuple):
+    op: str              # the wrapper's name, as the error messages spell it
+    slots: tuple         # in the ABI's own order
+    typed: bool = False  # one entry with a leading `dtype` code; else an `_f64` / `_f32` pair (the reals are `float` in `_f32`)
+    same: tuple = ()     # the fields that share a shape, as the error lists them (default: the fields at "shape", in slot order)
+
+
+def _fields(*names, **kw):
+    return tuple(Slot("field", n, **kw) for n in names)
+
+
+def _metrics(*names, at="shape"):
+    """names, or (name, what a stride error calls it)"""
+    return tuple(Slot("metric", n, at, n) if isinstance(n, str) else Slot("metric", n[0], at, n[1]) for n in names)
+
+
+def _results(*names, at="shape"):
+    return tuple(Slot("result", n, at) for n in names)
+
+
+def _of(kind, *names):
+    return tuple(Slot(kind, n) for n in names)
+
+
+def _bc(*axes):
+    return tuple(Slot("bc", "bc_" + a, fills=("fill_" + a,)) for a in axes)
+
+
+_HALOS = (Slot("halo", "halo_x", dim=-2), Slot("halo", "halo_y", dim=-1))
+_SHAPE = _of("shape", "shape")  # `shape` plus `ndim`
+_STREAM = _of("stream", "stream")
+_XY = _SHAPE + _bc("x", "y")
+_XYZ = _SHAPE + _bc("x", "y", "z")
+_OUTER_XYZ = _SHAPE + _of("flag", "outer") + _bc("x", "y", "z")
+_KAPPA = _fields("a") + _metrics("kappa", ("mf", "metric of the flux"), at="faces") + _metrics(("mc", "metric of the result"))
+_SHEAR = _metrics(("mu", "metric at u's points"), ("mv", "metric at v's points"), ("mb", "metric at the centre"), at="faces")
+_SLOPE = _fields("b") + _metrics(("mx", "X metric"), ("my", "Y metric")) + _metrics(("mz", "Z metric at the faces"), at="faces")
+
+FUSED = {
+    "xg_gradient": Row("gradient", _fields("a") + _HALOS + _results("out_x", "out_y") + _XY + _metrics("mx", "my") + _STREAM),
+    "xg_flux": Row("flux", _fields("u", "v", "t") + _HALOS + _results("out_x", "out_y") + _XY + _STREAM),
+    "xg_flux_divergence": Row("flux_divergence", _fields("u", "v", "t") + _metrics("area") + _results("out") + _XY + _STREAM),
+    "xg_flux_divergence3d": Row("flux_divergence_3d", _fields("u", "v", "w", "t") + _metrics(("vol", "volume"), ("vol2", "volume"))
+                                + _results("out") + _XYZ + _STREAM),
+    "xg_vertical_velocity": Row("vertical_velocity", _fields("u", "v")
+                                + _metrics(*((m, "face weight") for m in ("mu", "mu2", "mv", "mv2")), "area") + _results("out")
+                                + _XYZ + _of("flag", "reverse") + _STREAM),
+    "xg_hydrostatic_pressure_gradient": Row("hydrostatic_pressure_gradient", _fields("b") + _metrics(("w", "Z weight"), "dxC", "dyC")
+                                            + _results("out_x", "out_y") + _XYZ + _STREAM),
+    "xg_vertical_momentum_advection": Row("vertical_momentum_advection", _fields("u", "v", "w")
+                                          + _metrics(("mu", "metric of gu"), ("mv", "metric of gv")) + _results("out_u", "out_v") + _XYZ + _STREAM),
+    "xg_kinetic_energy": Row("kinetic_energy", _fields("u", "v") + _results("out") + _XY + _STREAM),
+    "xg_momentum_advection": Row("momentum_advection", _fields("u", "v") + _metrics("coriolis", "rAz", "dxC", "dyC")
+                                 + _results("out_u", "out_v") + _XY + _STREAM),
+    "xg_horizontal_viscosity": Row("horizontal_viscosity", _fields("u", "v")
+                                   + _metrics("rA", "rAz", "dxC", "dyC", "dyG", "dxG", "nu_d", "nu_z") + _results("out_u", "out_v") + _SHAPE
+                                   + tuple(Slot("bc", "bc_" + a, fills=("fill_" + a, "zfill_" + a)) for a in "xy") + _STREAM),
+    "xg_laplacian": Row("laplacian", _fields("a") + _metrics("dxC", "dyC", "dyG", "dxG", "area") + _results("out") + _XY + _STREAM),
+    "xg_vertical_diffusion": Row("vertical_diffusion", _KAPPA + _results("out") + _SHAPE + _of("flag", "outer") + _bc("z") + _STREAM, True),
+    "xg_implicit_vertical_diffusion": Row("implicit_vertical_diffusion", _KAPPA + _of("work", "work") + _results("out") + _SHAPE
+                                          + _of("flag", "outer") + _of("real", "dt") + _STREAM, True),
+    "xg_implicit_vertical_viscosity": Row("implicit_vertical_viscosity", _fields("u", "v")
+                                          + _metrics("nu", ("mfu", "metric of u's flux"), at="faces") + _metrics(("mcu", "metric of u's result"))
+                                          + _metrics(("mfv", "metric of v's flux"), at="faces") + _metrics(("mcv", "metric of v's result"))
+                                          + _of("work", "work_u", "work_v") + _results("out_u", "out_v") + _SHAPE + _of("flag", "outer")
+                                          + _bc("x", "y") + _of("real", "dt") + _STREAM, True),
+    "xg_richardson_number": Row("richardson_number", _fields("b", null=True) + _fields("u", "v") + _SHEAR + _results("out", at="faces")
+                                + _OUTER_XYZ + _STREAM, True, ("u", "v", "b")),
+    "xg_richardson_mixing": Row("richardson_mixing", _fields("b", "u", "v") + _SHEAR
+                                + _of("real", "nu0", "alpha", "nu_b", "kappa_b", "shear_floor")
+                                + _results("out_nu", "out_kappa", at="faces") + _OUTER_XYZ + _STREAM, True, ("u", "v", "b")),
+    "xg_isopycnal_slope": Row("isopycnal_slope", _SLOPE + _results("out_x", "out_y", at="faces") + _OUTER_XYZ + _STREAM, True),
+    "xg_redi_tensor": Row("redi_tensor", _SLOPE + _of("real", "kappa", "slope_max2") + _of("flag", "taper")
+                          + _results("out_x", "out_y", "out_z", at="faces") + _OUTER_XYZ + _STREAM, True),
+    "xg_redi_vertical_flux_divergence": Row("redi_vertical_flux_divergence", _fields("a") + _fields("kwx", "kwy", at="faces")
+                                            + _metrics(("mx", "X metric"), ("my", "Y metric"), ("mc", "Z metric at the centre"))
+                                            + _results("out") + _SHAPE + _of("flag", "outer", "closed") + _bc("x", "y", "z") + _STREAM, True),
+}
+for _name in ("vorticity", "divergence"):
+    FUSED["xg_" + _name] = Row(_name, _fields("u", "v") + _HALOS + _metrics("area") + _results("out") + _XY + _STREAM)
+
+
+def forms(name: str):
+    """(entry, has the halo slots) of the forms of row `name`: itself, and `_halo` where the row has halo slots"""
+    return [(name, False)] + [(name + "_halo", True)] * any(s.kind == "halo" for s in FUSED[name].slots)
+
+
+def _argtypes(row: Row, halo: bool, real):
+    per = {"metric": [_vp, _i64p], "shape": [_i64p, C.c_int], "flag": [C.c_int], "real": [real]}
+    args = [C.c_int] if row.typed else []
+    for s in row.slots:
+        if s.kind != "halo" or halo:
+            args += [C.c_int] + [real] * len(s.fills) if s.kind == "bc" else per.get(s.kind, [_vp])
+    return args
+
+
+for _name, _row in FUSED.items():
+    for _entry, _halo in forms(_name):
+        if _row.typed:
+            SIGNATURES[_entry] = (C.c_int, _argtypes(_row, _halo, C.c_double))
+        else:
+            SIGNATURES[_entry + "_f64"] = (C.c_int, _argtypes(_row, _halo, C.c_double))
+            SIGNATURES[_entry + "_f32"] = (C.c_int, _argtypes(_row, _halo, C.c_float))
 
 
 class MultiDesc(C.Structure):

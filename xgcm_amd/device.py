@@ -19,11 +19,12 @@ for `da * metric` (reference xgcm/grid.py:806-808,830-832).
 from __future__ import annotations
 
 import contextlib
+import functools
 import os
 import threading
 import weakref
 from collections import OrderedDict
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -353,9 +354,13 @@ def _is_int(x) -> bool:
 def _common(*arrays):
     """(dtype, ABI suffix) of the float lanes an array and its metrics share: numpy's promotion -- float32 only if it
     yields float32 (all float32, or float32 next to 8 / 16-bit integers), float64 otherwise."""
-    present = [_dt.np_dtype(a) for a in arrays if a is not None]
-    f = _dt.float_of(*present)
-    return (torch.float32, "f32") if f == _dt.FLOAT32 else (torch.float64, "f64")
+    return _lanes(tuple([_dt.np_dtype(a) for a in arrays if a is not None]))
+
+
+@functools.lru_cache(maxsize=None)
+def _lanes(present: tuple):
+    """`_common` of these dtypes: every call asks, and few mixes ever occur"""
+    return (torch.float32, "f32") if _dt.float_of(*present) == _dt.FLOAT32 else (torch.float64, "f64")
 
 
 # ---- integer arrays: int64 / int32 lanes between a widening and a narrowing conversion (xgcm_amd.dtypes.lane_of) -------
@@ -1323,72 +1328,120 @@ def _binary_blockwise(op: str, a, b):
     return _ch.BlockArray(res.blocks, chunks, res.dtype)
 
 
-def _pair_halos(halo_x, halo_y, shape, dt):
-    hx = None if halo_x is None else asdevice(halo_x, dt).reshape(shape[:-2] + [shape[-2]])
-    hy = None if halo_y is None else asdevice(halo_y, dt).reshape(shape[:-2] + [shape[-1]])
-    return hx, hy
+class _Plan(NamedTuple):
+    """one form of a row of _hip.FUSED, resolved for `_fused` once at import"""
+
+    names: dict      # ABI suffix -> the entry's name (a typed entry has one name and takes the `dtype` code first)
+    arrays: tuple    # every array slot of the ROW: the halo slabs count towards the dtype whichever form is called
+    fields: tuple    # (name, the header takes NULL)
+    same: tuple      # the fields that share the shape everything else is measured against
+    mismatch: str    # ... and the error when they do not
+    metrics: tuple   # (name, name of its strides, the shape it broadcasts against, what a stride error calls it)
+    halos: tuple     # (name, the dim of the last two the slab keeps)
+    work: tuple      # names
+    results: tuple   # (name, the shape it has: "shape" / "faces")
+    call: tuple      # (the header's parameter name, value -> argument or None: as it is), in the ABI's order
+
+
+def _flag(x) -> int:
+    return int(bool(x))
+
+
+# value -> argument of the scalar slots (None: as it is); a pointer that is never NULL goes through Tensor.data_ptr itself
+_ARGUMENT = {"flag": _flag, "real": float, "bc": _hip.BC.__getitem__, "stream": None}
+
+
+def _plan(row, entry: str, halo: bool) -> _Plan:
+    slots = [s for s in row.slots if s.kind != "halo" or halo]
+    same = row.same or tuple(s.name for s in slots if s.kind == "field" and s.at == "shape")
+    call = [("dtype", None)] if row.typed else []
+    for s in slots:
+        if s.kind == "metric":
+            call += [(s.name, _ptr), (s.name + "_strides", None)]
+        elif s.kind == "shape":
+            call += [("shape", None), ("ndim", None)]
+        elif s.kind == "halo" or s.null:
+            call.append((s.name, _ptr))
+        else:  # (a boundary is its code and then its fills)
+            call.append((s.name, _ARGUMENT.get(s.kind, torch.Tensor.data_ptr)))
+            call += [(f, float) for f in s.fills]
+    return _Plan(
+        names={sfx: entry if row.typed else entry + "_" + sfx for sfx in ("f64", "f32")},
+        arrays=tuple(s.name for s in row.slots if s.kind in ("field", "halo", "metric")),
+        fields=tuple((s.name, s.null) for s in slots if s.kind == "field"), same=same,
+        mismatch=f"{row.op}: {', '.join(same[:-1])} and {same[-1]} must have the same shape",
+        metrics=tuple((s.name, s.name + "_strides", s.at, s.what) for s in slots if s.kind == "metric"),
+        halos=tuple((s.name, s.dim) for s in slots if s.kind == "halo"), work=tuple(s.name for s in slots if s.kind == "work"),
+        results=tuple((s.name, s.at) for s in slots if s.kind == "result"), call=tuple(call))
+
+
+_PLANS = {entry: _plan(row, entry, halo) for name, row in _hip.FUSED.items() for entry, halo in _hip.forms(name)}
+_DTYPE_CODE = {"f64": _hip.DTYPE["float64"], "f32": _hip.DTYPE["float32"]}
+
+
+def _fused(entry: str, v: dict, check=None):
+    """ONE call of a fused entry point, marshalled from its row of _hip.FUSED.  `v` holds the values by the parameter names
+    of include/xgcm_hip.h: a wrapper hands over its own `locals()` (names the row does not have are ignored), and what is
+    made here -- results, work buffers, strides, `shape`, `ndim`, `dtype`, `stream` -- joins them under its own name.
+    `check(v)`, called once the fields are placed, is the wrapper's own validation; it returns the shape of the faces of Z
+    where the row measures something against them.  Returns the result, or the tuple of them."""
+    names, arrays, fields, same, mismatch, metrics, halos, work, results, call = _PLANS[entry]
+    lib = _MEM.lib()
+    dt, sfx = _common(*[v[n] for n in arrays])
+    for n, null in fields:
+        if not (null and v[n] is None):
+            v[n] = asdevice(v[n], dt)
+    faces = None if check is None else check(v)
+    first = v[same[0]]
+    for n in same[1:]:
+        if v[n] is not None and v[n].shape != first.shape:
+            raise ValueError(mismatch)
+    shape = list(first.shape)
+    shapes = {"shape": shape, "faces": faces}
+    for n, _, _, _ in metrics:
+        v[n] = _prep_metric(v[n], dt)
+    outs = []
+    for n, at in results:
+        v[n] = _empty(shapes[at], dtype=dt, device=first.device)
+        outs.append(v[n])
+    if outs[0].numel():  # (nothing to launch for an empty result: a NULL data_ptr is not a valid ABI argument)
+        for n, dim in halos:
+            v[n] = None if v[n] is None else asdevice(v[n], dt).reshape(shape[:-2] + [shape[dim]])
+        for n in work:
+            v[n] = _empty(shape, dtype=dt, device=first.device)
+        for n, strides, at, what in metrics:
+            v[strides] = _hip.i64(_bstrides(v[n], shapes[at], what))
+        v["dtype"], v["shape"], v["ndim"], v["stream"] = _DTYPE_CODE[sfx], _hip.i64(shape), len(shape), _stream()
+        _check(getattr(lib, names[sfx])(*[v[n] if arg is None else arg(v[n]) for n, arg in call]))
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def _form(entry: str, bc_x, bc_y) -> str:
+    """the `_halo` form of an entry where an axis takes its one-cell halo from a pre-gathered slab"""
+    return entry + "_halo" if bc_x == "halo" or bc_y == "halo" else entry
+
+
+def _faces(t: torch.Tensor, outer: bool, need: str, level: bool = True):
+    """shape of the faces of Z over the placed field `t`: its levels (Z:left) or, `outer`, one more (Z:outer); `need`: the
+    error for a field without (Z, Y, X) as its last three dims or, `level`, without a level along Z"""
+    if t.dim() < 3 or (level and t.shape[-3] == 0):
+        raise ValueError(need)
+    shape = list(t.shape)
+    return shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
 
 
 def vorticity(u, v, area, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, halo_x=None,
               halo_y=None) -> torch.Tensor:
     """Fused ((v[j,i]-v[j,i-1]) - (u[j,i]-u[j-1,i])) / area on (..., Y, X) arrays (xg_vorticity_f64).
     A boundary mode "halo" takes that axis' one-cell halo from `halo_x` (..., Y) / `halo_y` (..., X)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, area, halo_x, halo_y)
-    u = asdevice(u, dt)
-    v = asdevice(v, dt)
-    if u.shape != v.shape:
-        raise ValueError("vorticity: u and v must have the same shape")
-    shape = list(u.shape)
-    area = _prep_metric(area, dt)
-    out = _empty(shape, dtype=dt, device=u.device)
-    if out.numel() == 0:
-        return out
-    if bc_x == "halo" or bc_y == "halo":
-        hx, hy = _pair_halos(halo_x, halo_y, shape, dt)
-        _check(
-            getattr(lib, "xg_vorticity_halo_" + sfx)(u.data_ptr(), v.data_ptr(), _ptr(hx), _ptr(hy), _ptr(area),
-                                          _hip.i64(_bstrides(area, shape, "area")), out.data_ptr(), _hip.i64(shape),
-                                          len(shape), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y), _stream())
-        )
-        return out
-    _check(
-        getattr(lib, "xg_vorticity_" + sfx)(u.data_ptr(), v.data_ptr(), _ptr(area), _hip.i64(_bstrides(area, shape, "area")),
-                             out.data_ptr(), _hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x),
-                             _hip.BC[bc_y], float(fill_y), _stream())
-    )
-    return out
+    return _fused(_form("xg_vorticity", bc_x, bc_y), locals())
 
 
 def divergence(u, v, area, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, halo_x=None,
                halo_y=None) -> torch.Tensor:
     """Fused ((u[j,i+1]-u[j,i]) + (v[j+1,i]-v[j,i])) / area on (..., Y, X) arrays (xg_divergence_f64).
     A boundary mode "halo" takes that axis' one-cell halo from `halo_x` (..., Y) / `halo_y` (..., X)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, area, halo_x, halo_y)
-    u = asdevice(u, dt)
-    v = asdevice(v, dt)
-    if u.shape != v.shape:
-        raise ValueError("divergence: u and v must have the same shape")
-    shape = list(u.shape)
-    area = _prep_metric(area, dt)
-    out = _empty(shape, dtype=dt, device=u.device)
-    if out.numel() == 0:
-        return out
-    if bc_x == "halo" or bc_y == "halo":
-        hx, hy = _pair_halos(halo_x, halo_y, shape, dt)
-        _check(
-            getattr(lib, "xg_divergence_halo_" + sfx)(u.data_ptr(), v.data_ptr(), _ptr(hx), _ptr(hy), _ptr(area),
-                                          _hip.i64(_bstrides(area, shape, "area")), out.data_ptr(), _hip.i64(shape),
-                                          len(shape), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y), _stream())
-        )
-        return out
-    _check(
-        getattr(lib, "xg_divergence_" + sfx)(u.data_ptr(), v.data_ptr(), _ptr(area), _hip.i64(_bstrides(area, shape, "area")),
-                             out.data_ptr(), _hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x),
-                             _hip.BC[bc_y], float(fill_y), _stream())
-    )
-    return out
+    return _fused(_form("xg_divergence", bc_x, bc_y), locals())
 
 
 def gradient(a, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, mx=None, my=None, halo_x=None,
@@ -1396,70 +1449,20 @@ def gradient(a, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, 
     """Fused (a - a[x-1]) / mx and (a - a[y-1]) / my on a (..., Y, X) array, both center -> left
     (xg_gradient_f64); `mx` / `my` None = plain differences.  A boundary mode "halo" takes that axis'
     one-cell halo of `a` from `halo_x` (..., Y) / `halo_y` (..., X).  Returns (out_x, out_y)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(a, mx, my, halo_x, halo_y)
-    a = asdevice(a, dt)
-    shape = list(a.shape)
-    mx, my = _prep_metric(mx, dt), _prep_metric(my, dt)
-    out_x = _empty(shape, dtype=dt, device=a.device)
-    out_y = _empty(shape, dtype=dt, device=a.device)
-    if a.numel() == 0:
-        return out_x, out_y
-    tail = (_hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y), _ptr(mx),
-            _hip.i64(_bstrides(mx, shape, "mx")), _ptr(my), _hip.i64(_bstrides(my, shape, "my")), _stream())
-    if bc_x == "halo" or bc_y == "halo":
-        hx, hy = _pair_halos(halo_x, halo_y, shape, dt)
-        _check(getattr(lib, "xg_gradient_halo_" + sfx)(a.data_ptr(), _ptr(hx), _ptr(hy), out_x.data_ptr(),
-                                                          out_y.data_ptr(), *tail))
-    else:
-        _check(getattr(lib, "xg_gradient_" + sfx)(a.data_ptr(), out_x.data_ptr(), out_y.data_ptr(), *tail))
-    return out_x, out_y
+    return _fused(_form("xg_gradient", bc_x, bc_y), locals())
 
 
 def flux(u, v, t, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, halo_x=None, halo_y=None):
     """Fused u * (t[x-1] + t) / 2 and v * (t[y-1] + t) / 2 on (..., Y, X) arrays (xg_flux_f64); the
     boundary modes (or the pre-gathered "halo" slabs) pad the TRACER.  Returns (flux_x, flux_y)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, t, halo_x, halo_y)
-    u, v, t = asdevice(u, dt), asdevice(v, dt), asdevice(t, dt)
-    if u.shape != t.shape or v.shape != t.shape:
-        raise ValueError("flux: u, v and t must have the same shape")
-    shape = list(t.shape)
-    out_x = _empty(shape, dtype=dt, device=t.device)
-    out_y = _empty(shape, dtype=dt, device=t.device)
-    if t.numel() == 0:
-        return out_x, out_y
-    tail = (out_x.data_ptr(), out_y.data_ptr(), _hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x),
-            _hip.BC[bc_y], float(fill_y), _stream())
-    if bc_x == "halo" or bc_y == "halo":
-        hx, hy = _pair_halos(halo_x, halo_y, shape, dt)
-        _check(getattr(lib, "xg_flux_halo_" + sfx)(u.data_ptr(), v.data_ptr(), t.data_ptr(), _ptr(hx), _ptr(hy), *tail))
-    else:
-        _check(getattr(lib, "xg_flux_" + sfx)(u.data_ptr(), v.data_ptr(), t.data_ptr(), *tail))
-    return out_x, out_y
+    return _fused(_form("xg_flux", bc_x, bc_y), locals())
 
 
 def flux_divergence(u, v, t, area, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused divergence(flux(u, v, t)) in one pass (xg_flux_divergence_f64): the flux u * (t[x-1] + t) / 2,
     v * (t[y-1] + t) / 2 never leaves the registers.  `bc_x` / `bc_y` pad the tracer below / left of the first cell
     and the flux above / right of the last one, as the two operators of the chain do; `area` None = no division."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, t, area)
-    u, v, t = asdevice(u, dt), asdevice(v, dt), asdevice(t, dt)
-    if u.shape != t.shape or v.shape != t.shape:
-        raise ValueError("flux_divergence: u, v and t must have the same shape")
-    shape = list(t.shape)
-    area = _prep_metric(area, dt)
-    out = _empty(shape, dtype=dt, device=t.device)
-    if out.numel() == 0:
-        return out
-    _check(
-        getattr(lib, "xg_flux_divergence_" + sfx)(u.data_ptr(), v.data_ptr(), t.data_ptr(), _ptr(area),
-                                                  _hip.i64(_bstrides(area, shape, "area")), out.data_ptr(),
-                                                  _hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x),
-                                                  _hip.BC[bc_y], float(fill_y), _stream())
-    )
-    return out
+    return _fused("xg_flux_divergence", locals())
 
 
 def flux_divergence_3d(u, v, w, t, vol, vol2, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0, fill_y: float = 0.0,
@@ -1467,24 +1470,7 @@ def flux_divergence_3d(u, v, w, t, vol, vol2, bc_x: str, bc_y: str, bc_z: str, f
     """Fused 3-D tracer flux divergence in one pass (xg_flux_divergence3d_f64): flux_divergence's horizontal part plus
     Fz[k+1] - Fz[k] with Fz = w * (t[z-1] + t) / 2, divided by `vol` (* `vol2`, the product formed per cell); `vol` None = no
     division.  Each axis pads twice as the chain does: the tracer below the first cell, then the flux above the last one."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, w, t, vol, vol2)
-    u, v, w, t = asdevice(u, dt), asdevice(v, dt), asdevice(w, dt), asdevice(t, dt)
-    if u.shape != t.shape or v.shape != t.shape or w.shape != t.shape:
-        raise ValueError("flux_divergence_3d: u, v, w and t must have the same shape")
-    shape = list(t.shape)
-    vol, vol2 = _prep_metric(vol, dt), _prep_metric(vol2, dt)
-    out = _empty(shape, dtype=dt, device=t.device)
-    if out.numel() == 0:
-        return out
-    _check(
-        getattr(lib, "xg_flux_divergence3d_" + sfx)(u.data_ptr(), v.data_ptr(), w.data_ptr(), t.data_ptr(), _ptr(vol),
-                                                    _hip.i64(_bstrides(vol, shape, "volume")), _ptr(vol2),
-                                                    _hip.i64(_bstrides(vol2, shape, "volume")), out.data_ptr(),
-                                                    _hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x),
-                                                    _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z), _stream())
-    )
-    return out
+    return _fused("xg_flux_divergence3d", locals())
 
 
 def vertical_velocity(u, v, mu, mu2, mv, mv2, area, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0,
@@ -1492,25 +1478,7 @@ def vertical_velocity(u, v, mu, mu2, mv, mv2, area, bc_x: str, bc_y: str, bc_z: 
     """Fused w from continuity in one pass (xg_vertical_velocity_f64): the divergence of u * (mu * mu2) and v * (mv * mv2)
     (None: the field itself), its nancumsum along Z from the centre to the left position (upward with the Z pad at level 0,
     or `reverse`), negated and divided by `area` (None = no division).  The second factors vary along Z only."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, mu, mu2, mv, mv2, area)
-    u, v = asdevice(u, dt), asdevice(v, dt)
-    if u.shape != v.shape:
-        raise ValueError("vertical_velocity: u and v must have the same shape")
-    shape = list(u.shape)
-    mets = [_prep_metric(m, dt) for m in (mu, mu2, mv, mv2, area)]
-    out = _empty(shape, dtype=dt, device=u.device)
-    if out.numel() == 0:
-        return out
-    margs = []
-    for m, what in zip(mets, ("face weight", "face weight", "face weight", "face weight", "area")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
-    _check(
-        getattr(lib, "xg_vertical_velocity_" + sfx)(u.data_ptr(), v.data_ptr(), *margs, out.data_ptr(), _hip.i64(shape),
-                                                    len(shape), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y),
-                                                    _hip.BC[bc_z], float(fill_z), int(bool(reverse)), _stream())
-    )
-    return out
+    return _fused("xg_vertical_velocity", locals())
 
 
 def hydrostatic_pressure_gradient(b, w, dxC, dyC, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0, fill_y: float = 0.0,
@@ -1519,25 +1487,7 @@ def hydrostatic_pressure_gradient(b, w, dxC, dyC, bc_x: str, bc_y: str, bc_z: st
     b * w along Z from the centre to the outer position (the Z pad at level 0), its mean at the centre, and that field's
     differences towards the left points along X and Y, divided by `dxC` / `dyC` (None = no division; `w` None = b itself).
     Returns (gx, gy)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(b, w, dxC, dyC)
-    b = asdevice(b, dt)
-    shape = list(b.shape)
-    mets = [_prep_metric(m, dt) for m in (w, dxC, dyC)]
-    out_x = _empty(shape, dtype=dt, device=b.device)
-    out_y = _empty(shape, dtype=dt, device=b.device)
-    if out_x.numel() == 0:
-        return out_x, out_y
-    margs = []
-    for m, what in zip(mets, ("Z weight", "dxC", "dyC")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
-    _check(
-        getattr(lib, "xg_hydrostatic_pressure_gradient_" + sfx)(b.data_ptr(), *margs, out_x.data_ptr(), out_y.data_ptr(),
-                                                                _hip.i64(shape), len(shape), _hip.BC[bc_x], float(fill_x),
-                                                                _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z),
-                                                                _stream())
-    )
-    return out_x, out_y
+    return _fused("xg_hydrostatic_pressure_gradient", locals())
 
 
 def vertical_momentum_advection(u, v, w, mu, mv, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0, fill_y: float = 0.0,
@@ -1546,27 +1496,7 @@ def vertical_momentum_advection(u, v, w, mu, mv, bc_x: str, bc_y: str, bc_z: str
     and the one left of / below it, times the difference of u / v to the level above, the mean of that product with the
     next level's, negated and divided by `mu` / `mv` (None = no division).  Each stage pads as the chain does: w left of /
     below the first cell, u and v above level 0, the products beyond the last level.  Returns (gu, gv)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, w, mu, mv)
-    u, v, w = asdevice(u, dt), asdevice(v, dt), asdevice(w, dt)
-    if v.shape != u.shape or w.shape != u.shape:
-        raise ValueError("vertical_momentum_advection: u, v and w must have the same shape")
-    shape = list(u.shape)
-    mets = [_prep_metric(m, dt) for m in (mu, mv)]
-    out_u = _empty(shape, dtype=dt, device=u.device)
-    out_v = _empty(shape, dtype=dt, device=u.device)
-    if out_u.numel() == 0:
-        return out_u, out_v
-    margs = []
-    for m, what in zip(mets, ("metric of gu", "metric of gv")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
-    _check(
-        getattr(lib, "xg_vertical_momentum_advection_" + sfx)(u.data_ptr(), v.data_ptr(), w.data_ptr(), *margs,
-                                                              out_u.data_ptr(), out_v.data_ptr(), _hip.i64(shape),
-                                                              len(shape), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y],
-                                                              float(fill_y), _hip.BC[bc_z], float(fill_z), _stream())
-    )
-    return out_u, out_v
+    return _fused("xg_vertical_momentum_advection", locals())
 
 
 def vertical_diffusion(a, kappa, mf, mc, outer: bool, bc_z: str, fill_z: float = 0.0) -> torch.Tensor:
@@ -1575,23 +1505,8 @@ def vertical_diffusion(a, kappa, mf, mc, outer: bool, bc_z: str, fill_z: float =
     `mc` (None = that step is absent).  `outer` False: the flux at Z:left -- `a` is padded above level 0, the flux beyond
     the last level; True: at Z:outer -- `a` is padded on both sides, the flux has one level more and needs no pad.  `kappa`
     and `mf` broadcast against the flux' shape, `mc` against `a`'s."""
-    lib = _MEM.lib()
-    dt, sfx = _common(a, kappa, mf, mc)
-    a = asdevice(a, dt)
-    if a.dim() < 3:
-        raise ValueError("vertical_diffusion: the field needs (Z, Y, X) as its last three dims")
-    shape = list(a.shape)
-    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
-    kappa, mf, mc = (_prep_metric(m, dt) for m in (kappa, mf, mc))
-    out = _empty(shape, dtype=dt, device=a.device)
-    if out.numel() == 0:
-        return out
-    margs = []
-    for m, against, what in ((kappa, fshape, "kappa"), (mf, fshape, "metric of the flux"), (mc, shape, "metric of the result")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
-    _check(lib.xg_vertical_diffusion(_hip.DTYPE["float32" if sfx == "f32" else "float64"], a.data_ptr(), *margs, out.data_ptr(),
-                                     _hip.i64(shape), len(shape), int(bool(outer)), _hip.BC[bc_z], float(fill_z), _stream()))
-    return out
+    need = "vertical_diffusion: the field needs (Z, Y, X) as its last three dims"
+    return _fused("xg_vertical_diffusion", locals(), lambda p: _faces(p["a"], outer, need, level=False))
 
 
 def implicit_vertical_diffusion(a, kappa, mf, mc, outer: bool, dt: float) -> torch.Tensor:
@@ -1600,25 +1515,8 @@ def implicit_vertical_diffusion(a, kappa, mf, mc, outer: bool, dt: float) -> tor
     in one launch.  `kappa` and `mf` (None = absent) broadcast against the flux' shape, which has `a`'s levels (`outer`
     False, Z:left) or one more (True, Z:outer); `mc` against `a`'s.  The workspace of the forward sweep is allocated here,
     per call: the library keeps no state between calls."""
-    lib = _MEM.lib()
-    dt_, sfx = _common(a, kappa, mf, mc)
-    a = asdevice(a, dt_)
-    if a.dim() < 3:
-        raise ValueError("implicit_vertical_diffusion: the field needs (Z, Y, X) as its last three dims")
-    shape = list(a.shape)
-    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
-    kappa, mf, mc = (_prep_metric(m, dt_) for m in (kappa, mf, mc))
-    out = _empty(shape, dtype=dt_, device=a.device)
-    if out.numel() == 0:
-        return out
-    work = _empty(shape, dtype=dt_, device=a.device)
-    margs = []
-    for m, against, what in ((kappa, fshape, "kappa"), (mf, fshape, "metric of the flux"), (mc, shape, "metric of the result")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
-    _check(lib.xg_implicit_vertical_diffusion(_hip.DTYPE["float32" if sfx == "f32" else "float64"], a.data_ptr(), *margs,
-                                              work.data_ptr(), out.data_ptr(), _hip.i64(shape), len(shape), int(bool(outer)),
-                                              float(dt), _stream()))
-    return out
+    need = "implicit_vertical_diffusion: the field needs (Z, Y, X) as its last three dims"
+    return _fused("xg_implicit_vertical_diffusion", locals(), lambda p: _faces(p["a"], outer, need, level=False))
 
 
 def implicit_vertical_viscosity(u, v, nu, mfu, mcu, mfv, mcv, outer: bool, bc_x: str, bc_y: str, dt: float,
@@ -1629,31 +1527,13 @@ def implicit_vertical_viscosity(u, v, nu, mfu, mcu, mfv, mcv, outer: bool, bc_x:
     `nu`, `mfu` and `mfv` (the metrics of the two fluxes; None = absent) broadcast against the flux' shape, which has the
     fields' levels (`outer` False, Z:left) or one more (True, Z:outer); `mcu` and `mcv` against the fields'.  Returns
     `(xu, xv)`.  The two workspaces of the forward sweeps are allocated here, per call: the library keeps no state."""
-    lib = _MEM.lib()
-    dt_, sfx = _common(u, v, nu, mfu, mcu, mfv, mcv)
-    u, v = asdevice(u, dt_), asdevice(v, dt_)
-    if u.dim() < 3:
-        raise ValueError("implicit_vertical_viscosity: the fields need (Z, Y, X) as their last three dims")
-    if v.shape != u.shape:
-        raise ValueError("implicit_vertical_viscosity: u and v must have the same shape")
-    if nu is None:
-        raise ValueError("implicit_vertical_viscosity: nu is required")
-    shape = list(u.shape)
-    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
-    nu, mfu, mcu, mfv, mcv = (_prep_metric(m, dt_) for m in (nu, mfu, mcu, mfv, mcv))
-    out_u, out_v = (_empty(shape, dtype=dt_, device=u.device) for _ in range(2))
-    if out_u.numel() == 0:
-        return out_u, out_v
-    work_u, work_v = (_empty(shape, dtype=dt_, device=u.device) for _ in range(2))
-    margs = []
-    for m, against, what in ((nu, fshape, "nu"), (mfu, fshape, "metric of u's flux"), (mcu, shape, "metric of u's result"),
-                             (mfv, fshape, "metric of v's flux"), (mcv, shape, "metric of v's result")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
-    _check(lib.xg_implicit_vertical_viscosity(_hip.DTYPE["float32" if sfx == "f32" else "float64"], u.data_ptr(), v.data_ptr(),
-                                              *margs, work_u.data_ptr(), work_v.data_ptr(), out_u.data_ptr(), out_v.data_ptr(),
-                                              _hip.i64(shape), len(shape), int(bool(outer)), _hip.BC[bc_x], float(fill_x),
-                                              _hip.BC[bc_y], float(fill_y), float(dt), _stream()))
-    return out_u, out_v
+    def check(p):
+        faces = _faces(p["u"], outer, "implicit_vertical_viscosity: the fields need (Z, Y, X) as their last three dims", level=False)
+        if nu is None:
+            raise ValueError("implicit_vertical_viscosity: nu is required")
+        return faces
+
+    return _fused("xg_implicit_vertical_viscosity", locals(), check)
 
 
 def richardson_number(b, u, v, mu, mv, mb, outer: bool, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0,
@@ -1663,27 +1543,12 @@ def richardson_number(b, u, v, mu, mv, mb, outer: bool, bc_x: str, bc_y: str, bc
     right of / above them, the sum of their squares, the quotient.  `b` None: the squared shear alone (`mb` is ignored).
     `outer` False: nz faces (Z:left), the fields are padded above level 0; True: nz + 1 (Z:outer), padded on both sides.
     The differences are padded right of the last column / above the last row.  The metrics broadcast against the result."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, b, mu, mv, mb)
-    u, v = asdevice(u, dt), asdevice(v, dt)
-    b = None if b is None else asdevice(b, dt)
-    if u.dim() < 3 or u.shape[-3] == 0:
-        raise ValueError("richardson_number: the fields need (Z, Y, X) as their last three dims and a level along Z")
-    if v.shape != u.shape or (b is not None and b.shape != u.shape):
-        raise ValueError("richardson_number: u, v and b must have the same shape")
-    shape = list(u.shape)
-    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
-    mets = [_prep_metric(m, dt) for m in (mu, mv, None if b is None else mb)]
-    out = _empty(fshape, dtype=dt, device=u.device)
-    if out.numel() == 0:
-        return out
-    margs = []
-    for m, what in zip(mets, ("metric at u's points", "metric at v's points", "metric at the centre")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, fshape, what))]
-    _check(lib.xg_richardson_number(_hip.DTYPE["float32" if sfx == "f32" else "float64"], _ptr(b), u.data_ptr(), v.data_ptr(),
-                                    *margs, out.data_ptr(), _hip.i64(shape), len(shape), int(bool(outer)), _hip.BC[bc_x],
-                                    float(fill_x), _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z), _stream()))
-    return out
+    def check(p):
+        if p["b"] is None:
+            p["mb"] = None
+        return _faces(p["u"], outer, "richardson_number: the fields need (Z, Y, X) as their last three dims and a level along Z")
+
+    return _fused("xg_richardson_number", locals(), check)
 
 
 def richardson_mixing(b, u, v, mu, mv, mb, nu0: float, alpha: float, nu_b: float, kappa_b: float, shear_floor: float,
@@ -1693,28 +1558,8 @@ def richardson_mixing(b, u, v, mu, mv, mb, nu0: float, alpha: float, nu_b: float
     `richardson_number` forms them from `b`, `u`, `v` and the metrics, then ri = N2 / (S2 + shear_floor),
     rp = (ri + |ri|) * 0.5, den = 1 + alpha * rp, nu = nu0 / (den * den) + nu_b, kappa = nu / den + kappa_b.  The five
     scalars are cast to the fields' dtype once.  Returns (nu, kappa), two tensors of `richardson_number`'s result shape."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, b, mu, mv, mb)
-    b, u, v = asdevice(b, dt), asdevice(u, dt), asdevice(v, dt)
-    if u.dim() < 3 or u.shape[-3] == 0:
-        raise ValueError("richardson_mixing: the fields need (Z, Y, X) as their last three dims and a level along Z")
-    if v.shape != u.shape or b.shape != u.shape:
-        raise ValueError("richardson_mixing: u, v and b must have the same shape")
-    shape = list(u.shape)
-    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
-    mets = [_prep_metric(m, dt) for m in (mu, mv, mb)]
-    nu, kappa = _empty(fshape, dtype=dt, device=u.device), _empty(fshape, dtype=dt, device=u.device)
-    if nu.numel() == 0:
-        return nu, kappa
-    margs = []
-    for m, what in zip(mets, ("metric at u's points", "metric at v's points", "metric at the centre")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, fshape, what))]
-    _check(lib.xg_richardson_mixing(_hip.DTYPE["float32" if sfx == "f32" else "float64"], b.data_ptr(), u.data_ptr(),
-                                    v.data_ptr(), *margs, float(nu0), float(alpha), float(nu_b), float(kappa_b),
-                                    float(shear_floor), nu.data_ptr(), kappa.data_ptr(), _hip.i64(shape), len(shape),
-                                    int(bool(outer)), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z],
-                                    float(fill_z), _stream()))
-    return nu, kappa
+    need = "richardson_mixing: the fields need (Z, Y, X) as their last three dims and a level along Z"
+    return _fused("xg_richardson_mixing", locals(), lambda p: _faces(p["u"], outer, need))
 
 
 def isopycnal_slope(b, mx, my, mz, outer: bool, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0, fill_y: float = 0.0,
@@ -1724,24 +1569,8 @@ def isopycnal_slope(b, mx, my, mz, outer: bool, bc_x: str, bc_y: str, bc_z: str,
     level above; the difference of `b` to the level above divided by `mz`; the two quotients, negated.  `outer` False: nz
     faces (Z:left), padded above level 0; True: nz + 1 (Z:outer), padded on both sides.  `mx` and `my` broadcast against
     `b`, `mz` against the results.  Returns (sx, sy)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(b, mx, my, mz)
-    b = asdevice(b, dt)
-    if b.dim() < 3 or b.shape[-3] == 0:
-        raise ValueError("isopycnal_slope: the field needs (Z, Y, X) as its last three dims and a level along Z")
-    shape = list(b.shape)
-    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
-    mets = [_prep_metric(m, dt) for m in (mx, my, mz)]
-    sx, sy = _empty(fshape, dtype=dt, device=b.device), _empty(fshape, dtype=dt, device=b.device)
-    if sx.numel() == 0:
-        return sx, sy
-    margs = []
-    for m, against, what in zip(mets, (shape, shape, fshape), ("X metric", "Y metric", "Z metric at the faces")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
-    _check(lib.xg_isopycnal_slope(_hip.DTYPE["float32" if sfx == "f32" else "float64"], b.data_ptr(), *margs, sx.data_ptr(),
-                                  sy.data_ptr(), _hip.i64(shape), len(shape), int(bool(outer)), _hip.BC[bc_x], float(fill_x),
-                                  _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z), _stream()))
-    return sx, sy
+    need = "isopycnal_slope: the field needs (Z, Y, X) as its last three dims and a level along Z"
+    return _fused("xg_isopycnal_slope", locals(), lambda p: _faces(p["b"], outer, need))
 
 
 def redi_tensor(b, mx, my, mz, kappa: float, slope_max2, outer: bool, bc_x: str, bc_y: str, bc_z: str, fill_x: float = 0.0,
@@ -1751,26 +1580,10 @@ def redi_tensor(b, mx, my, mz, kappa: float, slope_max2, outer: bool, bc_x: str,
     kt = kappa * (slope_max2 / max(s2, slope_max2)), the maximum as m2 + (ex + |ex|) * 0.5 over ex = s2 - m2; `slope_max2`
     (the SQUARE of the largest slope) None: kt = kappa, no taper.  Both scalars are cast to the fields' dtype once.
     Returns (kwx, kwy, kwz)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(b, mx, my, mz)
-    b = asdevice(b, dt)
-    if b.dim() < 3 or b.shape[-3] == 0:
-        raise ValueError("redi_tensor: the field needs (Z, Y, X) as its last three dims and a level along Z")
-    shape = list(b.shape)
-    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
-    mets = [_prep_metric(m, dt) for m in (mx, my, mz)]
-    outs = tuple(_empty(fshape, dtype=dt, device=b.device) for _ in range(3))
-    if outs[0].numel() == 0:
-        return outs
-    margs = []
-    for m, against, what in zip(mets, (shape, shape, fshape), ("X metric", "Y metric", "Z metric at the faces")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, against, what))]
     taper = slope_max2 is not None
-    _check(lib.xg_redi_tensor(_hip.DTYPE["float32" if sfx == "f32" else "float64"], b.data_ptr(), *margs, float(kappa),
-                              float(slope_max2) if taper else 0.0, int(taper), *(o.data_ptr() for o in outs), _hip.i64(shape),
-                              len(shape), int(bool(outer)), _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y),
-                              _hip.BC[bc_z], float(fill_z), _stream()))
-    return outs
+    slope_max2 = slope_max2 if taper else 0.0
+    need = "redi_tensor: the field needs (Z, Y, X) as its last three dims and a level along Z"
+    return _fused("xg_redi_tensor", locals(), lambda p: _faces(p["b"], outer, need))
 
 
 def redi_vertical_flux_divergence(a, kwx, kwy, mx, my, mc, outer: bool, closed: bool, bc_x: str, bc_y: str, bc_z: str,
@@ -1781,75 +1594,28 @@ def redi_vertical_flux_divergence(a, kwx, kwy, mx, my, mc, outer: bool, closed: 
     and `kwy` have the face shape, nz faces (`outer` False) or nz + 1 (True): the results of `redi_tensor`.  `closed`: the
     flux at face 0 and, `outer`, at face nz is +0.0 and nothing is read there.  `mx`, `my` and `mc` broadcast against `a`.
     Returns the result, of `a`'s shape."""
-    lib = _MEM.lib()
-    dt, sfx = _common(a, kwx, kwy, mx, my, mc)
-    a = asdevice(a, dt)
-    if a.dim() < 3 or a.shape[-3] == 0:
-        raise ValueError("redi_vertical_flux_divergence: the field needs (Z, Y, X) as its last three dims and a level along Z")
-    shape = list(a.shape)
-    fshape = shape[:-3] + [shape[-3] + (1 if outer else 0)] + shape[-2:]
-    kwx, kwy = asdevice(kwx, dt), asdevice(kwy, dt)
-    for k, what in ((kwx, "kwx"), (kwy, "kwy")):
-        if list(k.shape) != fshape:
-            raise ValueError(f"redi_vertical_flux_divergence: {what} has shape {tuple(k.shape)}, the faces have {tuple(fshape)}")
-    kwx, kwy = kwx.contiguous(), kwy.contiguous()
-    mets = [_prep_metric(m, dt) for m in (mx, my, mc)]
-    out = _empty(shape, dtype=dt, device=a.device)
-    if out.numel() == 0:
-        return out
-    margs = []
-    for m, what in zip(mets, ("X metric", "Y metric", "Z metric at the centre")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
-    _check(lib.xg_redi_vertical_flux_divergence(_hip.DTYPE["float32" if sfx == "f32" else "float64"], a.data_ptr(),
-                                                kwx.data_ptr(), kwy.data_ptr(), *margs, out.data_ptr(), _hip.i64(shape),
-                                                len(shape), int(bool(outer)), int(bool(closed)), _hip.BC[bc_x], float(fill_x),
-                                                _hip.BC[bc_y], float(fill_y), _hip.BC[bc_z], float(fill_z), _stream()))
-    return out
+    def check(p):
+        faces = _faces(p["a"], outer, "redi_vertical_flux_divergence: the field needs (Z, Y, X) as its last three dims and a level along Z")
+        for what in ("kwx", "kwy"):
+            if list(p[what].shape) != faces:
+                raise ValueError(f"redi_vertical_flux_divergence: {what} has shape {tuple(p[what].shape)}, the faces have {tuple(faces)}")
+            p[what] = p[what].contiguous()
+        return faces
+
+    return _fused("xg_redi_vertical_flux_divergence", locals(), check)
 
 
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:
     """Fused 0.5 * (interp(u * u, X) + interp(v * v, Y)) at the cell centre in one pass (xg_kinetic_energy_f64): the
     squares are padded right of / above the last column / row (fill: the fill value itself)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v)
-    u, v = asdevice(u, dt), asdevice(v, dt)
-    if u.shape != v.shape:
-        raise ValueError("kinetic_energy: u and v must have the same shape")
-    shape = list(u.shape)
-    out = _empty(shape, dtype=dt, device=u.device)
-    if out.numel() == 0:
-        return out
-    _check(
-        getattr(lib, "xg_kinetic_energy_" + sfx)(u.data_ptr(), v.data_ptr(), out.data_ptr(), _hip.i64(shape), len(shape),
-                                                 _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y), _stream())
-    )
-    return out
+    return _fused("xg_kinetic_energy", locals())
 
 
 def momentum_advection(u, v, coriolis, rAz, dxC, dyC, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0):
     """Fused vector-invariant momentum advection (+ Coriolis) in one pass (xg_momentum_advection_f64): (gu, gv) with
     gu = interp(zeta, Y) * interp(interp(v, X), Y) - d ke / dx, gv = -(interp(zeta, X) * interp(interp(u, Y), X)) - d ke / dy,
     zeta = vorticity(u, v) / rAz + coriolis.  rAz, dxC, dyC all given or all None; `coriolis` None = no Coriolis term."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, coriolis, rAz, dxC, dyC)
-    u, v = asdevice(u, dt), asdevice(v, dt)
-    if u.shape != v.shape:
-        raise ValueError("momentum_advection: u and v must have the same shape")
-    shape = list(u.shape)
-    out_u = _empty(shape, dtype=dt, device=u.device)
-    out_v = _empty(shape, dtype=dt, device=u.device)
-    if out_u.numel() == 0:
-        return out_u, out_v
-    mets = [_prep_metric(m, dt) for m in (coriolis, rAz, dxC, dyC)]
-    margs = []
-    for m, what in zip(mets, ("coriolis", "rAz", "dxC", "dyC")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
-    _check(
-        getattr(lib, "xg_momentum_advection_" + sfx)(u.data_ptr(), v.data_ptr(), *margs, out_u.data_ptr(),
-                                                     out_v.data_ptr(), _hip.i64(shape), len(shape), _hip.BC[bc_x],
-                                                     float(fill_x), _hip.BC[bc_y], float(fill_y), _stream())
-    )
-    return out_u, out_v
+    return _fused("xg_momentum_advection", locals())
 
 
 def horizontal_viscosity(u, v, rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z, bc_x: str, bc_y: str, fill_x: float = 0.0,
@@ -1858,28 +1624,8 @@ def horizontal_viscosity(u, v, rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z, bc_x: st
     gu = d(D * nu_d) / dx - d(zeta * nu_z) / dy, gv = d(D * nu_d) / dy + d(zeta * nu_z) / dx, D = divergence(u, v) / rA,
     zeta = vorticity(u, v) / rAz.  The six metrics rA, rAz, dxC, dyC, dyG, dxG all given or all None; the two coefficients
     both given or both None.  `zfill_x` / `zfill_y` pad the product zeta * nu_z (default: `fill_x` / `fill_y`)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(u, v, rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z)
-    u, v = asdevice(u, dt), asdevice(v, dt)
-    if u.shape != v.shape:
-        raise ValueError("horizontal_viscosity: u and v must have the same shape")
-    shape = list(u.shape)
-    out_u = _empty(shape, dtype=dt, device=u.device)
-    out_v = _empty(shape, dtype=dt, device=u.device)
-    if out_u.numel() == 0:
-        return out_u, out_v
-    mets = [_prep_metric(m, dt) for m in (rA, rAz, dxC, dyC, dyG, dxG, nu_d, nu_z)]
-    margs = []
-    for m, what in zip(mets, ("rA", "rAz", "dxC", "dyC", "dyG", "dxG", "nu_d", "nu_z")):
-        margs += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
-    _check(
-        getattr(lib, "xg_horizontal_viscosity_" + sfx)(u.data_ptr(), v.data_ptr(), *margs, out_u.data_ptr(),
-                                                       out_v.data_ptr(), _hip.i64(shape), len(shape), _hip.BC[bc_x],
-                                                       float(fill_x), float(fill_x if zfill_x is None else zfill_x),
-                                                       _hip.BC[bc_y], float(fill_y),
-                                                       float(fill_y if zfill_y is None else zfill_y), _stream())
-    )
-    return out_u, out_v
+    zfill_x, zfill_y = fill_x if zfill_x is None else zfill_x, fill_y if zfill_y is None else zfill_y
+    return _fused("xg_horizontal_viscosity", locals())
 
 
 def laplacian(a, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0, dxC=None, dyC=None, dyG=None,
@@ -1887,22 +1633,7 @@ def laplacian(a, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0,
     """Fused finite-volume del2 in one pass (xg_laplacian_f64): Fx = (a - a[x-1]) / dxC * dyG, Fy = (a - a[y-1]) / dyC
     * dxG (the four metrics None: plain differences), then (Fx[x+1] - Fx + Fy[y+1] - Fy) / area -- gradient, the two
     face-length products and divergence bit for bit, with the two boundary rules of that chain (see flux_divergence)."""
-    lib = _MEM.lib()
-    dt, sfx = _common(a, dxC, dyC, dyG, dxG, area)
-    a = asdevice(a, dt)
-    shape = list(a.shape)
-    dxC, dyC, dyG, dxG, area = (_prep_metric(m, dt) for m in (dxC, dyC, dyG, dxG, area))
-    out = _empty(shape, dtype=dt, device=a.device)
-    if out.numel() == 0:
-        return out
-    args = []
-    for m, what in ((dxC, "dxC"), (dyC, "dyC"), (dyG, "dyG"), (dxG, "dxG"), (area, "area")):
-        args += [_ptr(m), _hip.i64(_bstrides(m, shape, what))]
-    _check(
-        getattr(lib, "xg_laplacian_" + sfx)(a.data_ptr(), *args, out.data_ptr(), _hip.i64(shape), len(shape),
-                                            _hip.BC[bc_x], float(fill_x), _hip.BC[bc_y], float(fill_y), _stream())
-    )
-    return out
+    return _fused("xg_laplacian", locals())
 
 
 def stencil2d_supported(x, padx, pady) -> bool:
