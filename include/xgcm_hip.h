@@ -58,6 +58,7 @@
  *   xg_redi_tensor      kappa * taper * (sx, sy, sx^2 + sy^2) of those slopes, the taper min(1, m2 / s2): one pass (likewise)
  *   xg_redi_vertical_flux_divergence  d/dz(kwx * gx + kwy * gy) of a tracer, gx and gy its level means at the faces: one
  *                      pass (likewise)
+ *   (the Gent-McWilliams eddy-induced velocity from xg_redi_tensor's results: include/xgcm_hip_gm.h)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)

@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only; 5pp: richardson_mixing against its chain, alone only; 5is: isopycnal_slope against its chain, alone only; 5rt: redi_tensor against its chain, alone or after 5is; 5rf: redi_vertical_flux_divergence against its chain, alone only), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only; 5pp: richardson_mixing against its chain, alone only; 5is: isopycnal_slope against its chain, alone only; 5rt: redi_tensor against its chain, alone or after 5is; 5rf: redi_vertical_flux_divergence against its chain, alone only; 5bv: bolus_velocity against its chain, alone only), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -492,6 +492,77 @@ def run_redi_vertical_flux_divergence(reps, nz=90, n=4320):
     print(json.dumps({"config": 5, "check": "one-pass redi_vertical_flux_divergence == chain bit for bit at full size", "ok": ok,
                       "result_finite_everywhere": finite, "fraction_of_cells_nonzero": round(nonzero, 4),
                       "outermost_faces_of_kwx_are_nan": nan_faces, "speedup": round(med(tc) / med(tf), 2),
+                      "rounds_ms_fused": [round(t, 3) for t in tf], "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_bolus_velocity(reps, nz=90, n=4320):
+    """bolus_velocity in one pass against its chain (two interpolations, the two copies that close the top and the bottom
+    faces, two derivatives along Z, two negations, two metric products and the fused divergence: eleven launches; dyG, dxG, rA,
+    drF(Z); periodic / extend / extend, Z:outer, closed=True), timed in turns, every paired round reported.  kwx and kwy are
+    `redi_tensor(b)`'s at its defaults, as they are: their outermost faces are NaN (0 * inf), which a closed call never reads.
+    By the count of its launches the chain moves about 184 B/cell (16 for each interpolation, closing copy and negation, 16
+    for each derivative, 16 for each product, 24 for the divergence) against the one pass's 40: two reads and three writes.
+    The two tensor columns 27 GB, the three results twice for the comparison 81 GB, the chain's live temporaries about 80 GB;
+    b and kwz are freed before: about 190 GB at the peak, all 90 levels."""
+    coords = {"XC": ("XC", np.arange(n) + 0.5), "XG": ("XG", np.arange(n) * 1.0), "YC": ("YC", np.arange(n) + 0.5),
+              "YG": ("YG", np.arange(n) * 1.0), "Z": ("Z", np.arange(nz) + 0.5), "Zp1": ("Zp1", np.arange(nz + 1) * 1.0)}
+    ds = Dataset({"dxC": DataArray(D.synthetic((n, n), 31, 0, 1000.0, 1000.0), ("YC", "XG")),
+                  "dyC": DataArray(D.synthetic((n, n), 32, 0, 1000.0, 1000.0), ("YG", "XC")),
+                  "dyG": DataArray(D.synthetic((n, n), 35, 0, 1000.0, 1000.0), ("YC", "XG")),
+                  "dxG": DataArray(D.synthetic((n, n), 36, 0, 1000.0, 1000.0), ("YG", "XC")),
+                  "rA": DataArray(D.synthetic((n, n), 37, 0, 1e6, 1e6), ("YC", "XC")),
+                  "drC": DataArray(D.synthetic((nz + 1,), 34, 0, 10.0, 10.0), ("Zp1",)),
+                  "drF": DataArray(D.synthetic((nz,), 33, 0, 10.0, 10.0), ("Z",))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                            "Z": {"center": "Z", "outer": "Zp1"}},
+                padding={"X": "periodic", "Y": "extend", "Z": "extend"},
+                metrics={("X",): ["dxC", "dxG"], ("Y",): ["dyC", "dyG"], ("X", "Y"): ["rA"], ("Z",): ["drC", "drF"]},
+                autoparse_metadata=False)
+    B = DataArray(D.synthetic((nz, n, n), 63), ("Z", "YC", "XC"))
+    kwx, kwy, kwz = grid.redi_tensor(B)
+    del B, kwz
+    torch.cuda.empty_cache()
+    cells = nz * n * n
+
+    def closed(p):
+        data = p.data.clone()     # the closed top and bottom: no eddy transport
+        data[0] = 0.0
+        data[nz] = 0.0
+        return p._replace(data=data)
+
+    def chain():
+        px, py = closed(grid.interp(kwx, "X")), closed(grid.interp(kwy, "Y"))
+        ub = -grid.derivative(px, "Z")
+        vb = -grid.derivative(py, "Z")
+        tx = px * grid.get_metric(px, ("Y",))
+        ty = py * grid.get_metric(py, ("X",))
+        del px, py
+        return ub, vb, grid.divergence(tx, ty)
+
+    one = lambda: grid.bolus_velocity(kwx, kwy)  # noqa: E731   (the defaults: closed=True)
+    got, want = list(one()), list(chain())
+    ok, finite, nonzero = [], [], []
+    while got:
+        g, w = got.pop(0), want.pop(0)
+        eq = g.data.view(torch.int64) == w.data.view(torch.int64)
+        eq |= torch.isnan(g.data) & torch.isnan(w.data)
+        ok.append(bool(eq.all()) and g.dims == w.dims)
+        finite.append(bool(torch.isfinite(g.data).all()))
+        nonzero.append(round(float((g.data != 0).double().mean()), 4))
+        del g, w, eq
+        torch.cuda.empty_cache()
+    nan_faces = bool(torch.isnan(kwx.data[0]).all() and torch.isnan(kwx.data[nz]).all())
+    tf, tc = timeit_rounds(one, chain, max(3, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    bpc = 40   # kwx, kwy in, ub, vb, wb out (the 91st face of kwx, kwy and wb is not counted)
+    rec(5, "bolus_velocity one pass: kwx, kwy in, Z:outer, closed, dyG, dxG, rA, drF(Z), periodic/extend/extend: 2 reads + 3 writes", med(tf), cells, bpc)
+    rec(5, "bolus_velocity as its chain (11 launches and the two closing copies), one-pass-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": "one-pass bolus_velocity == chain bit for bit at full size (ub, vb, wb)", "ok": ok,
+                      "result_finite_everywhere": finite, "fraction_of_cells_nonzero": nonzero,
+                      "outermost_faces_of_kwx_are_nan": nan_faces, "bytes_per_cell_one_pass": bpc, "bytes_per_cell_chain": 184,
+                      "bound_by_bytes": round(184 / bpc, 2), "speedup": round(med(tc) / med(tf), 2),
+                      "fraction_of_8TBps_at_40B_per_cell": round(cells * bpc / (med(tf) * 1e-3) / 8e12, 4),
                       "rounds_ms_fused": [round(t, 3) for t in tf], "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
 
@@ -1198,6 +1269,8 @@ def main():
         run_redi_tensor(a.reps)
     if "5rf" in cfgs:   # (not part of 5x: about 125 GB)
         run_redi_vertical_flux_divergence(a.reps)
+    if "5bv" in cfgs:   # (not part of 5x: about 190 GB)
+        run_bolus_velocity(a.reps, *((shp[0], shp[2]) if shp else (90, 4320)))
     ranks.close()
 
 

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/xgcm_hip.h"
+#include "../../include/xgcm_hip_gm.h"
 
 namespace {
 
@@ -1163,6 +1164,101 @@ int rediflux(const R* a, const R* kwx, const R* kwy, const R* const arr[3], cons
   return XG_OK;
 }
 
+// the bolus velocity of the header as the stages of its chain over one lead index at a time, each into a temporary: the two
+// means towards the left points, the closed faces, the differences to the next face's over their metrics, negated; the
+// two transports, their differences to the next column's / row's, the sum over the area.
+// arr[] = {mzu, mzv, dyG, dxG, rA}: the first two at the levels, the others at the faces
+template <typename R>
+int bolus(const R* kwx, const R* kwy, const R* const arr[5], const int64_t* const st[5], R* out_u, R* out_v, R* out_w,
+          const int64_t* shape, int ndim, int outer, int closed, const int bc[3], const R fill[3]) {  // bc, fill: X, Y, Z
+  const char* name = "bolus velocity";
+  if (!kwx || !kwy || !out_u || !out_v || !out_w || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "%s: ndim %d not in [3,%d]", name, ndim, XG_MAX_NDIM);
+  for (int k = 0; k < 3; ++k)
+    if (bc[k] < XG_BC_PERIODIC || bc[k] > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "%s: boundary mode %d: periodic, fill or extend", name, bc[k]);
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (closed != 0 && closed != 1) return fail(XG_ERR_INVALID, "%s: closed %d is neither 0 nor 1", name, closed);
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx;
+  if (nz < 1) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  for (int k = 0; k < 5; ++k)
+    if (arr[k] && !st[k]) return fail(XG_ERR_INVALID, "%s: metric without strides", name);
+  const int64_t nf = nz + outer;  // faces
+  int64_t lead = 1;
+  for (int d = 0; d < ndim - 3; ++d) lead *= shape[d];
+  if (lead == 0 || plane == 0) return XG_OK;
+  std::vector<R> psi[2], t[2];
+  for (int ax = 0; ax < 2; ++ax) {
+    psi[ax].resize((size_t)(nf * plane));
+    t[ax].resize((size_t)(nf * plane));
+  }
+  for (int64_t o = 0; o < lead; ++o) {
+    int64_t rem = o, off[5] = {0, 0, 0, 0, 0};  // the lead index decomposed for the broadcast strides
+    for (int dd = ndim - 4; dd >= 0; --dd) {
+      const int64_t i = rem % shape[dd];
+      rem /= shape[dd];
+      for (int k = 0; k < 5; ++k)
+        if (arr[k]) off[k] += i * st[k][dd];
+    }
+    auto met = [&](int k, int64_t z, int64_t j, int64_t i) -> R {
+      return arr[k][off[k] + z * st[k][ndim - 3] + j * st[k][ndim - 2] + i * st[k][ndim - 1]];
+    };
+    for (int ax = 0; ax < 2; ++ax) {  // 0: X, kwx, ub;  1: Y, kwy, vb
+      const R* kw = (ax == 0 ? kwx : kwy) + o * nf * plane;
+      const int64_t n = ax == 0 ? nx : ny, step = ax == 0 ? 1 : nx;
+      // (1) the mean with the cell before, (2) the closed faces, (3) the transport
+      for (int64_t z = 0; z < nf; ++z) {
+        const bool shut = closed && (z == 0 || z == nz);  // (kw is not read there)
+        for (int64_t j = 0; j < ny; ++j)
+          for (int64_t i = 0; i < nx; ++i) {
+            const int64_t c = z * plane + j * nx + i, at = ax == 0 ? i : j;
+            R p = R(0);
+            if (!shut) {
+              R before;
+              if (at > 0) before = kw[c - step];
+              else if (bc[ax] == XG_BC_FILL) before = fill[ax];
+              else before = kw[c + ((bc[ax] == XG_BC_PERIODIC) ? n - 1 : 0) * step];
+              p = (before + kw[c]) * R(0.5);
+            }
+            psi[ax][c] = p;
+            t[ax][c] = arr[2 + ax] ? p * met(2 + ax, z, j, i) : p;
+          }
+      }
+      // (4) the difference to the next face's over the metric, negated; `left` pads the streamfunction beyond its last face
+      R* po = (ax == 0 ? out_u : out_v) + o * nz * plane;
+      for (int64_t z = 0; z < nz; ++z)
+        for (int64_t j = 0; j < ny; ++j)
+          for (int64_t i = 0; i < nx; ++i) {
+            const int64_t c = j * nx + i;
+            R next;
+            if (z + 1 < nf) next = psi[ax][(z + 1) * plane + c];
+            else if (bc[2] == XG_BC_FILL) next = fill[2];
+            else next = psi[ax][((bc[2] == XG_BC_PERIODIC) ? 0 : nz - 1) * plane + c];
+            R d = next - psi[ax][z * plane + c];
+            if (arr[ax]) d = d / met(ax, z, j, i);
+            po[z * plane + c] = R(-1) * d;
+          }
+    }
+    // (5) the divergence of the transports, each padded beyond its last column / row, over the area
+    R* pw = out_w + o * nf * plane;
+    for (int64_t z = 0; z < nf; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t c = z * plane + j * nx + i;
+          R right, up;
+          if (i + 1 < nx) right = t[0][c + 1];
+          else if (bc[0] == XG_BC_FILL) right = fill[0];
+          else right = t[0][c - i + ((bc[0] == XG_BC_PERIODIC) ? 0 : nx - 1)];
+          if (j + 1 < ny) up = t[1][c + nx];
+          else if (bc[1] == XG_BC_FILL) up = fill[1];
+          else up = t[1][c - j * nx + ((bc[1] == XG_BC_PERIODIC) ? 0 : ny - 1) * nx];
+          R d = (right - t[0][c]) + (up - t[1][c]);
+          if (arr[4]) d = d / met(4, z, j, i);
+          pw[c] = d;
+        }
+  }
+  return XG_OK;
+}
+
 // kinetic energy (ke_only) and the vector-invariant momentum advection of the header: the stages of the chain one after
 // the other over whole planes, each read through `get`, which pads a plane by one cell on one axis at a time (periodic:
 // the plane's own value at the wrapped index, extend: at the clamped index, fill: the fill value of that axis).
@@ -1884,6 +1980,27 @@ int xg_redi_vertical_flux_divergence(int dtype, const void* a, const void* kwx, 
                            closed, bc, fill);
   }
   return fail(XG_ERR_INVALID, "redi vertical flux divergence: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+
+int xg_bolus_velocity(int dtype, const void* kwx, const void* kwy, const void* mzu, const int64_t* mzus, const void* mzv,
+                      const int64_t* mzvs, const void* dyG, const int64_t* dyGs, const void* dxG, const int64_t* dxGs,
+                      const void* rA, const int64_t* rAs, void* out_u, void* out_v, void* out_w, const int64_t* shape, int ndim,
+                      int outer, int closed, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void*) {
+  const int64_t* const st[5] = {mzus, mzvs, dyGs, dxGs, rAs};
+  const int bc[3] = {bc_x, bc_y, bc_z};
+  if (dtype == XG_T_F64) {
+    const double* const arr[5] = {(const double*)mzu, (const double*)mzv, (const double*)dyG, (const double*)dxG, (const double*)rA};
+    const double fill[3] = {fill_x, fill_y, fill_z};
+    return bolus<double>((const double*)kwx, (const double*)kwy, arr, st, (double*)out_u, (double*)out_v, (double*)out_w, shape,
+                         ndim, outer, closed, bc, fill);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const arr[5] = {(const float*)mzu, (const float*)mzv, (const float*)dyG, (const float*)dxG, (const float*)rA};
+    const float fill[3] = {(float)fill_x, (float)fill_y, (float)fill_z};
+    return bolus<float>((const float*)kwx, (const float*)kwy, arr, st, (float*)out_u, (float*)out_v, (float*)out_w, shape, ndim,
+                        outer, closed, bc, fill);
+  }
+  return fail(XG_ERR_INVALID, "bolus velocity: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 
 int xg_convert(const void* src, int st, void* dst, int dt, uint64_t n, int via, double scale, int flags, void*) {

@@ -4,6 +4,7 @@
 #include <initializer_list>
 
 #include "xg_common.hpp"
+#include "../../include/xgcm_hip_gm.h"
 
 // rows of Y per wave-task of the fused two-component kernels (see STENCIL_SEG in xg_stencil.hip): A/B on one GPU
 // (XG_HIP_LIB), 4320 x 4320 x 90: vorticity 70.0 / 71.7 / 71.3 % with 4 / 2 / 1 rows, gradient 73.9 / 75.7 / 75.6 %,
@@ -2690,6 +2691,222 @@ __global__ __launch_bounds__(BLOCK) void k_islope(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7t: the Gent-McWilliams eddy-induced (bolus) velocity from the two tensor components of K7r in ONE pass over
+// (lead, Z, Y, X), two fields in at the faces of Z (nz of them at Z:left, nz + 1 at Z:outer), three out:
+//   px[i] = (kwx[i-1] + kwx[i]) * 0.5      py[j] = (kwy[j-1] + kwy[j]) * 0.5       the streamfunction at u's / v's columns
+//   closed: px = py = +0.0 at face 0 and, `outer`, at face nz -- their rows of kwx and kwy are never loaded
+//   ub[k] = -1 * ((px[k+1] - px[k]) [/ mzu[k]])      vb[k] = -1 * ((py[k+1] - py[k]) [/ mzv[k]])         at the levels
+//   tx = px [* dyg]    ty = py [* dxg]    wb = ((tx[i+1] - tx[i]) + (ty[j+1] - ty[j])) [/ ra]            at the faces
+// i.e. interp (X / Y, center -> left), the closing copy, -diff | -derivative (Z, faces -> center), the two metric products
+// and K7b's divergence; no FMA, IEEE quotients.  Pads as the chain's: kwx left of column 0 / kwy below row 0, the TRANSPORTS
+// right of the last column / above the last row (periodic: the transport at index 0, extend: at n-1, fill: the fill value
+// itself), and, at Z:left, the streamfunction beyond face nz-1 (periodic: face 0's -- closed: that +0.0 --, extend: face
+// nz-1's, fill: fill_z itself).  A closed face of wb goes through the same products, differences and quotient with +0.0.
+// K7q's wave-task: a wave owns one (lead, Y segment, X tile) column and marches the faces.  A face brings SEG rows of kwx
+// with the element left of the lane's vector from the lane below by DPP (the tile's first lane and the row's edge load their
+// own) and SEG + 2 rows of kwy (the row below and the row above the segment: L2 hits); the finished transport right of the
+// vector comes from the lane above by DPP (the tile's last lane and a periodic edge form their own from the column right of
+// it), the transport of the row above is formed from the extra row.  px and py of the face above stay in registers for the
+// level between the two faces; at Z:left, periodic and open, face 0's are formed AGAIN after the march, as K7s forms its f[0]
+// (one more face read per column in that mode): held through the march they cost the float64 metric instance 16 VGPRs and
+// with them its second wave per SIMD (EXPERIMENTS.md "K7t").  Otherwise every input cell is read once; every result cell
+// is written once.  Five broadcast metrics, each may be absent: mzu and
+// mzv at the levels, dyg, dxg and ra at the faces; rows that do not vary along Z are loaded once per wave, dyg also at the
+// column right of the lane, dxg also at the row above the segment.
+// ------------------------------------------------------------------------------------------
+template <typename T, int SEG>
+struct BolusPsi {  // the streamfunction of the segment at one face
+  T x[SEG], y[SEG];
+};
+
+template <int V, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_bolus(
+    const real* __restrict__ kwx, const real* __restrict__ kwy, real* __restrict__ out_u, real* __restrict__ out_v,
+    real* __restrict__ out_w, int64_t o0, u32 nouter, u32 nblk, int64_t nz, int64_t ny, int64_t nx, FastDiv ntile,
+    FastDiv nseg, int outer, int closed, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, VolIdx mzu,
+    VolIdx mzv, VolIdx dyg, VolIdx dxg, VolIdx ra, int ntl) {
+  typedef typename VecT<V>::type T;
+  typedef BolusPsi<T, SEG> Psi;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t nf = nz + outer;                                    // faces
+  const int64_t fcol = o * nf * plane, lcol = o * nz * plane;       // face 0 / level 0 of this lead index (int64)
+  // X: the columns left and right of the lane's vector, always inside the row (the clamped left column IS the extend pad of
+  // kwx); a fill edge replaces kwx on the left, a fill or extend edge the transport on the right
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);
+  const bool per_x = bc_x == XG_BC_PERIODIC, per_z = bc_z == XG_BC_PERIODIC;
+  const bool fill_l = e.edge_l && bc_x == XG_BC_FILL;
+  const bool pad_r = e.edge_r && !per_x;
+  // Y: the row below the segment and the row above it, where the top transport is formed; wave-uniform
+  const bool fill_b = j0 == 0 && bc_y == XG_BC_FILL;
+  const int64_t jb = (j0 > 0) ? j0 - 1 : ((bc_y == XG_BC_PERIODIC) ? ny - 1 : 0);
+  const int64_t q = j0 + nrow;
+  const bool pad_t = q >= ny && bc_y != XG_BC_PERIODIC;
+  const int64_t jt = (q < ny) ? q : ((bc_y == XG_BC_PERIODIC) ? 0 : ny - 1);
+  int64_t ro[SEG];  // the segment's rows in a plane (short tails repeat the last row)
+#pragma unroll
+  for (int s_ = 0; s_ < SEG; ++s_) ro[s_] = (j0 + ((s_ < nrow) ? s_ : nrow - 1)) * nx;
+
+  // the metric rows of a face (dyg with the column right of the lane, dxg with the row above the segment, ra) and of a level
+  // (mzu, mzv): in registers, loaded again only when the array varies along Z
+  T dyr[SEG], dxr[SEG], dxt, rar[SEG], mur[SEG], mvr[SEG];
+  real dyrr[SEG];
+  int64_t dyo = 0, dro = 0, dxo = 0, dto = 0, rao = 0, muo = 0, mvo = 0;
+  auto fmetrics = [&](int64_t k, bool first) {
+    if (dyg.p && (first || dyg.sz != 0)) {
+      load_rows<T, SEG>(dyr, dyg.p, dyo + k * dyg.sz, dyg.sy, dyg.sx, nrow, (ntl & 4) != 0);
+      if (e.own_r) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) dyrr[s_] = dyg.p[dro + k * dyg.sz + ((s_ < nrow) ? s_ : nrow - 1) * dyg.sy];
+      }
+    }
+    if (dxg.p && (first || dxg.sz != 0)) {
+      load_rows<T, SEG>(dxr, dxg.p, dxo + k * dxg.sz, dxg.sy, dxg.sx, nrow, (ntl & 8) != 0);
+      T top[1];
+      load_rows<T, 1>(top, dxg.p, dto + k * dxg.sz, dxg.sy, dxg.sx, 1, (ntl & 8) != 0);
+      dxt = top[0];
+    }
+    if (ra.p && (first || ra.sz != 0)) load_rows<T, SEG>(rar, ra.p, rao + k * ra.sz, ra.sy, ra.sx, nrow, (ntl & 16) != 0);
+  };
+  auto lmetrics = [&](int64_t k, bool first) {
+    if (mzu.p && (first || mzu.sz != 0)) load_rows<T, SEG>(mur, mzu.p, muo + k * mzu.sz, mzu.sy, mzu.sx, nrow, (ntl & 32) != 0);
+    if (mzv.p && (first || mzv.sz != 0)) load_rows<T, SEG>(mvr, mzv.p, mvo + k * mzv.sz, mzv.sy, mzv.sx, nrow, (ntl & 64) != 0);
+  };
+  if (MET) {
+    const int64_t yo = dyg.p ? area_outer_off(dyg.ai, o) : 0, xo = dxg.p ? area_outer_off(dxg.ai, o) : 0;
+    dyo = yo + j0 * dyg.sy + i0 * dyg.sx;
+    dro = yo + j0 * dyg.sy + e.ridx * dyg.sx;
+    dxo = xo + j0 * dxg.sy + i0 * dxg.sx;
+    dto = xo + jt * dxg.sy + i0 * dxg.sx;
+    if (ra.p) rao = area_outer_off(ra.ai, o) + j0 * ra.sy + i0 * ra.sx;
+    if (mzu.p) muo = area_outer_off(mzu.ai, o) + j0 * mzu.sy + i0 * mzu.sx;
+    if (mzv.p) mvo = area_outer_off(mzv.ai, o) + j0 * mzv.sy + i0 * mzv.sx;
+    fmetrics(0, true);
+    lmetrics(0, true);
+  }
+
+  // one face: its rows (none where it is `shut`), the streamfunction into `ps`, and -- `store` -- the transports and wb
+  auto face = [&](int64_t k, bool shut, Psi& ps, bool store) {
+    const int64_t fl = fcol + k * plane;
+    T pyt;          // py of the row above the segment
+    real pxr[SEG];  // px of the column right of the lane's vector
+    if (shut) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        ps.x[s_] = ps.y[s_] = splat<T>(real(0));
+        pxr[s_] = real(0);
+      }
+      pyt = splat<T>(real(0));
+    } else {
+      T kx[SEG], ky[SEG];
+      real kl[SEG], kr[SEG];
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        kx[s_] = *reinterpret_cast<const T*>(kwx + fl + ro[s_] + i0);
+        kl[s_] = e.own_l ? kwx[fl + ro[s_] + e.lidx] : real(0);
+        kr[s_] = e.form_r ? kwx[fl + ro[s_] + e.ridx] : real(0);
+        ky[s_] = *reinterpret_cast<const T*>(kwy + fl + ro[s_] + i0);
+      }
+      const T below = *reinterpret_cast<const T*>(kwy + fl + jb * nx + i0);
+      const T above = *reinterpret_cast<const T*>(kwy + fl + jt * nx + i0);
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        real left = kl[s_];
+        if (e.shl) {
+          const real dpp = from_lane_below(vec_last(kx[s_]));  // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+          if (!e.own_l) left = dpp;
+        }
+        if (fill_l) left = fill_x;
+        ps.x[s_] = interp_left_of(kx[s_], left);
+        pxr[s_] = (vec_last(kx[s_]) + kr[s_]) * real(0.5);  // (a periodic edge: kwx[nx-1] is the pad left of column 0)
+        const T lower = (s_ == 0) ? (fill_b ? splat<T>(fill_y) : below) : ky[(s_ > 0) ? s_ - 1 : 0];
+        ps.y[s_] = op2<XG_OP_INTERP>(lower, ky[s_]);
+      }
+      pyt = op2<XG_OP_INTERP>(ky[SEG - 1], above);  // (short tails repeat the last row: ky[SEG - 1] is row nrow - 1)
+    }
+    if (!store) return;
+    if (MET && k > 0) fmetrics(k, false);
+    T tx[SEG], ty[SEG], tyt = pyt;
+    real txr[SEG];
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      tx[s_] = ps.x[s_];
+      ty[s_] = ps.y[s_];
+      txr[s_] = pxr[s_];
+    }
+    if (MET) {
+      if (dyg.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) tx[s_] = ps.x[s_] * dyr[s_];
+        if (e.own_r) {
+#pragma unroll
+          for (int s_ = 0; s_ < SEG; ++s_) txr[s_] = pxr[s_] * dyrr[s_];
+        }
+      }
+      if (dxg.p) {
+#pragma unroll
+        for (int s_ = 0; s_ < SEG; ++s_) ty[s_] = ps.y[s_] * dxr[s_];
+        tyt = pyt * dxt;
+      }
+    }
+    if (e.shl) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) {
+        const real right = from_lane_above(vec_first(tx[s_]));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+        if (!e.own_r) txr[s_] = right;
+      }
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (pad_r) txr[s_] = (bc_x == XG_BC_FILL) ? fill_x : vec_last(tx[s_]);
+      T up = (s_ + 1 < nrow) ? ty[(s_ + 1 < SEG) ? s_ + 1 : s_] : tyt;
+      if (s_ + 1 >= nrow && pad_t) up = (bc_y == XG_BC_FILL) ? splat<T>(fill_y) : ty[s_];
+      if (s_ < nrow) {
+        T z = dudx_fwd(tx[s_], txr[s_]) + (up - ty[s_]);  // (K7b's add order)
+        if (MET) {
+          if (ra.p) z = z / rar[s_];
+        }
+        stg_s<T, NTS>(out_w + fl + ro[s_] + i0, z);
+      }
+    }
+  };
+
+  const bool shut = closed != 0;
+  const T minus = splat<T>(real(-1));
+  Psi prev, cur;
+  face(0, shut, prev, true);
+  for (int64_t k = 0; k < nz; ++k) {
+    const int64_t kn = k + 1;
+    if (kn < nf) {
+      face(kn, shut && kn == nz, cur, true);  // (face nz exists at Z:outer alone: the closed bottom)
+    } else if (per_z) {
+      face(0, shut, cur, false);  // (Z:left: the pad beyond face nz-1 is face 0's, formed again -- open: its rows read again)
+    } else if (bc_z == XG_BC_FILL) {
+#pragma unroll
+      for (int s_ = 0; s_ < SEG; ++s_) cur.x[s_] = cur.y[s_] = splat<T>(fill_z);
+    } else {
+      cur = prev;
+    }
+    if (MET && k > 0) lmetrics(k, false);
+    const int64_t lv = lcol + k * plane + i0;
+#pragma unroll
+    for (int s_ = 0; s_ < SEG; ++s_) {
+      if (s_ < nrow) {
+        T du = op2<XG_OP_DIFF>(prev.x[s_], cur.x[s_]);
+        T dv_ = op2<XG_OP_DIFF>(prev.y[s_], cur.y[s_]);
+        if (MET) {
+          if (mzu.p) du = du / mur[s_];
+          if (mzv.p) dv_ = dv_ / mvr[s_];
+        }
+        stg_s<T, NTS>(out_u + lv + ro[s_], minus * du);
+        stg_s<T, NTS>(out_v + lv + ro[s_], minus * dv_);
+      }
+    }
+    prev = cur;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -3903,6 +4120,84 @@ int xg_redi_vertical_flux_divergence(int dtype, const void* a, const void* kwx, 
                                     (const float*)my, my_strides, (const float*)mc, mc_strides, (float*)out, shape, ndim, outer,
                                     closed, bc_x, (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
   return fail(XG_ERR_INVALID, "redi vertical flux divergence: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+
+// K7t's launcher: kwx and kwy at the faces of `shape`'s levels (nz faces, `outer`: nz + 1), five optional broadcast metrics
+// (met[]: mzu and mzv at the levels, dyG, dxG and rA at the faces), out_u and out_v of `shape`, out_w at the faces; one wave
+// per column, the isopycnal family's plan
+static int bolus_impl(const real* kwx, const real* kwy, const real* const met[5], const int64_t* const ms[5], real* out_u,
+                      real* out_v, real* out_w, const int64_t* shape, int ndim, int outer, int closed, int bc_x, real fill_x,
+                      int bc_y, real fill_y, int bc_z, real fill_z, void* stream) {
+  const char* name = "bolus velocity";
+  if (!kwx || !kwy || !out_u || !out_v || !out_w || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (closed != 0 && closed != 1) return fail(XG_ERR_INVALID, "%s: closed %d is neither 0 nor 1", name, closed);
+  if (shape[ndim - 3] < 1) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  VolIdx mi[5];
+  for (int k = 0; k < 5; ++k)
+    if ((rc = vol_index(&mi[k], met[k], ms[k], shape, ndim))) return rc;
+  FusedPlan p;
+  const bool al = aligned16(kwx) && aligned16(kwy) && aligned16(out_u) && aligned16(out_v) && aligned16(out_w);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  // bit 0: the lane neighbours by DPP, bits 2 .. 6: the rows of dyG, dxG, rA, mzu, mzv are aligned vectors
+  static const int bit_of[5] = {32, 64, 4, 8, 16};
+  int vnt = vec_nt_bits(1);
+  bool any = false;
+  for (int k = 0; k < 5; ++k) {
+    any = any || mi[k].p != nullptr;
+    if (p.V > 1 && mi[k].p && mi[k].sz % NV == 0 && plane_vec_ok(mi[k].p, mi[k].ai, mi[k].sy, mi[k].sx)) vnt |= bit_of[k];
+  }
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_bolus<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, kwx, kwy, out_u, out_v, out_w, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, closed, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], mi[3], mi[4], vnt); } while (0)
+#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (any) XG_N(V_, true); else XG_N(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+// One ABI entry for both element types (xg_bolus_velocity, below).
+__attribute__((visibility("hidden"))) int xg_internal_bolus_f64(
+    const double* kwx, const double* kwy, const double* const met[5], const int64_t* const ms[5], double* out_u, double* out_v,
+    double* out_w, const int64_t* shape, int ndim, int outer, int closed, int bc_x, double fill_x, int bc_y, double fill_y,
+    int bc_z, double fill_z, void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_bolus_f32(
+    const float* kwx, const float* kwy, const float* const met[5], const int64_t* const ms[5], float* out_u, float* out_v,
+    float* out_w, const int64_t* shape, int ndim, int outer, int closed, int bc_x, float fill_x, int bc_y, float fill_y, int bc_z,
+    float fill_z, void* stream);
+
+int XG_FN(xg_internal_bolus)(const real* kwx, const real* kwy, const real* const met[5], const int64_t* const ms[5], real* out_u,
+                             real* out_v, real* out_w, const int64_t* shape, int ndim, int outer, int closed, int bc_x,
+                             real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, void* stream) {
+  return bolus_impl(kwx, kwy, met, ms, out_u, out_v, out_w, shape, ndim, outer, closed, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z,
+                    stream);
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument, the fills are cast to it here
+int xg_bolus_velocity(int dtype, const void* kwx, const void* kwy, const void* mzu, const int64_t* mzu_strides, const void* mzv,
+                      const int64_t* mzv_strides, const void* dyG, const int64_t* dyG_strides, const void* dxG,
+                      const int64_t* dxG_strides, const void* rA, const int64_t* rA_strides, void* out_u, void* out_v,
+                      void* out_w, const int64_t* shape, int ndim, int outer, int closed, int bc_x, double fill_x, int bc_y,
+                      double fill_y, int bc_z, double fill_z, void* stream) {
+  const int64_t* const ms[5] = {mzu_strides, mzv_strides, dyG_strides, dxG_strides, rA_strides};
+  if (dtype == XG_T_F64) {
+    const double* const met[5] = {(const double*)mzu, (const double*)mzv, (const double*)dyG, (const double*)dxG, (const double*)rA};
+    return xg_internal_bolus_f64((const double*)kwx, (const double*)kwy, met, ms, (double*)out_u, (double*)out_v, (double*)out_w,
+                                 shape, ndim, outer, closed, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, stream);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const met[5] = {(const float*)mzu, (const float*)mzv, (const float*)dyG, (const float*)dxG, (const float*)rA};
+    return xg_internal_bolus_f32((const float*)kwx, (const float*)kwy, met, ms, (float*)out_u, (float*)out_v, (float*)out_w, shape,
+                                 ndim, outer, closed, bc_x, (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
+  }
+  return fail(XG_ERR_INVALID, "bolus velocity: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 #endif
 

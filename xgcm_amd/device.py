@@ -1329,12 +1329,13 @@ def _binary_blockwise(op: str, a, b):
 
 
 class _Plan(NamedTuple):
-    """one form of a row of _hip.FUSED, resolved for `_fused` once at import"""
+    """one form of a row of _hip.FUSED / _hip.FUSED_AT_FACES, resolved for `_fused` once at import"""
 
     names: dict      # ABI suffix -> the entry's name (a typed entry has one name and takes the `dtype` code first)
     arrays: tuple    # every array slot of the ROW: the halo slabs count towards the dtype whichever form is called
     fields: tuple    # (name, the header takes NULL)
     same: tuple      # the fields that share the shape everything else is measured against
+    base: str        # ... which is "shape", or the "faces" (then the wrapper's check returns `shape`, the levels')
     mismatch: str    # ... and the error when they do not
     metrics: tuple   # (name, name of its strides, the shape it broadcasts against, what a stride error calls it)
     halos: tuple     # (name, the dim of the last two the slab keeps)
@@ -1369,13 +1370,14 @@ def _plan(row, entry: str, halo: bool) -> _Plan:
         names={sfx: entry if row.typed else entry + "_" + sfx for sfx in ("f64", "f32")},
         arrays=tuple(s.name for s in row.slots if s.kind in ("field", "halo", "metric")),
         fields=tuple((s.name, s.null) for s in slots if s.kind == "field"), same=same,
+        base=next(s.at for s in slots if s.kind == "field" and s.name == same[0]),
         mismatch=f"{row.op}: {', '.join(same[:-1])} and {same[-1]} must have the same shape",
         metrics=tuple((s.name, s.name + "_strides", s.at, s.what) for s in slots if s.kind == "metric"),
         halos=tuple((s.name, s.dim) for s in slots if s.kind == "halo"), work=tuple(s.name for s in slots if s.kind == "work"),
         results=tuple((s.name, s.at) for s in slots if s.kind == "result"), call=tuple(call))
 
 
-_PLANS = {entry: _plan(row, entry, halo) for name, row in _hip.FUSED.items() for entry, halo in _hip.forms(name)}
+_PLANS = {entry: _plan(row, entry, halo) for name, row in _hip.ROWS.items() for entry, halo in _hip.forms(name)}
 _DTYPE_CODE = {"f64": _hip.DTYPE["float64"], "f32": _hip.DTYPE["float32"]}
 
 
@@ -1384,19 +1386,20 @@ def _fused(entry: str, v: dict, check=None):
     of include/xgcm_hip.h: a wrapper hands over its own `locals()` (names the row does not have are ignored), and what is
     made here -- results, work buffers, strides, `shape`, `ndim`, `dtype`, `stream` -- joins them under its own name.
     `check(v)`, called once the fields are placed, is the wrapper's own validation; it returns the shape of the faces of Z
-    where the row measures something against them.  Returns the result, or the tuple of them."""
-    names, arrays, fields, same, mismatch, metrics, halos, work, results, call = _PLANS[entry]
+    where the row measures something against them -- and the levels' shape where the row's fields sit at the faces
+    themselves.  Returns the result, or the tuple of them."""
+    names, arrays, fields, same, base, mismatch, metrics, halos, work, results, call = _PLANS[entry]
     lib = _MEM.lib()
     dt, sfx = _common(*[v[n] for n in arrays])
     for n, null in fields:
         if not (null and v[n] is None):
             v[n] = asdevice(v[n], dt)
-    faces = None if check is None else check(v)
+    other = None if check is None else check(v)
     first = v[same[0]]
     for n in same[1:]:
         if v[n] is not None and v[n].shape != first.shape:
             raise ValueError(mismatch)
-    shape = list(first.shape)
+    shape, faces = (other, list(first.shape)) if base == "faces" else (list(first.shape), other)
     shapes = {"shape": shape, "faces": faces}
     for n, _, _, _ in metrics:
         v[n] = _prep_metric(v[n], dt)
@@ -1412,7 +1415,7 @@ def _fused(entry: str, v: dict, check=None):
         for n, strides, at, what in metrics:
             v[strides] = _hip.i64(_bstrides(v[n], shapes[at], what))
         v["dtype"], v["shape"], v["ndim"], v["stream"] = _DTYPE_CODE[sfx], _hip.i64(shape), len(shape), _stream()
-        _check(getattr(lib, names[sfx])(*[v[n] if arg is None else arg(v[n]) for n, arg in call]))
+        _check(_hip.entry(lib, names[sfx])(*[v[n] if arg is None else arg(v[n]) for n, arg in call]))
     return outs[0] if len(outs) == 1 else tuple(outs)
 
 
@@ -1603,6 +1606,26 @@ def redi_vertical_flux_divergence(a, kwx, kwy, mx, my, mc, outer: bool, closed: 
         return faces
 
     return _fused("xg_redi_vertical_flux_divergence", locals(), check)
+
+
+def bolus_velocity(kwx, kwy, mzu, mzv, dyG, dxG, rA, outer: bool, closed: bool, bc_x: str, bc_y: str, bc_z: str,
+                   fill_x: float = 0.0, fill_y: float = 0.0, fill_z: float = 0.0):
+    """Fused Gent-McWilliams eddy-induced (bolus) velocity in one pass (xg_bolus_velocity): the means of `kwx` / `kwy` with
+    the column / row before (the streamfunction), `closed`: +0.0 at face 0 and, `outer`, at face nz, nothing read there; the
+    difference to the next face's divided by `mzu` / `mzv` and negated (ub, vb, at the levels); the streamfunction times
+    `dyG` / `dxG`, the differences of the two transports to the next column's / row's, their sum divided by `rA` (wb, at
+    the faces).  `kwx` and `kwy` have nz faces (`outer` False) or nz + 1 (True): the results of `redi_tensor`.  `mzu` and
+    `mzv` broadcast against the levels' shape, `dyG`, `dxG` and `rA` against the faces'; None = that step is absent.
+    Returns (ub, vb, wb)."""
+    def check(p):
+        faces = list(p["kwx"].shape)
+        if len(faces) < 3 or faces[-3] < 1 + bool(outer):
+            raise ValueError("bolus_velocity: the fields need (Z face, Y, X) as their last three dims and a level along Z")
+        for what in ("kwx", "kwy"):
+            p[what] = p[what].contiguous()
+        return faces[:-3] + [faces[-3] - (1 if outer else 0)] + faces[-2:]
+
+    return _fused("xg_bolus_velocity", locals(), check)
 
 
 def kinetic_energy(u, v, bc_x: str, bc_y: str, fill_x: float = 0.0, fill_y: float = 0.0) -> torch.Tensor:

@@ -2547,6 +2547,141 @@ class Grid:
         res = res._replace(data=_dev.tohost(out) if host else out)
         return to_xarray(res) if was_xr else res
 
+    def bolus_velocity(self, kwx, kwy, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z", closed: bool = True,
+                       padding=None, fill_value=None, metric_weighted: bool = True):
+        """The Gent-McWilliams eddy-induced (bolus) velocity `(ub, vb, wb)` from the two off-diagonal components of
+        `redi_tensor`, `kwx = kappa * taper * Sx` and `kwy = kappa * taper * Sy` -- the GM streamfunction at the W points
+        -- in ONE pass: `kwx` and `kwy` are read once and the three results written once (about 40 B/cell in float64,
+        against about 184 for the eleven launches of the chain).  It is what MITgcm's `gmredi_calc_psi_b` and
+        `gmredi_residual_flow` form of the same tensor column:
+
+            u* = -d/dz(kappa Sx)      v* = -d/dz(kappa Sy)      w* = d/dx(kappa Sx) + d/dy(kappa Sy)
+
+        `flux_divergence_3d(ub, vb, wb, T)` is the advective form of the GM tendency.  With different GM and Redi
+        diffusivities the caller scales `kwx` and `kwy` first; nothing is built for it.
+
+        `kwx` and `kwy` at (lead, Z face, Y:center, X:center), Z third from last: the dims and the position of
+        `redi_tensor`'s results.  The face position, Z:outer (nz + 1 faces) or Z:left (nz), is read from the inputs' own Z
+        dim.  `ub` at (lead, Z:center, Y:center, X:left), `vb` at (lead, Z:center, Y:left, X:center), `wb` at the inputs'
+        dims.  Bit-identical, dims, coords and names included, to the chain
+
+            kw   = dict(padding=padding, fill_value=fill_value)
+            step = grid.derivative if metric_weighted else grid.diff
+            px = grid.interp(kwx, x_axis, **kw)          # psi_x at (Z face, Y:center, X:left): (kwx[i-1] + kwx[i]) * 0.5
+            py = grid.interp(kwy, y_axis, **kw)          # psi_y at (Z face, Y:left, X:center)
+            if closed:                                   # psi = 0 at the top and the bottom
+                px, py = copies with face 0 -- and at Z:outer also face nz -- set to +0.0
+            ub = -step(px, z_axis, **kw)                 # -(px[k+1] - px[k]) [/ drF at u's points]
+            vb = -step(py, z_axis, **kw)
+            tx, ty = px, py
+            if metric_weighted:
+                tx = px * grid.get_metric(px, (y_axis,))         # dyG: the transport through the west face
+                ty = py * grid.get_metric(py, (x_axis,))         # dxG
+            wb = grid.divergence(tx, ty, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+
+        every operation in the fields' dtype, no fused multiply-add, IEEE quotients; the negation is a sign change, so
+        `-(+0.0)` is `-0.0`.  The pads are the chain's own: `kwx` left of column 0 and `kwy` below row 0; the TRANSPORTS
+        right of the last column and above the last row (fill: `fill_value` itself, not multiplied by a metric); at Z:left
+        only, psi beyond face nz-1 (periodic: psi[0], +0.0 when closed; extend: psi[nz-1]; fill: `fill_value`).
+
+        `closed=True`, the default, is MITgcm's condition -- no eddy transport through the top and the bottom -- and makes
+        the operator usable on `redi_tensor`'s results as they are: the closed faces' rows of `kwx` and `kwy` are never
+        read, so their NaN outermost faces under `extend` reach none of the three results.  The closed faces of `wb` are
+        still formed from psi = +0.0 through the same products, differences and quotient; with a non-zero `fill` pad on X
+        or Y the chain gives a non-zero `wb` in the last column or row of a closed face, and so does the operator.
+        `closed=False` is the plain chain.
+
+        Sign convention: `isopycnal_slope`'s, all derivatives run along increasing index, so d/dx u* + d/dy v* + d/dz w* = 0
+        holds in index space.  Discretely `divergence(ub * dyG, vb * dxG) * drF + (wb[k+1] - wb[k]) * rA` is zero to
+        rounding when drF is a profile: the eddy-induced flow is non-divergent cell by cell.  Out of scope: partial cells
+        (hFac), land masks, the U- and V-point components of the tensor, and the bolus streamfunction integrated along X.
+
+        The one pass serves the call when both inputs are unchunked labelled arrays of the same float32 or float64 dtype,
+        dims and shape, the dims are lead + (Z:left | Z:outer, Y:center, X:center) with no grid dim in lead and a level
+        along Z, both horizontal axes have `left` and `center` and the Z axis `center`, no axis has a face connection or a
+        fold, all three have a boundary, and -- `metric_weighted` -- the five metrics (Z at ub's and at vb's dims, Y at
+        px's, X at py's, (X, Y) at wb's) resolve to unchunked arrays whose dims are a subset of their stage's.  For
+        everything else the chain above itself runs, the same calls in the same order, raising what it raises; a deferred
+        or chunked psi is computed first by the closing step."""
+        args = (kwx, kwy)
+        (kwx, xr1), (kwy, xr2) = self._wrap_in(kwx), self._wrap_in(kwy)
+        was_xr = xr1 or xr2
+        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
+        to = next((pos for pos in ("outer", "left") if zax.coords.get(pos) in getattr(kwx, "dims", ())), None)
+        plan = None
+        served = (isinstance(kwx, DataArray) and isinstance(kwy, DataArray) and kwx.ndim >= 3 and to is not None
+                  and all("center" in ax.coords for ax in (zax, yax, xax)) and "left" in yax.coords and "left" in xax.coords
+                  and not gridops.complex_topology(self, z_axis))
+        if served:
+            tz, zf = zax.coords["center"], zax.coords[to]
+            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            lead = kwx.dims[:-3]
+            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
+            nz = kwx.shape[-3] - (1 if to == "outer" else 0)
+            served = (kwx.dims == lead + (zf, yc, xc) and kwy.dims == kwx.dims and tuple(kwy.shape) == tuple(kwx.shape)
+                      and not held & set(lead) and nz > 0)
+        mets = [None] * 5
+        if served:
+            l_shape = tuple(kwx.shape[:-3]) + (nz,) + tuple(kwx.shape[-2:])
+            w_dims = kwx.dims
+            # the five metrics' stages: ub's and vb's dims, px's and py's, wb's
+            m_dims = [lead + (tz, yc, xl), lead + (tz, yl, xc), lead + (zf, yc, xl), lead + (zf, yl, xc), w_dims]
+            m_axes = [(z_axis,), (z_axis,), (y_axis,), (x_axis,), (x_axis, y_axis)]
+            try:
+                if metric_weighted:
+                    for k in range(5):
+                        mets[k] = self._resident(self.get_metric(_DimsOnly(m_dims[k], kwx.name), m_axes[k], _layout=m_dims[k]), kwx.data)
+                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, m_dims))
+            except (KeyError, ValueError):
+                served = False  # (the chain raises it where the chain looks the metric up)
+        if served:
+            plan = self._second_order_plan([kwx, kwy], x_axis, y_axis, padding, fill_value, [m for m in mets if m is not None])
+        if plan is not None:
+            bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
+            fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
+            # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as it is
+            # (None: 0.0), so a -0.0 or a NaN keeps its bits on all three axes
+            fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
+            plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
+        if plan is None:
+            kwx, kwy = args
+            kw = dict(padding=padding, fill_value=fill_value)
+            step = self.derivative if metric_weighted else self.diff
+            px = self.interp(kwx, x_axis, **kw)
+            py = self.interp(kwy, y_axis, **kw)
+            if closed:
+                px = self._closed_flux(px, zax.coords.get(to), to == "outer")
+                py = self._closed_flux(py, zax.coords.get(to), to == "outer")
+            ub = -step(px, z_axis, **kw)
+            vb = -step(py, z_axis, **kw)
+            tx, ty = px, py
+            if metric_weighted:
+                tx = px * self.get_metric(px, (y_axis,))
+                ty = py * self.get_metric(py, (x_axis,))
+            wb = self.divergence(tx, ty, x_axis, y_axis, metric_weighted=metric_weighted, **kw)
+            return ub, vb, wb
+        bcx, bcy, fvx, fvy, bcz, fvz = plan
+        host = not any(_is_tensor(x.data) for x in (kwx, kwy))
+        mzu, mzv, dyg, dxg, ra = (None if m is None else _aligned_view(m, dims) for m, dims in zip(mets, m_dims))
+        outs = _dev.bolus_velocity(kwx.data, kwy.data, mzu, mzv, dyg, dxg, ra, to == "outer", bool(closed), bcx, bcy, bcz,
+                                   fvx, fvy, fvz)
+
+        # dims, coords and names as the chain's, step by step over placeholders: the two means (closing them changes neither
+        # coords nor name), the step to the centre named after its metric quotient (the negation changes neither), the
+        # transports named after their products, the divergence nameless with the coords of its two components
+        def named(g, m):
+            return g if m is None else g._replace(name=_name_after(g.name, m))
+
+        px = self._labels_of_step(kwx, m_dims[2], xl)
+        py = self._labels_of_step(kwy, m_dims[3], yl)
+        ub = named(self._labels_of_step(px, m_dims[0], tz, l_shape), mets[0])
+        vb = named(self._labels_of_step(py, m_dims[1], tz, l_shape), mets[1])
+        tx = px if mets[2] is None else self._labels_of_binary(px, mets[2])
+        ty = py if mets[3] is None else self._labels_of_binary(py, mets[3])
+        wb = _reattach_coords([DataArray(_placeholder(kwx.shape), w_dims)], self, None, {xc, yc}, [tx, ty])[0]
+        res = tuple(r._replace(data=_dev.tohost(out) if host else out) for r, out in zip((ub, vb, wb), outs))
+        return tuple(to_xarray(r) for r in res) if was_xr else res
+
     def _closed_flux(self, f, face_dim, outer):
         """a copy of the flux `f` with face 0 and (`outer`) its last face along `face_dim` set to +0.0; dims, coords and name
         stay f's.  A deferred or chunked flux is computed first; a flux without that dim passes as it is"""
