@@ -1,0 +1,1080 @@
+"""The tapered off-diagonal tensor components at the U and V points, `Grid.redi_horizontal_tensor`, on CPU.
+
+The one-pass path runs through the `host_abi` fixture (the product's `xgcm_amd.device` over libxgcm_host.so); the chain it
+replaces (the method's docstring) runs through the same Grid over the oracle double, installed AFTER the one-pass calls of a
+test have run.  `_want` states the chain a third time, over plain numpy arrays with `R.stencil1d` and `R.binary`.  Every
+comparison is bit for bit (NaN where the other has NaN, -0.0 is not +0.0), with dims, coords and names where labels are
+compared.  The one-pass device entry is counted and the chain's device functions are barred wherever a case must not pass by
+falling back.  The case builders, grids and fields are those of tests/test_isopycnal_slope.py, by import.
+
+Asserted on the REFERENCE alone, before anything is compared (`Case.solid`): for nz >= 3, or nz = 2 with Z not periodic, and
+without a planted NaN or a NaN fill, both results are finite everywhere and at least half of each result's cells are
+non-zero -- except kuz where nx = 1 and X is not `fill`, and kvz where ny = 1 and Y is not `fill`: the derivative there is
+b - b, so the result is +-0 throughout, which is asserted instead.  The remaining shapes (one level; two levels with periodic
+Z) are 0 / 0 tables by construction wherever the 4-point mean of db/dz cancels: they are compared bit for bit all the same.
+
+`Tally`: over all cases with slope_max = 2.0 of all tables taken together, each branch of the taper (s2 <= m2, s2 > m2) holds
+at least a tenth of the finite cells (`test_both_branches_of_the_taper_are_met`).
+
+The bound where tapered, |kuz|, |kvz| <= kappa * slope_max * (1 + 7 eps), for a kappa that is exact in the fields' dtype.  With s2 > m2 = M, exact arithmetic gives
+kappa * (M / s2) * |s| <= kappa * M / sqrt(s2) < kappa * sqrt(M), as |s| <= sqrt(s2).  The roundings between the slope s and
+the result: the two squares and their sum (s2 is within 2 eps below sx^2 + sy^2 at worst, i.e. |s| <= sqrt(s2) (1 + eps) to
+first order: one), `ex = s2 - m2` and `m2 + ex` (den within 2 eps of s2: two, `ex + |ex|` and `* 0.5` are exact), the
+quotient m2 / den (one), the product with kappa (one), the product with the slope (one), and m2 itself, the product
+slope_max * slope_max cast to the dtype (sqrt(m2) is within eps / 2 of slope_max: counted as one): n = 7, the length of
+`BOUND_OPERATIONS`, which `test_the_bound_where_tapered` holds to the chain's own operations and to the method's docstring."""
+
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import guarded_memory as GM
+import test_isopycnal_slope as TI
+import test_richardson_number as TR
+from oracle import refimpl as R
+from test_fused_layouts import ALIGNED, _contig, _strided
+from xgcm_amd import DataArray, _hip
+from xgcm_amd.chunked import BlockArray
+
+FILL, ZDIM, PADS3, FILLS = TI.FILL, TI.ZDIM, TI.PADS3, TI.FILLS
+SLOPE_MAXES = (None, 1e-2, 2.0)
+KAPPAS = (1000.0, 2.5, 3)        # (exact in float32; the int is a weak scalar too)
+# the roundings between the slope and a tapered result, one entry per operation of the chain that rounds (the module docstring)
+BOUND_OPERATIONS = ("s2 = sa * sa + sb * sb, against |s| = sqrt(s2): half of its two roundings", "ex = s2 - m2", "m2 + ex",
+                    "m2 / den", "kappa * (m2 / den)", "kt * pick", "m2 = slope_max * slope_max, cast: half a rounding on sqrt(m2), counted whole")
+BOUND_ROUNDINGS = len(BOUND_OPERATIONS)
+DIMS_U, DIMS_V = ("ZC", "YC", "XG"), ("ZC", "YG", "XC")
+_same_labelled, _same_bits, _same_error = TR._same_labelled, TR._same_bits, TR._same_error
+
+
+def _taper(sa, sb, pick, kappa, slope_max):
+    """redi_tensor's taper at one point, one `R.binary` per operation of the chain"""
+    B = R.binary
+    s2 = B("add", B("mul", sa, sa), B("mul", sb, sb))
+    if slope_max is None:
+        kt = kappa
+    else:
+        m2 = float(slope_max) * float(slope_max)
+        ex = B("sub", s2, m2)
+        kt = B("mul", kappa, B("div", m2, B("add", m2, B("mul", B("add", ex, np.abs(ex)), 0.5))))
+    return B("mul", kt, pick)
+
+
+def _slopes(b, pads, to, fill=FILL, mx=None, my=None, mz=None):
+    """the numpy statement up to the four slopes: (sxu, syu) at u's points, (sxv, syv) at v's"""
+    px, py, pz = pads
+    z, y, x = b.ndim - 3, b.ndim - 2, b.ndim - 1
+    hi = 1 if to == "outer" else 0
+    S, B = R.stencil1d, R.binary
+    fx, fy, fz = fill["X"], fill["Y"], fill["Z"]
+    with np.errstate(all="ignore"):
+        gx = S("diff", b, x, 1, 0, px, fx, m_out=mx)
+        gy = S("diff", b, y, 1, 0, py, fy, m_out=my)
+        bzc = S("interp", S("diff", b, z, 1, hi, pz, fz, m_out=mz), z, 0, 1 - hi, pz, fz)
+        bzu, bzv = S("interp", bzc, x, 1, 0, px, fx), S("interp", bzc, y, 1, 0, py, fy)
+        gyu = S("interp", S("interp", gy, y, 0, 1, py, fy), x, 1, 0, px, fx)
+        gxv = S("interp", S("interp", gx, x, 0, 1, px, fx), y, 1, 0, py, fy)
+        neg = lambda q: B("mul", -1, q)  # noqa: E731
+        out = neg(B("div", gx, bzu)), neg(B("div", gyu, bzu)), neg(B("div", gxv, bzv)), neg(B("div", gy, bzv))
+    assert all(o.dtype == b.dtype and o.shape == b.shape for o in out)
+    return out
+
+
+def _want(b, pads, to, fill=FILL, mx=None, my=None, mz=None, kappa=1000.0, slope_max=1e-2):
+    """the numpy statement: (kuz, kvz)"""
+    sxu, syu, sxv, syv = _slopes(b, pads, to, fill, mx, my, mz)
+    with np.errstate(all="ignore"):
+        out = _taper(sxu, syu, sxu, kappa, slope_max), _taper(sxv, syv, syv, kappa, slope_max)
+    assert all(o.dtype == b.dtype for o in out)
+    return out
+
+
+def _chain(grid, b, kappa=1000.0, slope_max=1e-2, x_axis="X", y_axis="Y", z_axis="Z", to=None, padding=None, fill_value=None,
+           metric_weighted=True):
+    """the specification"""
+    kw = dict(padding=padding, fill_value=fill_value)
+    step = grid.derivative if metric_weighted else grid.diff
+    if to is None:
+        to = "outer" if "outer" in grid.axes[z_axis].coords else "left"
+    gx = step(b, x_axis, **kw)
+    gy = step(b, y_axis, **kw)
+    bzc = grid.interp(step(b, z_axis, to=to, **kw), z_axis, to="center", **kw)
+    bzu = grid.interp(bzc, x_axis, to="left", **kw)
+    bzv = grid.interp(bzc, y_axis, to="left", **kw)
+    gyu = grid.interp(grid.interp(gy, y_axis, to="center", **kw), x_axis, to="left", **kw)
+    gxv = grid.interp(grid.interp(gx, x_axis, to="center", **kw), y_axis, to="left", **kw)
+    sxu, syu = -(gx / bzu), -(gyu / bzu)
+    sxv, syv = -(gxv / bzv), -(gy / bzv)
+    out = []
+    for sa, sb, pick in ((sxu, syu, sxu), (sxv, syv, syv)):
+        s2 = sa * sa + sb * sb
+        if slope_max is None:
+            kt = kappa
+        else:
+            m2 = float(slope_max) * float(slope_max)
+            kt = kappa * (m2 / (m2 + ((s2 - m2) + abs(s2 - m2)) * 0.5))
+        out.append(kt * pick)
+    return tuple(out)
+
+
+class Case:
+    """one call of the operator: a case of tests/test_isopycnal_slope.py (grid, b, keywords), kappa and slope_max"""
+
+    def __init__(self, base, slope_max, kappa=1000.0):
+        self.base, self.slope_max, self.kappa = base, slope_max, kappa
+        self.dims, self.to, self.nz, self.pads = base.dims, base.to, base.nz, base.pads
+
+    def __repr__(self):
+        return f"{self.base} kappa {self.kappa!r} slope_max {self.slope_max!r}"
+
+    def one_pass(self):
+        return self.base.grid.redi_horizontal_tensor(self.base.b, self.kappa, self.slope_max, **self.base.kw)
+
+    def chain(self):
+        return _chain(self.base.grid, self.base.b, self.kappa, self.slope_max, **self.base.kw)
+
+    def _args(self):
+        c = self.base
+        fill = c.kw["fill_value"] or {"X": 0.0, "Y": 0.0, "Z": 0.0}
+        mets = TI._metrics_of(c.ds, c.metric if c.kw["metric_weighted"] else None, c.to, c.dims)
+        return (c.b.values, c.pads, c.to, fill) + tuple(mets)
+
+    def slopes(self):
+        return _slopes(*self._args())
+
+    def want(self):
+        return _want(*self._args(), kappa=self.kappa, slope_max=self.slope_max)
+
+    def solid(self, want):
+        """the module docstring's conditions on the REFERENCE; returns 1 when the statement was made"""
+        c = self.base
+        fill = c.kw["fill_value"] or {}
+        nz, ny, nx = c.b.shape[-3:]
+        if c.nan or c.zero or any(np.isnan(v) for v in fill.values()) or not (nz >= 3 or (nz == 2 and c.pads[2] != "periodic")):
+            return 0
+        for w, flat in zip(want, (nx == 1 and c.pads[0] != "fill", ny == 1 and c.pads[1] != "fill")):
+            assert np.isfinite(w).all(), self
+            if flat:
+                assert (w == 0).all(), self          # the derivative is b - b: +-0 throughout
+            else:
+                assert 2 * np.count_nonzero(w) >= w.size, self
+        return 1
+
+
+def rotate(bases, shift=0):
+    """slope_max over None, 1e-2 and 2.0 and kappa over KAPPAS, rotating with the case"""
+    return [Case(c, SLOPE_MAXES[(n + shift) % 3], KAPPAS[(n // 3 + shift) % 3]) for n, c in enumerate(bases)]
+
+
+class Tally:
+    """the finite cells of the solid cases with slope_max = 2.0: how many lie below the limit and how many above it"""
+
+    def __init__(self):
+        self.below = self.above = 0
+
+    def add(self, c):
+        if c.slope_max != 2.0 or not c.solid(c.want()):
+            return
+        sxu, syu, sxv, syv = c.slopes()
+        with np.errstate(all="ignore"):
+            for s2 in (sxu * sxu + syu * syu, sxv * sxv + syv * syv):
+                s2 = s2[np.isfinite(s2)]
+                self.below += int((s2 <= 4.0).sum())
+                self.above += int((s2 > 4.0).sum())
+
+    def balanced(self):
+        n = self.below + self.above
+        assert n > 0 and 10 * self.below >= n and 10 * self.above >= n, (self.below, self.above)
+
+
+def check_properties(c, got):
+    """the consequences of the docstring on the two results `got` (numpy arrays) of a case"""
+    sxu, syu, sxv, syv = c.slopes()
+    eps = float(np.finfo(sxu.dtype).eps)
+    with np.errstate(all="ignore"):
+        for g, (sa, sb, pick) in zip(got, ((sxu, syu, sxu), (sxv, syv, syv))):
+            free = _taper(sa, sb, pick, c.kappa, None)
+            if c.slope_max is None:
+                _same_bits(g, free)
+                continue
+            s2 = sa * sa + sb * sb
+            m2 = np.asarray(float(c.slope_max) ** 2, sa.dtype)
+            low = s2 <= m2
+            _same_bits(g[low], free[low])           # exactly the untapered bits below the limit
+            high = (s2 > m2) & np.isfinite(s2)
+            bound = abs(float(c.kappa)) * float(c.slope_max) * (1 + BOUND_ROUNDINGS * eps)
+            assert (np.abs(g[high]).astype(np.float64) <= bound).all(), c
+
+
+def _counted(monkeypatch, bar_chain=True):
+    """the calls of the one-pass device entry; `bar_chain`: and those of the chain's own device functions"""
+    import xgcm_amd.device as D
+
+    calls = {"fused": 0, "chain": 0}
+
+    def counted(fn, key):
+        def wrapped(*a, **k):
+            calls[key] += 1
+            return fn(*a, **k)
+        return wrapped
+
+    monkeypatch.setattr(D, "redi_horizontal_tensor", counted(D.redi_horizontal_tensor, "fused"))
+    if bar_chain:
+        for name in ("binary", "stencil1d", "isopycnal_slope", "redi_tensor"):
+            monkeypatch.setattr(D, name, counted(getattr(D, name), "chain"))
+    return calls
+
+
+def compare_with_numpy(cases, monkeypatch=None):
+    """both results of every case against the numpy statement, bit for bit; the statement is first held to `solid` and to
+    the properties, then the operator; on whatever library `_MEM` serves.  With `monkeypatch`: exactly one call of the
+    one-pass entry per case and none of the chain's.  Returns the number of solid cases"""
+    calls = _counted(monkeypatch) if monkeypatch is not None else None
+    solid = 0
+    for c in cases:
+        want = c.want()
+        solid += c.solid(want)
+        check_properties(c, want)
+        got = c.one_pass()
+        try:
+            assert len(got) == 2
+            for g, w, dims in zip(got, want, (DIMS_U, DIMS_V)):
+                _same_bits(g.values, w)
+                assert g.dims == c.dims + dims
+            check_properties(c, [g.values for g in got])
+        except AssertionError as err:
+            raise AssertionError(f"case {c}") from err
+    if calls is not None:
+        assert calls == {"fused": len(cases), "chain": 0}
+    return solid
+
+
+def compare_with_chain(monkeypatch, cases):
+    """every one-pass call first (counted, the chain barred), then the chain over the oracle double: values, dims, coords, names"""
+    from oracle import fake_device
+
+    calls = _counted(monkeypatch)
+    got = [c.one_pass() for c in cases]
+    assert calls == {"fused": len(cases), "chain": 0}
+    fake_device.install(monkeypatch)
+    for c, pair in zip(cases, got):
+        with np.errstate(all="ignore"):
+            want = c.chain()
+        try:
+            assert len(pair) == len(want) == 2
+            for g, w in zip(pair, want):
+                _same_labelled(g, w)
+                _same_bits(g.values, w.values)
+        except AssertionError as err:
+            raise AssertionError(f"case {c}") from err
+
+
+# ---- 1. the numpy statement on its own --------------------------------------------------------------------------------------
+def test_the_statement_meets_its_own_conditions_and_the_operator_meets_the_statement(host_abi):
+    """without metrics: every boundary triple, both `to`, nz in 2, 3, 5, ny and nx down to one.  The reference alone first:
+    finite everywhere, at least half of each result non-zero, +-0 where the derivative is b - b, and the 0 / 0 tables are what
+    the docstring says they are; then the operator against it, bit for bit"""
+    made = 0
+    for (pads, to), (nz, ny, nx) in itertools.product(itertools.product(PADS3, TI.TOS), ((2, 3, 8), (3, 1, 3), (3, 2, 1), (5, 3, 2), (3, 9, 130))):
+        c = Case(TI.Case((), nz, ny, nx, np.float64, pads, to, None), 2.0)
+        want = c.want()
+        made += c.solid(want)
+        for g, w in zip(c.one_pass(), want):
+            _same_bits(g.values, w)
+    assert made == 27 * 2 * 5 - 9 * 2     # (two levels with periodic Z are no such case)
+    for pads, to, nz in itertools.product(PADS3, TI.TOS, (1, 2)):
+        zero_over_zero = (nz == 1 and (to == "outer" or pads[2] != "fill")) or (nz == 2 and pads[2] == "periodic")
+        c = Case(TI.Case((), nz, 3, 4, np.float64, pads, to, None, fill={"X": 0.0, "Y": 0.0, "Z": 0.5}), None, 1.0)
+        sxu = c.slopes()[0]
+        if zero_over_zero and "fill" not in pads[:2]:
+            assert not np.isfinite(sxu).any(), c    # bzu is exactly 0 everywhere
+        if not zero_over_zero and nz == 1:
+            assert np.isfinite(sxu).all(), c
+        _same_bits(c.one_pass()[0].values, sxu)     # (kappa = 1, untapered: the bare slope)
+
+
+# ---- 2. small shapes --------------------------------------------------------------------------------------------------------
+def shape_cases():
+    """the small shapes of tests/test_isopycnal_slope.py over NZS x NYS x NXS as ONE table, slope_max and kappa rotating"""
+    return rotate([c for nx in TI.NXS for c in TI.shape_cases(nx)])
+
+
+def test_small_shapes(host_abi, monkeypatch):
+    cases = shape_cases()
+    assert len(cases) == len(TI.NZS) * len(TI.NYS) * len(TI.NXS)
+    assert {c.slope_max for c in cases} == set(SLOPE_MAXES)
+    assert compare_with_numpy(cases) >= 15
+    share = both_branches_of_the_taper_are_met()
+    assert 0.1 <= share <= 0.9
+    compare_with_chain(monkeypatch, cases)
+
+
+# ---- 3. every boundary triple, metric forms, mid size, fills, fuzz ----------------------------------------------------------
+def matrix_cases(pads, dtype):
+    return rotate(TI.matrix_cases(pads, dtype), PADS3.index(tuple(pads)))
+
+
+@pytest.mark.parametrize("px,py,pz", PADS3)
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_every_boundary_triple(host_abi, monkeypatch, px, py, pz, dtype):
+    cases = matrix_cases((px, py, pz), dtype)
+    assert compare_with_numpy(cases) >= (1 if pz == "periodic" else 2)    # (two levels with periodic Z: 0 / 0, no such case)
+    compare_with_chain(monkeypatch, cases)
+
+
+def metric_cases(dtype):
+    return rotate(TI.metric_cases(dtype))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_metric_forms_and_leading_dims(host_abi, monkeypatch, dtype):
+    cases = metric_cases(dtype)
+    assert compare_with_numpy(cases) > 10
+    compare_with_chain(monkeypatch, cases)
+
+
+def mid_size_cases(dtype, nx):
+    return rotate(TI.mid_size_cases(dtype, nx), 2)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("nx", [515, 516])
+def test_mid_size(host_abi, monkeypatch, dtype, nx):
+    assert compare_with_numpy(mid_size_cases(dtype, nx), monkeypatch) == 2
+
+
+def fill_cases(dtype):
+    return rotate(TI.fill_cases(dtype))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_fills_keep_their_bits(host_abi, monkeypatch, dtype):
+    cases = fill_cases(dtype)
+    assert compare_with_numpy(cases, monkeypatch) == 8
+
+
+def fuzz_cases():
+    """the 120 seeded cases of tests/test_isopycnal_slope.py"""
+    return rotate(TI.fuzz_cases(), 1)
+
+
+def test_seeded_fuzz(host_abi, monkeypatch):
+    cases = fuzz_cases()
+    assert len(cases) == 120 and compare_with_numpy(cases) >= 10
+    compare_with_chain(monkeypatch, cases)
+
+
+def both_branches_of_the_taper_are_met():
+    """the reference alone, over every table the CPU and the GPU suite run, all cases with slope_max = 2.0 together: each
+    branch of the taper holds at least a tenth of the finite cells of the solid cases (called by `test_small_shapes`);
+    returns the tapered share"""
+    tables = [shape_cases()] + [matrix_cases(p, dt) for p in PADS3 for dt in (np.float64, np.float32)]
+    tables += [t(dt) for t in (metric_cases, fill_cases) for dt in (np.float64, np.float32)] + [fuzz_cases()]
+    tables += [mid_size_cases(dt, nx) for dt in (np.float64, np.float32) for nx in (515, 516)]
+    tally = Tally()
+    for table in tables:
+        for c in table:
+            tally.add(c)
+    tally.balanced()
+    share = tally.above / (tally.above + tally.below)
+    print("tapered share at slope_max 2.0:", share)
+    return share
+
+
+# ---- 4. labels, xarray ------------------------------------------------------------------------------------------------------
+def label_cases():
+    return rotate(TI.label_cases())
+
+
+def test_coords_and_names_follow_the_chain(host_abi, monkeypatch):
+    compare_with_chain(monkeypatch, label_cases())
+
+
+def test_xarray_in_xarray_out(host_abi, monkeypatch):
+    import xarray_standin
+    from oracle import fake_device
+
+    xarray_standin.install(monkeypatch)
+    import xarray as xr
+
+    c = Case(TI.Case((), 3, 4, 6, np.float64, ("periodic", "fill", "extend"), "left"), 2.0)
+    got = c.base.grid.redi_horizontal_tensor(xr.DataArray(c.base.b.values, dims=c.base.b.dims, name=c.base.b.name), c.kappa, 2.0,
+                                             **c.base.kw)
+    assert len(got) == 2 and all(type(g).__module__.split(".")[0] == "xarray" for g in got)
+    fake_device.install(monkeypatch)
+    with np.errstate(all="ignore"):
+        want = c.chain()
+    for g, w in zip(got, want):
+        assert tuple(g.dims) == tuple(w.dims) and g.name == w.name
+        _same_bits(np.asarray(g.values), np.asarray(w.values))
+
+
+def test_the_defaults_are_kappa_1000_and_slope_max_1e_2(host_abi, monkeypatch):
+    calls = _counted(monkeypatch)
+    base = TI.Case((), 3, 4, 6, np.float64, ("periodic", "fill", "extend"), "outer")
+    got = base.grid.redi_horizontal_tensor(base.b, fill_value=FILL)      # `to` None: "outer", the axis has it
+    assert calls == {"fused": 1, "chain": 0} and got[0].dims == DIMS_U and got[1].dims == DIMS_V and isinstance(got[0].data, np.ndarray)
+    for g, w in zip(got, Case(base, 1e-2, 1000.0).want()):
+        _same_bits(g.values, w)
+    got = base.grid.redi_horizontal_tensor(base.b, np.float32(4.0), np.float64(0.5), fill_value=FILL, to="outer")   # numpy scalars that do not promote
+    assert calls == {"fused": 2, "chain": 0}
+    for g, w in zip(got, Case(base, 0.5, 4.0).want()):
+        _same_bits(g.values, w)
+
+
+# ---- 5. identities ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_kappa_one_untapered_gives_the_bare_slopes(host_abi, dtype):
+    for pads, to in ((("periodic", "extend", "fill"), "left"), (("fill", "periodic", "extend"), "outer")):
+        c = Case(TI.Case((2,), 4, 5, 10, dtype, pads, to, "planes"), None, 1.0)
+        sxu, _, _, syv = c.slopes()
+        kuz, kvz = c.one_pass()
+        _same_bits(kuz.values, sxu)
+        _same_bits(kvz.values, syv)
+        assert np.isfinite(sxu).all() and (sxu != 0).any()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_a_slope_max_above_every_slope_equals_untapered(host_abi, dtype):
+    base = TI.Case((), 5, 9, 130, dtype, ("periodic", "extend", "fill"), "outer", "planes")
+    with np.errstate(all="ignore"):
+        top = max(float(np.max(np.abs(s))) for s in Case(base, None).slopes())
+    assert np.isfinite(top)
+    free, wide = Case(base, None, 2.5).one_pass(), Case(base, 2.0 * top + 1.0, 2.5).one_pass()
+    for f, w in zip(free, wide):
+        _same_bits(f.values, w.values)
+        assert (f.values != 0).any()
+
+
+def test_the_bound_where_tapered(host_abi):
+    """slopes far above the limit: every cell is tapered and the results stay under kappa * slope_max * (1 + 7 eps), and not
+    merely under it -- along the axis that carries the whole slope they come within a few percent of it.  The count is
+    derived: the taper's chain has eleven launches per point (`_taper`: three for s2, then ex, |ex|, their sum, the half, m2 +,
+    m2 /, kappa *, kt *), of which |ex|, ex + |ex| (a doubling or +0) and the half are exact and the three of s2 count once
+    against |s|; with m2's own rounding that leaves `BOUND_OPERATIONS`, and the method's docstring states the same number"""
+    import inspect
+
+    from xgcm_amd import Grid
+
+    launches = inspect.getsource(_taper).count('B("')
+    exact = 3       # |ex| is np.abs (no launch of B), ex + |ex| and * 0.5 are exact; s2's three launches count as one
+    assert launches == 10 and launches - exact - 2 + 1 + 1 == BOUND_ROUNDINGS == 7   # (-2: s2's three as one; +1: np.abs is no B; +1: m2)
+    assert f"(1 + {BOUND_ROUNDINGS} eps)" in Grid.redi_horizontal_tensor.__doc__
+    for dtype in (np.float64, np.float32):
+        base = TI.Case((), 5, 9, 136, dtype, ("periodic", "extend", "fill"), "left", None)
+        v = base.b.values
+        base.b = base.b._replace(data=(v * dtype(1e3) + np.arange(5, dtype=dtype)[:, None, None] * dtype(4)).astype(dtype))
+        c = Case(base, 0.75, 1000.0)
+        sxu, syu, sxv, syv = c.slopes()
+        assert ((sxu * sxu + syu * syu)[1:4] > 0.5625).mean() > 0.9
+        got = [g.values for g in c.one_pass()]
+        for g, w in zip(got, c.want()):
+            _same_bits(g, w)
+        check_properties(c, got)
+        assert np.nanmax(np.abs(got[0])) > 0.9 * 750.0 and np.nanmax(np.abs(got[1])) > 0.9 * 750.0
+
+
+NAN_AT = TI.NAN_AT
+
+
+@pytest.mark.parametrize("slope_max", [2.0, None])
+@pytest.mark.parametrize("to", TI.TOS)
+@pytest.mark.parametrize("pads", [("periodic", "periodic", "periodic"), ("extend", "fill", "fill"), ("fill", "extend", "extend")],
+                         ids=lambda p: "-".join(p))
+def test_a_nan_poisons_exactly_what_the_statement_has_as_nan(host_abi, to, pads, slope_max):
+    for at in NAN_AT:
+        c = Case(TI.Case((), 5, 6, 8, np.float64, pads, to, "planes"), slope_max)
+        clean = c.want()
+        c.base.b.values[at] = np.nan
+        got, want = c.one_pass(), c.want()
+        for g, w, w0 in zip(got, want, clean):
+            assert np.array_equal(np.isnan(g.values), np.isnan(w)), (c, at)
+            assert np.isnan(g.values).any() and not np.isnan(g.values).all() and not np.isnan(w0).any()
+        if at == NAN_AT[-1]:
+            # the middle of the volume: db/dz at the point reaches levels k-1 .. k+1 and both cells beside the point; the
+            # point's own derivative the level itself; the taper reads the cross mean too (2 x 3 cells of the level)
+            k, j, i = at
+            mu, mv = np.zeros(got[0].shape, bool), np.zeros(got[0].shape, bool)
+            mu[k - 1:k + 2, j, i:i + 2] = True
+            mv[k - 1:k + 2, j:j + 2, i] = True
+            mu[k, j - 1:j + 2, i:i + 2] = True      # gyu: rows j-1 .. j+1 of columns i, i+1
+            mv[k, j:j + 2, i - 1:i + 2] = True      # gxv
+            if slope_max is None:                   # kuz = kappa * sxu: the cross mean is not read
+                mu[k, [j - 1, j + 1], i:i + 2] = False
+                mv[k, j:j + 2, [i - 1, i + 1]] = False
+            assert np.array_equal(np.isnan(got[0].values), mu) and np.array_equal(np.isnan(got[1].values), mv), (c, at)
+
+
+# ---- 6. every fallback of the docstring takes the chain ---------------------------------------------------------------------
+def _no_fused(monkeypatch):
+    import xgcm_amd.device as D
+
+    monkeypatch.setattr(D, "redi_horizontal_tensor", lambda *a, **k: pytest.fail("one-pass entry called"))
+
+
+def _fallback_equals_chain(grid, b, *scalars, **kw):
+    with np.errstate(all="ignore"):
+        got, want = grid.redi_horizontal_tensor(b, *scalars, **kw), _chain(grid, b, *scalars, **kw)
+    assert len(got) == len(want) == 2
+    for g, w in zip(got, want):
+        _same_labelled(g, w)
+
+
+def _does_what_the_chain_does(grid, b, *scalars, **kw):
+    """equal to the chain where the chain runs, and the chain's error where it raises"""
+    try:
+        with np.errstate(all="ignore"):
+            _chain(grid, b, *scalars, **kw)
+    except Exception:
+        _same_error(lambda: grid.redi_horizontal_tensor(b, *scalars, **kw), lambda: _chain(grid, b, *scalars, **kw), own=())
+    else:
+        _fallback_equals_chain(grid, b, *scalars, **kw)
+
+
+def _case(pads=("periodic", "extend", "fill"), lead=(), nz=3, ny=5, nx=6, dtype=np.float64, to="outer", metric="planes", **kw):
+    return TI.Case(lead, nz, ny, nx, dtype, pads, to, metric, **kw)
+
+
+def test_an_array_kappa_runs_the_chain(host_abi, monkeypatch):
+    _no_fused(monkeypatch)
+    c = _case(lead=(2,))
+    profile = DataArray(np.linspace(500.0, 1500.0, 3), ("ZC",), name="kappa")
+    for sm in (2.0, None):
+        _fallback_equals_chain(c.grid, c.b, profile, sm, fill_value=FILL)
+    _fallback_equals_chain(c.grid, c.b, np.full((2, 3, 5, 6), 7.0), 2.0, fill_value=FILL)
+
+
+def test_a_wider_numpy_scalar_runs_the_chain(host_abi, monkeypatch):
+    _no_fused(monkeypatch)
+    c = _case(dtype=np.float32)
+    _fallback_equals_chain(c.grid, c.b, np.float64(1000.0), 2.0, fill_value=FILL)      # promotes the float32 fields
+    _fallback_equals_chain(c.grid, c.b, 1000.0, np.float64(2.0), fill_value=FILL)      # (float() of it: the same values)
+    with np.errstate(all="ignore"):
+        wide = c.grid.redi_horizontal_tensor(c.b, np.float64(1000.0), 2.0, fill_value=FILL)
+    assert all(np.asarray(w.values).dtype == np.float64 for w in wide)
+
+
+@pytest.mark.parametrize("dtype", [np.int64, np.int32, np.float16])
+def test_integer_and_half_fields_run_the_chain(backend, monkeypatch, dtype):
+    _no_fused(monkeypatch)
+    c = _case()
+    b = DataArray((c.b.values * 100).astype(dtype), c.b.dims, name="b")
+    _fallback_equals_chain(c.grid, b)
+    _fallback_equals_chain(c.grid, b, 2.5, None, metric_weighted=False, fill_value=FILL, to="left")
+
+
+def test_a_chunked_b_runs_the_chain(backend, monkeypatch):
+    _no_fused(monkeypatch)
+    c = _case(lead=(4,), ny=6, nx=8)
+    b = DataArray(BlockArray.from_array(c.b.values, ((2, 2), (3,), (6,), (8,))), c.b.dims, name="b")
+    with np.errstate(all="ignore"):
+        got, want = c.grid.redi_horizontal_tensor(b, 1000.0, 2.0, fill_value=FILL), _chain(c.grid, b, 1000.0, 2.0, fill_value=FILL)
+    for g, w, p in zip(got, want, Case(c, 2.0).want()):
+        assert g.dims == w.dims and g.name == w.name
+        assert np.array_equal(np.asarray(g.values), np.asarray(w.values), equal_nan=True)
+        assert np.array_equal(np.asarray(g.values), p, equal_nan=True)
+
+
+def test_b_elsewhere_or_z_elsewhere_does_what_the_chain_does(backend, monkeypatch):
+    _no_fused(monkeypatch)
+    c = _case(lead=(2,))
+    for dims in (("time", "ZC", "YC", "XG"), ("time", "ZC", "YG", "XC")):
+        _does_what_the_chain_does(c.grid, DataArray(c.b.values, dims, name="b"), 1000.0, 2.0, fill_value=FILL, metric_weighted=False)
+    _fallback_equals_chain(c.grid, c.b.transpose("ZC", "time", "YC", "XC"), 1000.0, 2.0, fill_value=FILL)
+    _fallback_equals_chain(c.grid, c.b.transpose("time", "YC", "ZC", "XC"), 2.5, None, fill_value=FILL, metric_weighted=False)
+
+
+@pytest.mark.parametrize("conn", ["x2x", "y2y", "z2z"])
+def test_connected_faces_run_the_chain(backend, monkeypatch, conn):
+    from test_topology import COORDS, X_TO_X
+    from xgcm_amd import Dataset, Grid
+
+    _no_fused(monkeypatch)
+    ds = Dataset({"drC": (("zo",), R.synthetic_metric((5,), 63)), "dxC": (("y", "xl"), R.synthetic_metric((4, 4), 61)),
+                  "dyC": (("yl", "x"), R.synthetic_metric((4, 4), 62))},
+                 coords={"x": np.arange(4), "xl": np.arange(4) - 0.5, "y": np.arange(4), "yl": np.arange(4) - 0.5,
+                         "face": np.arange(2), "zc": np.arange(4) + 0.5, "zo": np.arange(5) * 1.0})
+    grid = Grid(ds, coords=dict(COORDS, Z={"center": "zc", "outer": "zo"}), metrics={("X",): ["dxC"], ("Y",): ["dyC"], ("Z",): ["drC"]},
+                face_connections={"x2x": X_TO_X, "y2y": TR.Y_TO_Y, "z2z": TR.Z_TO_Z}[conn],
+                padding={"X": "fill", "Y": "extend", "Z": "fill"}, autoparse_metadata=False)
+    b = DataArray(R.synthetic_field((2, 4, 4, 4), 81), ("face", "zc", "y", "x"), name="f")
+    for mw in (True, False):
+        _fallback_equals_chain(grid, b, 1000.0, 2.0, fill_value=FILL, metric_weighted=mw)
+
+
+def test_a_missing_boundary_along_z_raises_the_chains_error(backend, monkeypatch):
+    _no_fused(monkeypatch)
+    grid, ds, dims = TI._grid((), 3, 5, 6, np.float64, {"X": "periodic", "Y": "extend"})
+    b = TI._field((), 3, 5, 6, np.float64, dims)
+    _same_error(lambda: grid.redi_horizontal_tensor(b, 1000.0, 2.0), lambda: _chain(grid, b, 1000.0, 2.0))
+
+
+def test_another_to_does_what_the_chain_does(backend, monkeypatch):
+    _no_fused(monkeypatch)
+    c = _case()
+    for to in ("right", "center"):
+        _does_what_the_chain_does(c.grid, c.b, to=to, fill_value=FILL)
+
+
+def _equal_values_and_labels(grid, b, want_values=None, **kw):
+    """a chunked input or metric: the fallback's results against the chain's (dims, names, values) and, where given, numpy's"""
+    with np.errstate(all="ignore"):
+        got, want = grid.redi_horizontal_tensor(b, 1000.0, 2.0, **kw), _chain(grid, b, 1000.0, 2.0, **kw)
+    assert len(got) == len(want) == 2
+    for n, (g, w) in enumerate(zip(got, want)):
+        assert g.dims == w.dims and g.name == w.name
+        assert np.array_equal(np.asarray(g.values), np.asarray(w.values), equal_nan=True)
+        if want_values is not None:
+            assert np.array_equal(np.asarray(g.values), want_values[n], equal_nan=True)
+
+
+def test_mixed_dtypes_run_the_chain(backend, monkeypatch):
+    _no_fused(monkeypatch)
+    grid, ds, dims = TI._grid((), 3, 5, 6, np.float32, {"X": "fill", "Y": "periodic", "Z": "extend"}, mdtype=np.float64)
+    _does_what_the_chain_does(grid, TI._field((), 3, 5, 6, np.float32, dims), 1000.0, 2.0, fill_value=FILL)   # float32 over float64 metrics
+
+
+def test_fewer_than_three_dims_do_what_the_chain_does(backend, monkeypatch):
+    _no_fused(monkeypatch)
+    c = _case(lead=(2,))
+    plane = DataArray(np.ascontiguousarray(c.b.values[0, 0]), ("YC", "XC"), name="b")   # no Z dim at all
+    _does_what_the_chain_does(c.grid, plane, 1000.0, 2.0, metric_weighted=False)
+    column = DataArray(np.ascontiguousarray(c.b.values[0, :, 0, 0]), ("ZC",), name="b")
+    _does_what_the_chain_does(c.grid, column, 1000.0, 2.0, metric_weighted=False, fill_value=FILL)
+
+
+@pytest.mark.parametrize("to", ["inner", "nowhere"])
+def test_other_targets_do_what_the_chain_does(backend, monkeypatch, to):
+    _no_fused(monkeypatch)
+    c = _case()
+    _does_what_the_chain_does(c.grid, c.b, to=to, fill_value=FILL)
+
+
+def test_a_position_the_axis_lacks_does_what_the_chain_does(backend, monkeypatch):
+    from xgcm_amd import Dataset, Grid
+
+    _no_fused(monkeypatch)
+    c = _case(to="left")
+    axes = dict(TI.AXES, Z={"center": "ZC", "left": "ZL"})
+    ds = Dataset({k: (c.ds[k].dims, np.asarray(c.ds[k].values)) for k in ("dxC", "dyC", "drCl")},
+                 {k: v for k, v in c.ds.coords.items() if k != "ZO"})
+    g2 = Grid(ds, coords=axes, metrics={("X",): ["dxC"], ("Y",): ["dyC"], ("Z",): ["drCl"]}, padding=dict(zip("XYZ", c.pads)),
+              autoparse_metadata=False)
+    _does_what_the_chain_does(g2, c.b, to="outer")
+
+
+def test_a_chunked_metric_runs_the_chain(backend, monkeypatch):
+    from xgcm_amd import Dataset, Grid
+
+    _no_fused(monkeypatch)
+    c = _case(nz=4, metric="full", to="left")
+    coords = {k: (k, np.asarray(c.ds.coords[k].values)) for k in ("XC", "XG", "YC", "YG", "ZC", "ZL", "ZO")}
+    for chunked in ("hx", "hy", "hzl"):
+        data = {k: (c.ds[k].dims, BlockArray.from_array(np.asarray(c.ds[k].values), ((2, 2), (5,), (6,))) if k == chunked
+                    else np.asarray(c.ds[k].values)) for k in ("hx", "hy", "hzl")}
+        g2 = Grid(Dataset(data, coords), coords=TI.AXES, metrics={("X",): ["hx"], ("Y",): ["hy"], ("Z",): ["hzl"]},
+                  padding=dict(zip("XYZ", c.pads)), autoparse_metadata=False)
+        _equal_values_and_labels(g2, c.b, Case(c, 2.0).want(), to="left", fill_value=FILL)
+
+
+@pytest.mark.parametrize("axis", ["X", "Y", "Z"])
+def test_a_metric_with_an_extra_dim_runs_the_chain(backend, monkeypatch, axis):
+    from xgcm_amd import Dataset, Grid
+
+    _no_fused(monkeypatch)
+    c = _case()
+    coords = {k: (k, np.asarray(c.ds.coords[k].values)) for k in ("XC", "XG", "YC", "YG", "ZC", "ZL", "ZO")}
+    coords["time"] = ("time", np.arange(2) * 2.0)
+    data = {k: (c.ds[k].dims, np.asarray(c.ds[k].values)) for k in ("dxC", "dyC", "drCo")}
+    name = {"X": "dxC", "Y": "dyC", "Z": "drCo"}[axis]
+    dims = data[name][0]
+    data[name] = (dims + ("time",), R.synthetic_metric(tuple(len(coords[d][1]) for d in dims) + (2,), 66))
+    g2 = Grid(Dataset(data, coords), coords=TI.AXES, metrics={("X",): ["dxC"], ("Y",): ["dyC"], ("Z",): ["drCo"]},
+              padding=dict(zip("XYZ", c.pads)), autoparse_metadata=False)
+    _does_what_the_chain_does(g2, c.b, 1000.0, 2.0, fill_value=FILL)
+    _does_what_the_chain_does(g2, c.b, 2.5, None, fill_value=FILL)
+
+
+@pytest.mark.parametrize("missing", ["X", "Y", "Z", "all"])
+def test_a_missing_metric_raises_the_chains_error(backend, monkeypatch, missing):
+    from xgcm_amd import Grid
+
+    _no_fused(monkeypatch)
+    c = _case()
+    names = {"X": ["dxC"], "Y": ["dyC"], "Z": ["drCl", "drCo"]}
+    g2 = Grid(c.ds, coords=TI.AXES, metrics={(ax,): v for ax, v in names.items() if ax != missing and missing != "all"},
+              padding=dict(zip("XYZ", c.pads)), autoparse_metadata=False)
+    _same_error(lambda: g2.redi_horizontal_tensor(c.b), lambda: _chain(g2, c.b))
+
+
+def test_a_missing_metric_is_still_served_unweighted(host_abi, monkeypatch):
+    base = _case(metric=None)
+    base.kw["metric_weighted"] = False
+    compare_with_chain(monkeypatch, [Case(base, 2.0), Case(base, None, 2.5)])
+
+
+@pytest.mark.parametrize("axis", ["X", "Y", "Z"])
+def test_an_axis_without_a_boundary_raises_the_chains_error(backend, monkeypatch, axis):
+    _no_fused(monkeypatch)
+    pad = {"X": "periodic", "Y": "extend", "Z": "fill"}
+    del pad[axis]
+    grid, ds, dims = TI._grid((), 3, 5, 6, np.float64, pad)
+    b = TI._field((), 3, 5, 6, np.float64, dims)
+    _same_error(lambda: grid.redi_horizontal_tensor(b, 1000.0, 2.0), lambda: _chain(grid, b, 1000.0, 2.0))
+
+
+def test_a_field_without_a_level_does_what_the_chain_does(backend, monkeypatch):
+    _no_fused(monkeypatch)
+    c = _case()
+    b = DataArray(np.zeros((0, 5, 6)), c.b.dims, name="b")
+    for to in ("left", "outer"):
+        _does_what_the_chain_does(c.grid, b, 1000.0, 2.0, fill_value=FILL, metric_weighted=False, to=to)
+
+
+def test_fold_grid_runs_the_chain(backend, monkeypatch):
+    import warnings
+
+    from test_topology import Nx, Ny
+    from xgcm_amd import Dataset, Grid
+
+    _no_fused(monkeypatch)
+    ds = Dataset({"drC": (("zo",), R.synthetic_metric((3,), 63))},
+                 coords={"xh": np.arange(Nx), "xl": np.arange(Nx), "yh": np.arange(Ny), "yl": np.arange(Ny),
+                         "zc": np.arange(2) + 0.5, "zo": np.arange(3) * 1.0})
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)
+        grid = Grid(ds, coords={"X": {"center": "xh", "left": "xl"}, "Y": {"center": "yh", "left": "yl"},
+                                "Z": {"center": "zc", "outer": "zo"}}, metrics={("Z",): ["drC"]},
+                    padding={"X": "periodic", "Y": {"fold": "corner"}, "Z": "fill"}, autoparse_metadata=False)
+        b = DataArray(R.synthetic_field((2, Ny, Nx), 91), ("zc", "yh", "xh"))
+        _does_what_the_chain_does(grid, b, 1000.0, 2.0, metric_weighted=False)
+        _does_what_the_chain_does(grid, b, 2.5, None, metric_weighted=False)
+
+
+def test_isopycnal_slope_and_redi_tensor_are_what_they_were(host_abi, monkeypatch):
+    """the operators that share their plan with this one: still one call of their own entry, none of this one's"""
+    import test_redi_tensor as TT
+
+    _no_fused(monkeypatch)
+    TI.compare_with_numpy(TI.metric_cases(np.float64), monkeypatch)
+    TT.compare_with_numpy(TT.metric_cases(np.float64))
+
+
+# ---- 7. the entry of the C ABI called directly, with views ------------------------------------------------------------------
+ABI_TENSOR = [(1000.0, 4.0, 1), (2.5, 0.0, 0)]   # (kappa, slope_max2, taper) by the parity of the table's row
+
+
+def _abi_call(D, dtype, shape, b, planes, k, offs=(ALIGNED, ALIGNED)):
+    """one call of xg_redi_horizontal_tensor: `b` a view, `planes` {mx, my, mz} views; each result is written `offs[n]`
+    elements into an allocation of its own full of SENTINEL, which must still surround it afterwards"""
+    (px, py, pz), to = TR.ABI_PADS[k]
+    kappa, m2, taper = ABI_TENSOR[k % 2]
+    fshape = shape[:-3] + [TR._nf(shape[-3], to)] + shape[-2:]
+    args = [TR.CODE[dtype], b.data_ptr()]
+    for name, against in (("mx", shape), ("my", shape), ("mz", fshape)):
+        m = planes.get(name)
+        if m is None:
+            args += [None, None]
+        else:
+            assert all(n in (1, s) for n, s in zip(m.shape, against))
+            args += [m.data_ptr(), _hip.i64([0 if n == 1 else m.stride(d) for d, n in enumerate(m.shape)])]
+    args += [kappa, m2, taper]
+    n = int(np.prod(shape))
+    bufs = [torch.full((off + n + ALIGNED,), TR.SENTINEL, dtype=TR.TORCH[dtype], device=D._MEM.device) for off in offs]
+    args += [buf[off:off + n].data_ptr() for buf, off in zip(bufs, offs)]
+    args += [_hip.i64(shape), len(shape), int(to == "outer"), _hip.BC[px], FILL["X"], _hip.BC[py], FILL["Y"], _hip.BC[pz], FILL["Z"]]
+    D._check(_hip.entry(D._MEM.lib(), "xg_redi_horizontal_tensor")(*args, D._stream()))
+    res = []
+    for buf, off in zip(bufs, offs):
+        whole = buf.cpu().numpy()
+        assert (whole[:off] == TR.SENTINEL).all() and (whole[off + n:] == TR.SENTINEL).all()
+        res.append(whole[off:off + n].reshape(shape))
+    return res
+
+
+def abi_layout_cases(dtype):
+    """Runs the direct-ABI table on whatever library `xgcm_amd.device._MEM` serves.  Every input view lives in a NaN-filled
+    allocation, so a read outside it shows in the results; the contiguous, aligned control of each set of planes is compared
+    with the numpy statement, every other layout with that control.  Result offsets: 0, 16 bytes and one element."""
+    import xgcm_amd.device as D
+
+    shape = [2, 5, 7, TR.ABI_NX[dtype]]
+    lead, nz, ny, nx = shape
+    bv = R.synthetic_field(tuple(shape), 101).astype(dtype)
+    bv.reshape(-1)[5::97] = np.nan
+    put = lambda a, st=None, off=ALIGNED: _strided(D, a, st or _contig(a.shape), off)  # noqa: E731
+    same = lambda got, want: [_same_bits(g, w) for g, w in zip(got, want)]  # noqa: E731
+    sixteen = 16 // np.dtype(dtype).itemsize
+    A = ALIGNED
+    for k, ((px, py, pz), to) in enumerate(TR.ABI_PADS):
+        kappa, m2, taper = ABI_TENSOR[k % 2]
+        nf = TR._nf(nz, to)
+        levels = {"mx": nz, "my": nz, "mz": nf}
+        form = lambda f, n: {"z": (1, n, 1, 1), "p": (1, 1, ny, nx), "v3": (1, n, ny, nx), "vl": (lead, n, ny, nx)}[f]  # noqa: E731
+        val = lambda name, f: R.synthetic_metric(form(f, levels[name]), 111 + "zpv3vl".index(f) + ord(name[1])).astype(dtype)  # noqa: E731
+        b = put(bv)
+        assert b.is_contiguous() and b.data_ptr() % 16 == 0
+        for present in ({"mx": "p"}, {"my": "p"}, {"mz": "z"}, {"mx": "p", "my": "p", "mz": "z"}, {"mx": "v3", "my": "vl", "mz": "v3"},
+                        {"mx": "vl", "my": "z", "mz": "p"}, {"mx": "z", "my": "v3", "mz": "vl"}, {}):
+            pv = {n: val(n, f) for n, f in present.items()}
+            aligned = {n: put(a) for n, a in pv.items()}
+            control = _abi_call(D, dtype, shape, b, aligned, k)
+            want = _want(bv, (px, py, pz), to, FILL, pv.get("mx"), pv.get("my"), pv.get("mz"), kappa, np.sqrt(m2) if taper else None)
+            assert control[0].dtype == want[0].dtype == np.dtype(dtype)
+            same(control, want)
+            assert not np.isnan(want[0]).all() and np.isfinite(want[1]).any() and (want[0] != want[1]).any()
+            views = [(put(bv, off=1), aligned, (A, A))]     # b one element in: the narrow form
+            assert views[0][0].data_ptr() % 16 == np.dtype(dtype).itemsize
+            views += [(b, aligned, offs) for offs in ((0, 0), (sixteen, sixteen), (1, A), (A, 1), (1, 1), (0, sixteen))]
+            # the planes one element in; with an odd row pitch; with an odd level pitch (volumes)
+            views.append((b, {n: put(a, off=1) for n, a in pv.items()}, (A, A)))
+            pitched = {}
+            for n, a in pv.items():
+                s = list(a.shape)
+                pitched[n] = put(a, _contig(s[:-1] + [s[-1] + 1]) if s[-1] > 1 else _contig(s))
+                assert s[-1] == 1 or (pitched[n].stride(-2) == nx + 1 and pitched[n].stride(-1) == 1)
+            views.append((b, pitched, (A, A)))
+            for n, f in present.items():
+                a, nl = pv[n], levels[n]
+                if f in ("v3", "vl"):
+                    st = [(nl * (ny * nx + 1)) * (a.shape[0] > 1), ny * nx + 1, nx, 1]
+                    lev = put(a, [s or 1 for s in st])
+                    assert lev.stride(1) == ny * nx + 1
+                    views.append((b, dict(aligned, **{n: lev}), (A, A)))
+                if f == "z":   # the Z-only metric three elements apart
+                    views.append((b, dict(aligned, **{n: put(a, [3 * nl, 3, 1, 1], 1)}), (A, A)))
+                if f == "p":   # the plane stored (X, Y): a transposed view
+                    t = put(np.ascontiguousarray(a.transpose(0, 1, 3, 2))).permute(0, 1, 3, 2)
+                    assert t.stride(-1) == ny and t.stride(-2) == 1
+                    views.append((b, dict(aligned, **{n: t}), (A, A)))
+            for b_, planes, offs in views:
+                same(_abi_call(D, dtype, shape, b_, planes, k, offs), control)
+        # stride-0 metrics along X and Y: one value per level, expanded over the whole volume, equal the Z-only metrics
+        flat = {n: put(val(n, "z")).expand(1, levels[n], ny, nx) for n in levels}
+        assert all(m.stride(-1) == 0 and m.stride(-2) == 0 for m in flat.values())
+        full = {n: put(np.ascontiguousarray(np.broadcast_to(val(n, "z"), (1, levels[n], ny, nx)))) for n in levels}
+        same(_abi_call(D, dtype, shape, b, flat, k), _abi_call(D, dtype, shape, b, full, k))
+    assert nx % TR.NVS[dtype] == 0 and len(TR.ABI_PADS) >= 2
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_abi_layouts(host_abi, dtype):
+    abi_layout_cases(dtype)
+
+
+def abi_bad_calls():
+    """bad calls return an error code, write nothing and leave the process alone; runs on whatever library `_MEM` serves.
+    The refusals are xg_redi_tensor's"""
+    import xgcm_amd.device as D
+
+    fn = _hip.entry(D._MEM.lib(), "xg_redi_horizontal_tensor")
+    shape = [2, 3, 4]
+    t = torch.ones(shape, dtype=torch.float64, device=D._MEM.device)
+    outs = [torch.full(shape, TR.SENTINEL, dtype=torch.float64, device=D._MEM.device) for _ in range(2)]
+    long = torch.full([2 * 36], TR.SENTINEL, dtype=torch.float64, device=D._MEM.device)
+    P = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+
+    def call(code=TR.CODE[np.float64], b=t, o=outs, shape=shape, ndim=3, outer=0, bcx=_hip.BC["periodic"], bcy=_hip.BC["extend"],
+             bcz=_hip.BC["fill"], mets=(None, None, None), strides=(None, None, None), taper=1):
+        margs = [x for pair in zip(mets, strides) for x in pair]
+        return fn(code, P(b), *margs, 1000.0, 4.0, taper, P(o[0]), P(o[1]), None if shape is None else _hip.i64(shape), ndim, outer,
+                  bcx, 0.0, bcy, 0.0, bcz, 0.0, D._stream())
+
+    untouched = lambda: all(bool((o == TR.SENTINEL).all()) for o in outs + [long])  # noqa: E731
+    for code in (-1, _hip.DTYPE["float16"], _hip.DTYPE["int64"], _hip.DTYPE["int32"], 12, 99):
+        assert call(code=code) == -1                              # any other element type: XG_ERR_INVALID
+    assert call(b=None) == -1 and call(shape=None) == -1          # NULL arguments
+    for k in range(2):                                            # a NULL result, each of the two
+        assert call(o=[None if j == k else outs[j] for j in range(2)]) == -1
+    assert call(taper=2) == -1 and call(taper=-1) == -1           # the taper flag
+    assert call(bcx=7) == -1 and call(bcy=-1) == -1 and call(bcz=9) == -1           # unknown boundary codes
+    assert call(outer=2) == -1 and call(outer=-1) == -1           # unknown face position
+    assert call(shape=[0, 3, 4]) == -1                            # nz = 0: no level to pad from
+    for k in range(3):                                            # a metric without strides, each of the three
+        assert call(mets=tuple(t.data_ptr() if j == k else None for j in range(3))) == -1
+    # results that overlap: the same array twice; one result beginning inside the other (24 elements each here)
+    assert call(o=[outs[0], outs[0]]) == -1
+    assert call(o=[long[0:24], long[23:47]]) == -1 and call(o=[long[30:54], long[8:32]]) == -1
+    assert call(ndim=2) < 0 and call(ndim=2) != -1                # XG_ERR_UNSUPPORTED
+    assert untouched()
+    assert call(shape=[2, 0, 4]) == 0 and call(shape=[2, 3, 0]) == 0 and untouched()   # an empty plane: nothing to do
+    assert call(o=[long[0:24], long[24:48]]) == 0                 # results end to end do not overlap
+    assert call() == 0 and call(bcz=_hip.BC["periodic"], outer=1, taper=0) == 0 and call(bcz=_hip.BC["extend"], outer=1) == 0
+    assert not any(bool((o == TR.SENTINEL).any()) for o in outs)
+
+
+def test_abi_refuses_bad_calls(host_abi):
+    abi_bad_calls()
+
+
+def test_empty_results_return_without_a_launch(host_abi, monkeypatch):
+    import xgcm_amd.device as D
+
+    monkeypatch.setattr(D, "_check", lambda rc: pytest.fail("the library was called for an empty result"))
+    for shape in ((2, 3, 0, 4), (0, 3, 5, 4), (3, 5, 0)):
+        outs = D.redi_horizontal_tensor(np.zeros(shape), None, None, None, 1000.0, 4.0, True, "periodic", "fill", "extend")
+        assert len(outs) == 2 and all(tuple(o.shape) == shape and o.numel() == 0 for o in outs)
+
+
+def test_the_device_wrapper_refuses_a_field_without_a_level(host_abi):
+    import xgcm_amd.device as D
+
+    with pytest.raises(ValueError, match="a level along Z"):
+        D.redi_horizontal_tensor(np.zeros((4, 6)), None, None, None, 1000.0, 4.0, True, "periodic", "fill", "extend")
+    with pytest.raises(ValueError, match="a level along Z"):
+        D.redi_horizontal_tensor(np.zeros((0, 4, 6)), None, None, None, 1000.0, None, False, "periodic", "fill", "extend")
+
+
+def ext_prototypes():
+    """name -> (return type, [(type, parameter name), ...]) of every prototype of include/xgcm_hip_ext.h, read as
+    tests/test_host_logic.py reads include/xgcm_hip.h"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "include", "xgcm_hip_ext.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    protos = {}
+    for ret, name, params in re.findall(r"^\s*((?:int|void)\s*\*?)\s*(xg_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        pairs = []
+        for q in [q.strip() for q in params.split(",") if q.strip() not in ("", "void")]:
+            ctype, pname = re.fullmatch(r"(.*?)(\w+)", q, flags=re.S).groups()
+            pairs.append((re.sub(r"\bconst\b|\bstruct\b|\s+", "", ctype), pname))
+        protos[name] = (ret.replace(" ", ""), pairs)
+    return protos
+
+
+def test_the_extension_header_its_table_and_both_libraries_agree():
+    """include/xgcm_hip_ext.h declares exactly the entries of `_hip.EXT_SIGNATURES`, whatever their number; none of them is in
+    `_hip.SIGNATURES` or `_hip.GM_SIGNATURES` (the export lists of the two other headers); each is bound parameter by
+    parameter as the header has it, the row names its slots as the header names the parameters, `_hip.ROWS` includes it, both
+    builds export it and `_hip.entry` types it lazily"""
+    import ctypes as C
+
+    import test_fused_marshalling as TM
+
+    protos = ext_prototypes()
+    assert "xg_redi_horizontal_tensor" in protos
+    assert set(protos) == set(_hip.EXT_SIGNATURES) == {e for name in _hip.FUSED_EXT for e, _ in _hip.forms(name)}
+    assert not set(protos) & (set(_hip.SIGNATURES) | set(_hip.GM_SIGNATURES) | set(_hip.FUSED) | set(_hip.FUSED_AT_FACES))
+    scalars = {"int": C.c_int, "double": C.c_double}
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    libs = [C.CDLL(os.path.join(root, "xgcm_amd", lib)) for lib in ("libxgcm_hip.so", "libxgcm_host.so")]
+    for name, row in _hip.FUSED_EXT.items():
+        assert row.typed and _hip.ROWS[name] is row
+        for entry, halo in _hip.forms(name):
+            ret, params = protos[entry]
+            res, args = _hip.EXT_SIGNATURES[entry]
+            assert ret == "int" and res is C.c_int and len(args) == len(params)
+            for (ctype, pname), a in zip(params, args):
+                if ctype.endswith("*"):
+                    assert a is C.c_void_p or (ctype == "int64_t*" and a._type_ is C.c_int64), (entry, pname)
+                else:
+                    assert a is scalars[ctype], (entry, pname)
+            assert TM._slot_names(row, halo) == [pname for _, pname in params]
+            for lib in libs:
+                assert hasattr(lib, entry)
+                assert _hip.entry(lib, entry).argtypes == args
+    row = _hip.FUSED_EXT["xg_redi_horizontal_tensor"]
+    assert [s.name for s in row.slots if s.kind == "result"] == ["out_u", "out_v"] and all(s.at == "shape" for s in row.slots if s.kind == "result")
+    assert [s.name for s in row.slots if s.kind == "real"] == ["kappa", "slope_max2"]
+
+
+def test_argument_order_through_the_recording_library(monkeypatch):
+    """every argument of one call reaches the parameter of its name"""
+    import test_fused_marshalling as TM
+    import xgcm_amd.device as D
+
+    mem = TM.RecordingMemory()
+    monkeypatch.setattr(D, "_MEM", mem)
+    shape, fshape = (2, 3, 3, 4), (2, 4, 3, 4)
+    b = TM._field(torch.float64, shape)
+    mets = {"mx": TM._field(torch.float64, (1, 3, 3, 4)), "my": TM._field(torch.float64, (2, 1, 3, 4)), "mz": TM._field(torch.float64, (2, 4, 1, 1))}
+    ku, kv = D.redi_horizontal_tensor(b, *mets.values(), 750.0, 0.25, True, "periodic", "fill", "extend", 1.5, -0.0, 2.5)
+    assert tuple(ku.shape) == tuple(kv.shape) == shape and fshape[1] == shape[1] + 1
+    expected = dict(dtype=_hip.DTYPE["float64"], b=b.data_ptr(), kappa=750.0, slope_max2=0.25, taper=1, out_u=ku.data_ptr(),
+                    out_v=kv.data_ptr(), shape=shape, ndim=4, outer=1, bc_x=_hip.BC["periodic"], fill_x=1.5,
+                    bc_y=_hip.BC["fill"], fill_y=-0.0, bc_z=_hip.BC["extend"], fill_z=2.5, stream=TM.STREAM)
+    for n, m in mets.items():
+        expected[n] = m.data_ptr()
+        expected[n + "_strides"] = tuple(0 if s == 1 else st for s, st in zip(m.shape, m.stride()))
+    monkeypatch.setitem(TM.PROTOS, "xg_redi_horizontal_tensor", ext_prototypes()["xg_redi_horizontal_tensor"])
+    TM._check_call(mem.recorder, "xg_redi_horizontal_tensor", expected)
+
+
+# ---- 8. the tunable call table, between guard bands -------------------------------------------------------------------------
+def tunable_calls(D, dtype):
+    """(calls, references) of the K7u tunable sweep: name -> thunk that calls `D` on inputs uploaded once, name -> thunk that
+    gives numpy's two results of the same call.  Both face positions; planes with a profile, three volumes, and no metric;
+    slope_max rotating"""
+    f = lambda shape, seed: R.synthetic_field(shape, seed).astype(dtype)  # noqa: E731
+    m = lambda shape, seed: R.synthetic_metric(shape, seed).astype(dtype)  # noqa: E731
+    calls, references = {}, {}
+    for n, shape in enumerate(((5, 300, 264), (3, 65, 131))):
+        nz, ny, nx = shape
+        b = f(shape, 150 + n)
+        b[1, 7, 9] = b[0, 0, 0] = b[nz - 1, ny - 1, nx - 1] = np.nan
+        dev = D.asdevice(b)
+        for k, (to, pads) in enumerate((("left", ("periodic", "extend", "fill")), ("outer", ("extend", "fill", "periodic")),
+                                        ("left", ("fill", "periodic", "extend")), ("outer", ("periodic", "periodic", "fill")))):
+            nf = nz + (to == "outer")
+            if k % 2:
+                mets = [m((1, ny, nx), 170), m((1, ny, nx), 171), m((nf, 1, 1), 172)]
+            else:
+                mets = [m((nz, ny, nx), 173), m((nz, ny, nx), 174), m((nf, ny, nx), 175)]
+            if k == 2:
+                mets = [None, None, None]
+            dm = tuple(None if x is None else D.asdevice(x) for x in mets)
+            key = f"{nx}{to}{pads[2]}"
+            fill = [FILL[a] for a in "XYZ"]
+            kappa, sm = KAPPAS[(n + k) % 3], SLOPE_MAXES[(n + k) % 3]
+            m2 = None if sm is None else sm * sm
+            calls[key] = lambda dev=dev, dm=dm, to=to, pads=pads, kappa=kappa, m2=m2: D.redi_horizontal_tensor(
+                dev, *dm, float(kappa), m2, to == "outer", *pads, *fill)
+            references[key] = lambda h=b, mets=mets, to=to, pads=pads, kappa=kappa, sm=sm: list(
+                _want(h, pads, to, FILL, *mets, kappa=kappa, slope_max=sm))
+    return calls, references
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_the_tunable_call_table_equals_its_numpy_references(host_abi, dtype):
+    """the thunks the GPU suite sweeps over every tunable value, once through the host build (which reads no tunable): the
+    arguments, their order, the shapes and the references are checked before any GPU time is spent on them"""
+    import xgcm_amd.device as D
+
+    calls, references = tunable_calls(D, dtype)
+    assert len(calls) == 8 and set(calls) == set(references)
+    for name, thunk in calls.items():
+        got, want = [D.tohost(x) for x in thunk()], references[name]()
+        assert len(got) == len(want) == 2, name
+        for g, w in zip(got, want):
+            assert g.dtype == np.dtype(dtype) and np.isnan(w).any() and np.isnan(w).mean() < 0.1, name
+            assert TI._bits_equal(g, w), name
+        assert (want[0] != want[1]).any()
+
+
+def guarded_table(D, monkeypatch, dtype, offset, same_bits):
+    """the table built and run between guard bands: a store outside either result, a cell left unwritten and a
+    result-changing read outside the field or a metric all fail; returns the number of results checked"""
+    checked = 0
+    with GM.guarded(D, monkeypatch, offset) as g:
+        calls, references = tunable_calls(D, dtype)
+        assert g.placed >= 2 + 2 * 3 * 3          # the field of both shapes, the metrics of the calls that have them
+        for k, fn in calls.items():
+            before = g.handed_out
+            got = [D.tohost(x) for x in fn()]
+            g.check(f"{k} at offset {offset}")
+            assert g.handed_out - before >= 2     # both results between guards
+            for x, want in zip(got, references[k]()):
+                assert same_bits(x, want), f"{k} at offset {offset}: not numpy's result"
+                checked += 1
+    return checked
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+def test_between_guard_bands_through_the_host_abi(host_abi, monkeypatch, dtype):
+    import xgcm_amd.device as D
+
+    for offset in (0, 16, np.dtype(dtype).itemsize):
+        assert guarded_table(D, monkeypatch, dtype, offset, TI._bits_equal) == 16

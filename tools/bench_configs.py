@@ -14,7 +14,7 @@ ranks (re-executing itself under torch.distributed.run when no launcher did, exa
   5   fused and unfused vorticity (diff(V,'X') - diff(U,'Y')) / rAz, `fill`, on 4320x4320x90 split along Z
       (90 -> 12,12,11,11,11,11,11,11 on 8 GPUs), rAz replicated.
 No data-path collective: RCCL carries barriers, the max-over-ranks time and a checksum of checksums.
-Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only; 5pp: richardson_mixing against its chain, alone only; 5is: isopycnal_slope against its chain, alone only; 5rt: redi_tensor against its chain, alone or after 5is; 5rf: redi_vertical_flux_divergence against its chain, alone only; 5bv: bolus_velocity against its chain, alone only), f1, f2, f4, llc, pcie, stream.
+Single-GPU extras: 4x (> 2^32-cell batch checks), 5x (divergence / gradient / flux; flux_divergence / laplacian / flux_divergence_3d / vertical_velocity / kinetic_energy / momentum_advection / hydrostatic_pressure_gradient / vertical_momentum_advection / horizontal_viscosity / vertical_diffusion / richardson_number against their chains, implicit_vertical_diffusion against its level loop; 5pg, 5vm, 5hv, 5vd, 5iv, 5ri: the last six pairs, each alone; 5vv: implicit_vertical_viscosity against its chain of four calls, alone only; 5pp: richardson_mixing against its chain, alone only; 5is: isopycnal_slope against its chain, alone only; 5rt: redi_tensor against its chain, alone or after 5is; 5rf: redi_vertical_flux_divergence against its chain, alone only; 5bv: bolus_velocity against its chain, alone only; 5ru: redi_horizontal_tensor against its chain, alone only), f1, f2, f4, llc, pcie, stream.
 """
 import argparse
 import json
@@ -563,6 +563,83 @@ def run_bolus_velocity(reps, nz=90, n=4320):
                       "outermost_faces_of_kwx_are_nan": nan_faces, "bytes_per_cell_one_pass": bpc, "bytes_per_cell_chain": 184,
                       "bound_by_bytes": round(184 / bpc, 2), "speedup": round(med(tc) / med(tf), 2),
                       "fraction_of_8TBps_at_40B_per_cell": round(cells * bpc / (med(tf) * 1e-3) / 8e12, 4),
+                      "rounds_ms_fused": [round(t, 3) for t in tf], "rounds_ms_chain": [round(t, 3) for t in tc],
+                      "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
+
+
+def run_redi_horizontal_tensor(reps, nz=90, n=4320):
+    """redi_horizontal_tensor in one pass against its chain of 40 launches (three derivatives, the mean of db/dz back to the
+    levels, two means of it towards u's and v's points, the two cross means of two interpolations each, four quotients, four
+    negations, twice eleven launches of taper arithmetic; dxC, dyC and a profile drC(Zp1); periodic / extend / extend,
+    to="outer", kappa 1000, slope_max 1e-2), timed in turns, every paired round reported.  The chain frees its temporaries as
+    it goes.  By the count of its launches it moves about 720 B/cell in float64 (ten stencils and four negations at 16, four
+    quotients at 24, twice eleven launches of taper arithmetic at about 200 together) against the one pass's 24: one read,
+    two writes.  The field 13 GB, the six results of the comparison 81 GB, the chain's live temporaries about 70 GB: about
+    165 GB at the peak, all 90 levels."""
+    coords = {"XC": ("XC", np.arange(n) + 0.5), "XG": ("XG", np.arange(n) * 1.0), "YC": ("YC", np.arange(n) + 0.5),
+              "YG": ("YG", np.arange(n) * 1.0), "Z": ("Z", np.arange(nz) + 0.5), "Zp1": ("Zp1", np.arange(nz + 1) * 1.0)}
+    ds = Dataset({"dxC": DataArray(D.synthetic((n, n), 31, 0, 1000.0, 1000.0), ("YC", "XG")),
+                  "dyC": DataArray(D.synthetic((n, n), 32, 0, 1000.0, 1000.0), ("YG", "XC")),
+                  "drC": DataArray(D.synthetic((nz + 1,), 34, 0, 10.0, 10.0), ("Zp1",))}, coords)
+    grid = Grid(ds, coords={"X": {"center": "XC", "left": "XG"}, "Y": {"center": "YC", "left": "YG"},
+                            "Z": {"center": "Z", "outer": "Zp1"}},
+                padding={"X": "periodic", "Y": "extend", "Z": "extend"},
+                metrics={("X",): ["dxC"], ("Y",): ["dyC"], ("Z",): ["drC"]}, autoparse_metadata=False)
+    B = DataArray(D.synthetic((nz, n, n), 63), ("Z", "YC", "XC"))
+    cells = nz * n * n
+    kappa, slope_max = 1000.0, 1e-2   # (the operator's defaults)
+
+    def taper(sa, sb, pick):
+        s2 = sa * sa + sb * sb
+        m2 = float(slope_max) * float(slope_max)
+        ex = s2 - m2
+        den = m2 + (ex + abs(ex)) * 0.5
+        del s2, ex
+        kt = kappa * (m2 / den)
+        del den
+        return kt * pick
+
+    def chain():
+        gx = grid.derivative(B, "X")
+        gy = grid.derivative(B, "Y")
+        bzc = grid.interp(grid.derivative(B, "Z", to="outer"), "Z", to="center")
+        bzu = grid.interp(bzc, "X", to="left")
+        bzv = grid.interp(bzc, "Y", to="left")
+        del bzc
+        gyu = grid.interp(grid.interp(gy, "Y", to="center"), "X", to="left")
+        gxv = grid.interp(grid.interp(gx, "X", to="center"), "Y", to="left")
+        sxu, syu = -(gx / bzu), -(gyu / bzu)
+        del bzu, gyu, gx
+        sxv, syv = -(gxv / bzv), -(gy / bzv)
+        del bzv, gxv, gy
+        kuz = taper(sxu, syu, sxu)
+        del sxu, syu
+        kvz = taper(sxv, syv, syv)
+        return kuz, kvz
+
+    one = lambda: grid.redi_horizontal_tensor(B, kappa, slope_max, to="outer")  # noqa: E731
+    got, want = list(one()), list(chain())
+    free = list(grid.redi_horizontal_tensor(B, kappa, None, to="outer"))
+    ok, finite, tapered = [], [], []
+    while got:
+        g, w, f = got.pop(0), want.pop(0), free.pop(0)
+        eq = g.data.view(torch.int64) == w.data.view(torch.int64)
+        eq |= torch.isnan(g.data) & torch.isnan(w.data)
+        ok.append(bool(eq.all()) and g.dims == w.dims)
+        finite.append(bool(torch.isfinite(g.data).all()))
+        tapered.append(round(float((g.data != f.data).double().mean()), 4))   # the taper is exactly 1 below the limit
+        del g, w, f, eq
+        torch.cuda.empty_cache()
+    tf, tc = timeit_rounds(one, chain, max(4, reps // 2))
+    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
+    bpc = 24   # b in, kuz and kvz out
+    rec(5, "redi_horizontal_tensor one pass: kuz, kvz from b, to=outer, dxC, dyC, drC(Zp1), periodic/extend/extend: 1 read + 2 writes", med(tf), cells, bpc)
+    rec(5, "redi_horizontal_tensor as its chain (40 launches), one-pass-equivalent bytes", med(tc), cells, bpc)
+    print(json.dumps({"config": 5, "check": "one-pass redi_horizontal_tensor == chain bit for bit at full size (kuz, kvz)", "ok": ok,
+                      "result_finite_everywhere": finite, "fraction_of_cells_tapered": tapered, "levels": nz,
+                      "bytes_per_cell_one_pass": bpc, "bytes_per_cell_chain": 720, "bound_by_bytes": round(720 / bpc, 1),
+                      "speedup": round(med(tc) / med(tf), 2),
+                      "fraction_of_8TBps_at_24B_per_cell": round(cells * bpc / (med(tf) * 1e-3) / 8e12, 4),
                       "rounds_ms_fused": [round(t, 3) for t in tf], "rounds_ms_chain": [round(t, 3) for t in tc],
                       "fused_below_chain_in_every_round": all(a < b for a, b in zip(tf, tc))}), flush=True)
 
@@ -1271,6 +1348,8 @@ def main():
         run_redi_vertical_flux_divergence(a.reps)
     if "5bv" in cfgs:   # (not part of 5x: about 190 GB)
         run_bolus_velocity(a.reps, *((shp[0], shp[2]) if shp else (90, 4320)))
+    if "5ru" in cfgs:   # (not part of 5x: about 165 GB)
+        run_redi_horizontal_tensor(a.reps, *((shp[0], shp[2]) if shp else (90, 4320)))
     ranks.close()
 
 

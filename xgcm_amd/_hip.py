@@ -233,7 +233,13 @@ FUSED_AT_FACES = {
                              + _results("out_u", "out_v") + _results("out_w", at="faces") + _SHAPE + _of("flag", "outer", "closed")
                              + _bc("x", "y", "z") + _STREAM, True, ("kwx", "kwy")),
 }
-ROWS = {**FUSED, **FUSED_AT_FACES}
+# The entries of include/xgcm_hip_ext.h, the open-ended home of every later fused entry point: FUSED and FUSED_AT_FACES are
+# held to fixed sets, as their two headers are, so a new row goes HERE and its prototype there.  Rows of FUSED's kind.
+FUSED_EXT = {
+    "xg_redi_horizontal_tensor": Row("redi_horizontal_tensor", _SLOPE + _of("real", "kappa", "slope_max2") + _of("flag", "taper")
+                                     + _results("out_u", "out_v") + _OUTER_XYZ + _STREAM, True),
+}
+ROWS = {**FUSED, **FUSED_AT_FACES, **FUSED_EXT}
 
 
 def forms(name: str):
@@ -250,11 +256,15 @@ def _argtypes(row: Row, halo: bool, real):
     return args
 
 
-GM_SIGNATURES = {}  # name -> (restype, argtypes); the export list of include/xgcm_hip_gm.h
+GM_SIGNATURES = {}   # name -> (restype, argtypes); the export list of include/xgcm_hip_gm.h
+EXT_SIGNATURES = {}  # ... and of include/xgcm_hip_ext.h (typed entries only)
 for _name, _row in ROWS.items():
     for _entry, _halo in forms(_name):
         if _name in FUSED_AT_FACES:
             GM_SIGNATURES[_entry] = (C.c_int, _argtypes(_row, _halo, C.c_double))
+        elif _name in FUSED_EXT:
+            assert _row.typed, _name
+            EXT_SIGNATURES[_entry] = (C.c_int, _argtypes(_row, _halo, C.c_double))
         elif _row.typed:
             SIGNATURES[_entry] = (C.c_int, _argtypes(_row, _halo, C.c_double))
         else:
@@ -306,6 +316,8 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
+    for name in EXT_SIGNATURES:  # (typed lazily, by `entry`; a build without one of them is no build of this ABI)
+        getattr(lib, name)
     if lib.xg_version() != 1:
         raise ImportError(f"libxgcm_hip.so ABI version {lib.xg_version()} != 1")
     _lib = lib
@@ -314,9 +326,9 @@ def load() -> C.CDLL:
 
 def entry(lib, name: str):
     """the entry `name` of a build of the ABI, typed: whoever opened `lib` typed the entries of SIGNATURES; one of
-    GM_SIGNATURES is typed here, on its first use, on whichever build serves the call"""
+    GM_SIGNATURES or EXT_SIGNATURES is typed here, on its first use, on whichever build serves the call"""
     fn = getattr(lib, name)
-    sig = GM_SIGNATURES.get(name)
+    sig = GM_SIGNATURES.get(name) or EXT_SIGNATURES.get(name)
     if sig is not None and getattr(fn, "argtypes", None) is None:
         fn.restype, fn.argtypes = sig
     return fn

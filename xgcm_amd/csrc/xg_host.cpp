@@ -27,6 +27,7 @@
 
 #include "../../include/xgcm_hip.h"
 #include "../../include/xgcm_hip_gm.h"
+#include "../../include/xgcm_hip_ext.h"
 
 namespace {
 
@@ -1164,6 +1165,121 @@ int rediflux(const R* a, const R* kwx, const R* kwy, const R* const arr[3], cons
   return XG_OK;
 }
 
+// the U- and V-point components of the tapered tensor of the header (xgcm_hip_ext.h) as the stages of their chain over one
+// (Z, Y, X) volume at a time, each into a temporary: the differences along X and Y over their metrics; b's difference along Z
+// at the faces over its metric and its mean back to the levels; the means of that towards u's and v's points; the centre
+// means of the two differences and their means towards the other point; the four quotients, negated; the taper at each
+// point -- each stage padding its own input.  arr[] = {mx, my, mz}: mx and my at the field's levels, mz at the faces
+template <typename R>
+int rediuv(const R* b, const R* const arr[3], const int64_t* const st[3], R kappa, R m2, int taper, R* out_u, R* out_v,
+           const int64_t* shape, int ndim, int outer, const int bc[3], const R fill[3]) {  // bc, fill: X, Y, Z
+  const char* name = "redi horizontal tensor";
+  if (!b || !out_u || !out_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  if (ndim < 3 || ndim > XG_MAX_NDIM) return fail(XG_ERR_UNSUPPORTED, "%s: ndim %d not in [3,%d]", name, ndim, XG_MAX_NDIM);
+  for (int k = 0; k < 3; ++k)
+    if (bc[k] < XG_BC_PERIODIC || bc[k] > XG_BC_EXTEND) return fail(XG_ERR_INVALID, "%s: boundary mode %d: periodic, fill or extend", name, bc[k]);
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (taper != 0 && taper != 1) return fail(XG_ERR_INVALID, "%s: taper %d is neither 0 nor 1", name, taper);
+  const int64_t nz = shape[ndim - 3], ny = shape[ndim - 2], nx = shape[ndim - 1], plane = ny * nx, vol = nz * plane;
+  if (nz == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  int64_t lead = 1;
+  for (int d = 0; d < ndim - 3; ++d) lead *= shape[d];
+  if (lead * vol > 0 && (uintptr_t)out_u < (uintptr_t)(out_v + lead * vol) && (uintptr_t)out_v < (uintptr_t)(out_u + lead * vol))
+    return fail(XG_ERR_INVALID, "%s: the results overlap", name);
+  for (int k = 0; k < 3; ++k)
+    if (arr[k] && !st[k]) return fail(XG_ERR_INVALID, "%s: metric without strides", name);
+  const int64_t nf = nz + outer;  // faces
+  if (lead == 0 || vol == 0) return XG_OK;
+  const int64_t n[3] = {nx, ny, nz}, step[3] = {1, nx, plane};
+  std::vector<R> g[2], gc((size_t)vol), bzf((size_t)(nf * plane)), bzc((size_t)vol), bzp((size_t)vol), cross((size_t)vol);
+  g[0].resize((size_t)vol);
+  g[1].resize((size_t)vol);
+  for (int64_t o = 0; o < lead; ++o) {
+    int64_t rem = o, off[3] = {0, 0, 0};  // the lead index decomposed for the broadcast strides
+    for (int dd = ndim - 4; dd >= 0; --dd) {
+      const int64_t i = rem % shape[dd];
+      rem /= shape[dd];
+      for (int k = 0; k < 3; ++k)
+        if (arr[k]) off[k] += i * st[k][dd];
+    }
+    auto met = [&](int k, int64_t z, int64_t j, int64_t i) -> R {
+      return arr[k][off[k] + z * st[k][ndim - 3] + j * st[k][ndim - 2] + i * st[k][ndim - 1]];
+    };
+    const R* p = b + o * vol;
+    // element q of `a` along axis `ax` (0: X, 1: Y, 2: Z) from the cell at `c` whose index there is `at`; beyond either end:
+    // the pad of that axis
+    auto get = [&](const R* a, int ax, int64_t c, int64_t at, int64_t q) -> R {
+      if (q < 0 || q >= n[ax]) {
+        if (bc[ax] == XG_BC_FILL) return fill[ax];
+        q = bc[ax] == XG_BC_PERIODIC ? (q < 0 ? n[ax] - 1 : 0) : (q < 0 ? 0 : n[ax] - 1);
+      }
+      return a[c + (q - at) * step[ax]];
+    };
+    // (1) the differences to the cell before along X and along Y, over their metrics: at u's and at v's points
+    for (int ax = 0; ax < 2; ++ax)
+      for (int64_t z = 0; z < nz; ++z)
+        for (int64_t j = 0; j < ny; ++j)
+          for (int64_t i = 0; i < nx; ++i) {
+            const int64_t c = z * plane + j * nx + i, at = ax == 0 ? i : j;
+            R d = p[c] - get(p, ax, c, at, at - 1);
+            if (arr[ax]) d = d / met(ax, z, j, i);
+            g[ax][c] = d;
+          }
+    // (2) b's difference along Z at the faces over its metric: level z of the padded field is a level of it or its pad
+    for (int64_t z = 0; z < nf; ++z)
+      for (int64_t j = 0; j < ny; ++j)
+        for (int64_t i = 0; i < nx; ++i) {
+          const int64_t c = j * nx + i;
+          R d = get(p, 2, c, 0, z) - get(p, 2, c, 0, z - 1);
+          if (arr[2]) d = d / met(2, z, j, i);
+          bzf[z * plane + c] = d;
+        }
+    // (3) its mean back to the levels; `left` pads the derivative beyond its last face
+    for (int64_t z = 0; z < nz; ++z)
+      for (int64_t c = 0; c < plane; ++c) {
+        R next;
+        if (z + 1 < nf) next = bzf[(z + 1) * plane + c];
+        else if (bc[2] == XG_BC_FILL) next = fill[2];
+        else next = bzf[((bc[2] == XG_BC_PERIODIC) ? 0 : nz - 1) * plane + c];
+        bzc[z * plane + c] = (bzf[z * plane + c] + next) * R(0.5);
+      }
+    for (int ax = 0; ax < 2; ++ax) {  // 0: u's points, kuz;  1: v's points, kvz
+      const int ot = 1 - ax;          // the other horizontal axis
+      // (4) db/dz at the point: the mean with the cell before along `ax`
+      // (5) the other derivative there: its centre mean along its own axis, then the mean with the cell before along `ax`
+      for (int64_t z = 0; z < nz; ++z)
+        for (int64_t j = 0; j < ny; ++j)
+          for (int64_t i = 0; i < nx; ++i) {
+            const int64_t c = z * plane + j * nx + i, at = ot == 0 ? i : j;
+            gc[c] = (g[ot][c] + get(g[ot].data(), ot, c, at, at + 1)) * R(0.5);
+          }
+      for (int64_t z = 0; z < nz; ++z)
+        for (int64_t j = 0; j < ny; ++j)
+          for (int64_t i = 0; i < nx; ++i) {
+            const int64_t c = z * plane + j * nx + i, at = ax == 0 ? i : j;
+            bzp[c] = (get(bzc.data(), ax, c, at, at - 1) + bzc[c]) * R(0.5);
+            cross[c] = (get(gc.data(), ax, c, at, at - 1) + gc[c]) * R(0.5);
+          }
+      // (6) the two slopes, the taper, the component along `ax`
+      R* po = (ax == 0 ? out_u : out_v) + o * vol;
+      for (int64_t c = 0; c < vol; ++c) {
+        const R q_own = g[ax][c] / bzp[c], q_other = cross[c] / bzp[c];
+        const R s_own = R(-1) * q_own, s_other = R(-1) * q_other;
+        const R sx = ax == 0 ? s_own : s_other, sy = ax == 0 ? s_other : s_own;
+        const R s2 = sx * sx + sy * sy;
+        R kt = kappa;
+        if (taper) {
+          const R ex = s2 - m2;
+          const R den = m2 + (ex + std::fabs(ex)) * R(0.5);
+          kt = kappa * (m2 / den);
+        }
+        po[c] = kt * s_own;
+      }
+    }
+  }
+  return XG_OK;
+}
+
 // the bolus velocity of the header as the stages of its chain over one lead index at a time, each into a temporary: the two
 // means towards the left points, the closed faces, the differences to the next face's over their metrics, negated; the
 // two transports, their differences to the next column's / row's, the sum over the area.
@@ -2001,6 +2117,27 @@ int xg_bolus_velocity(int dtype, const void* kwx, const void* kwy, const void* m
                         outer, closed, bc, fill);
   }
   return fail(XG_ERR_INVALID, "bolus velocity: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+
+int xg_redi_horizontal_tensor(int dtype, const void* b, const void* mx, const int64_t* mxs, const void* my, const int64_t* mys,
+                              const void* mz, const int64_t* mzs, double kappa, double slope_max2, int taper, void* out_u,
+                              void* out_v, const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y,
+                              double fill_y, int bc_z, double fill_z, void*) {
+  const int64_t* const st[3] = {mxs, mys, mzs};
+  const int bc[3] = {bc_x, bc_y, bc_z};
+  if (dtype == XG_T_F64) {
+    const double* const arr[3] = {(const double*)mx, (const double*)my, (const double*)mz};
+    const double fill[3] = {fill_x, fill_y, fill_z};
+    return rediuv<double>((const double*)b, arr, st, kappa, slope_max2, taper, (double*)out_u, (double*)out_v, shape, ndim, outer,
+                          bc, fill);
+  }
+  if (dtype == XG_T_F32) {
+    const float* const arr[3] = {(const float*)mx, (const float*)my, (const float*)mz};
+    const float fill[3] = {(float)fill_x, (float)fill_y, (float)fill_z};
+    return rediuv<float>((const float*)b, arr, st, (float)kappa, (float)slope_max2, taper, (float*)out_u, (float*)out_v, shape,
+                         ndim, outer, bc, fill);
+  }
+  return fail(XG_ERR_INVALID, "redi horizontal tensor: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 
 int xg_convert(const void* src, int st, void* dst, int dt, uint64_t n, int via, double scale, int flags, void*) {

@@ -5,6 +5,7 @@
 
 #include "xg_common.hpp"
 #include "../../include/xgcm_hip_gm.h"
+#include "../../include/xgcm_hip_ext.h"
 
 // rows of Y per wave-task of the fused two-component kernels (see STENCIL_SEG in xg_stencil.hip): A/B on one GPU
 // (XG_HIP_LIB), 4320 x 4320 x 90: vorticity 70.0 / 71.7 / 71.3 % with 4 / 2 / 1 rows, gradient 73.9 / 75.7 / 75.6 %,
@@ -2907,6 +2908,273 @@ __global__ __launch_bounds__(BLOCK) void k_bolus(
 }
 
 // ------------------------------------------------------------------------------------------
+// K7u: the tapered off-diagonal components of the Redi / Gent-McWilliams tensor at u's and v's points in ONE pass over
+// (lead, Z, Y, X), one field in, two out at the levels (include/xgcm_hip_ext.h):
+//   gx[i] = (b[i] - b[i-1]) [/ mx]    gy[j] = (b[j] - b[j-1]) [/ my]    f[k] = (b[k] - b[k-1]) [/ mz[k]]     bzc[k] = (f[k] + f[k+1]) * 0.5
+//   bzu[i] = (bzc[i-1] + bzc[i]) * 0.5          bzv[j] = (bzc[j-1] + bzc[j]) * 0.5
+//   gyu[i] = (gyc[i-1] + gyc[i]) * 0.5, gyc[j] = (gy[j] + gy[j+1]) * 0.5        gxv[j] = (gxc[j-1] + gxc[j]) * 0.5, gxc[i] = (gx[i] + gx[i+1]) * 0.5
+//   u's points: sx = -1 * (gx / bzu), sy = -1 * (gyu / bzu)        v's points: sx = -1 * (gxv / bzv), sy = -1 * (gy / bzv)
+//   K7r's epilogue at each point, kt = kappa * (m2 / (m2 + (ex + |ex|) * 0.5)), ex = sx * sx + sy * sy - m2;  out_u = kt * sx, out_v = kt * sy
+// K7q's wave-task: a wave owns one (lead, Y segment, X tile) column and marches the levels one level ahead of its stores
+// (bzc[k] needs the faces above and below level k, hence b of level k + 1); it carries the level's patch of b and the face
+// derivative f[k].  A level brings SEG + 2 rows of b (the row below and the row above the segment) with the elements left
+// and right of the lane's vector (from the lanes beside it by DPP; the tile's first / last lane and the row's edges load
+// their own), as K7q's IsRows with the two outer rows' neighbours as well: the patch has rows 0 (below), 1 .. SEG (the
+// segment), SEG + 1 (above) and columns 0 (left), 1 .. V (the lane's), V + 1 (right).  More of the halo than K7q: gx on the
+// row below (for gxv) and right of the lane (for gxc), gy above the segment (for gyc) and left of the lane (for gyu), f and
+// bzc left of the lane and on the row below -- each lane forms the derived values of its halo itself, from the patch.
+// Where a chain stage pads a DERIVED quantity -- bzc and gyc left of column 0, bzc and gxc below row 0, gx right of the last
+// column, gy above the last row, f beyond the last face of `left` -- the stage's pad is substituted (periodic: the far one,
+// which the wrapped patch row / column gives; extend: its own; fill: the fill value itself), never formed from padded b.
+// mx at rows 0 .. SEG, columns 1 .. V + 1; my at rows 1 .. SEG + 1, columns 0 .. V; mz (at the faces) at rows 0 .. SEG, columns
+// 0 .. V: element loads through the broadcast strides, those that do not vary along Z once per wave.  24 B/cell in float64.
+// ------------------------------------------------------------------------------------------
+template <int R, int C>
+struct UvPatch {  // b of one level around the lane: rows below, the segment's, above; columns left, the lane's, right
+  real v[R][C];
+};
+
+template <int V, bool MET, bool NTS, int SEG>
+__global__ __launch_bounds__(BLOCK) void k_rediuv(
+    const real* __restrict__ b, real* __restrict__ out_u, real* __restrict__ out_v, int64_t o0, u32 nouter, u32 nblk,
+    int64_t nz, int64_t ny, int64_t nx, FastDiv ntile, FastDiv nseg, int outer, int bc_x, real fill_x, int bc_y, real fill_y,
+    int bc_z, real fill_z, VolIdx mx, VolIdx my, VolIdx mz, int ntl, RediScalars c) {
+  typedef typename VecT<V>::type T;
+  constexpr int R = SEG + 2, C = V + 2;
+  typedef UvPatch<R, C> P;
+  XG_WAVE_TASK(V, SEG, false, ZBand{}, 1);
+  const int64_t plane = ny * nx;
+  const int64_t col = o * nz * plane;  // level 0 of this lead index (int64)
+  const LaneEdges e = lane_edges<V>(i0, nx, bc_x, ntl);
+  const bool per_x = bc_x == XG_BC_PERIODIC, per_y = bc_y == XG_BC_PERIODIC, per_z = bc_z == XG_BC_PERIODIC;
+  const bool fill_l = e.edge_l && bc_x == XG_BC_FILL;  // b, bzc and gyc left of column 0 are the fill value
+  const bool pad_r = e.edge_r && !per_x;               // gx right of the last column is its pad
+  const bool fill_b = j0 == 0 && bc_y == XG_BC_FILL;   // b, bzc and gxc below row 0 are the fill value
+  const int64_t jb = (j0 > 0) ? j0 - 1 : (per_y ? ny - 1 : 0);
+  const int64_t q = j0 + nrow;
+  const bool pad_t = q >= ny && !per_y;                // gy above the last row is its pad
+  const int64_t jt = (q < ny) ? q : (per_y ? 0 : ny - 1);
+  int64_t rj[R];  // the patch's rows in a plane (short tails repeat the last row of the segment)
+  rj[0] = jb;
+#pragma unroll
+  for (int r = 1; r <= SEG; ++r) rj[r] = j0 + ((r <= nrow) ? r - 1 : nrow - 1);
+  rj[R - 1] = jt;
+  int64_t ci[C];  // ... and its columns in a row
+  ci[0] = e.lidx;
+#pragma unroll
+  for (int k = 1; k <= V; ++k) ci[k] = i0 + k - 1;
+  ci[C - 1] = e.ridx;
+
+  // the metrics of a level (mx, my) and of a face (mz), element by element through the broadcast strides; loaded again per
+  // level / face only when the array varies along Z
+  real mxv[SEG + 1][V + 1], myv[SEG + 1][V + 1], mzv[SEG + 1][V + 1];
+  int64_t mxo = 0, myo = 0, mzo = 0;
+  auto hmetrics = [&](int64_t k, bool first) {
+    if (mx.p && (first || mx.sz != 0)) {
+#pragma unroll
+      for (int r = 0; r <= SEG; ++r)
+#pragma unroll
+        for (int k_ = 1; k_ <= V + 1; ++k_) mxv[r][k_ - 1] = mx.p[mxo + k * mx.sz + rj[r] * mx.sy + ci[k_] * mx.sx];
+    }
+    if (my.p && (first || my.sz != 0)) {
+#pragma unroll
+      for (int r = 1; r <= SEG + 1; ++r)
+#pragma unroll
+        for (int k_ = 0; k_ <= V; ++k_) myv[r - 1][k_] = my.p[myo + k * my.sz + rj[r] * my.sy + ci[k_] * my.sx];
+    }
+  };
+  auto zmetric = [&](int64_t kf, bool first) {
+    if (mz.p && (first || mz.sz != 0)) {
+#pragma unroll
+      for (int r = 0; r <= SEG; ++r)
+#pragma unroll
+        for (int k_ = 0; k_ <= V; ++k_) mzv[r][k_] = mz.p[mzo + kf * mz.sz + rj[r] * mz.sy + ci[k_] * mz.sx];
+    }
+  };
+  if (MET) {
+    if (mx.p) mxo = area_outer_off(mx.ai, o);
+    if (my.p) myo = area_outer_off(my.ai, o);
+    if (mz.p) mzo = area_outer_off(mz.ai, o);
+    hmetrics(0, true);
+  }
+
+  auto fetch = [&](int64_t k) -> P {
+    P x;
+    const int64_t lv = col + k * plane;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t row = lv + rj[r] * nx;
+      const T own = *reinterpret_cast<const T*>(b + row + i0);
+      real left = e.own_l ? b[row + e.lidx] : real(0);
+      real right = e.own_r ? b[row + e.ridx] : real(0);
+      if (e.shl) {
+        const real lo = from_lane_below(vec_last(own));   // DPP wave_shr:1 (lane 0 reads 0 and is `own_l`)
+        const real hi = from_lane_above(vec_first(own));  // DPP wave_shl:1 (lane 63 reads 0 and is `own_r`)
+        if (!e.own_l) left = lo;
+        if (!e.own_r) right = hi;
+      }
+      x.v[r][0] = fill_l ? fill_x : left;
+#pragma unroll
+      for (int k_ = 0; k_ < V; ++k_) x.v[r][k_ + 1] = vec_at(own, k_);
+      x.v[r][C - 1] = right;
+    }
+    if (fill_b) {
+#pragma unroll
+      for (int k_ = 0; k_ < C; ++k_) x.v[0][k_] = fill_y;
+    }
+    return x;
+  };
+  auto padded = [&]() -> P {  // a level of the fill value: the pad of b along Z
+    P x;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int k_ = 0; k_ < C; ++k_) x.v[r][k_] = fill_z;
+    return x;
+  };
+  // the face derivative at face kf between the level above it (`lo`) and the level below it (`hi`): rows 0 .. SEG, columns 0 .. V
+  auto zface = [&](const P& lo, const P& hi, int64_t kf, bool first, real (&f)[SEG + 1][V + 1]) {
+    if (MET) zmetric(kf, first);
+#pragma unroll
+    for (int r = 0; r <= SEG; ++r)
+#pragma unroll
+      for (int k_ = 0; k_ <= V; ++k_) {
+        real d = hi.v[r][k_] - lo.v[r][k_];
+        if (MET) {
+          if (mz.p) d = d / mzv[r][k_];
+        }
+        f[r][k_] = d;
+      }
+  };
+
+  const real minus = real(-1), half = real(0.5);
+  const bool taper = c.taper != 0;
+  auto tensor = [&](real sx, real sy, real pick) -> real {  // K7r's epilogue, one operation per line of the chain
+    const real s2 = sx * sx + sy * sy;
+    real kt = c.kappa;
+    if (taper) {
+      const real ex = s2 - c.m2;
+      const real den = c.m2 + (ex + __builtin_elementwise_abs(ex)) * half;
+      kt = c.kappa * (c.m2 / den);
+    }
+    return kt * pick;
+  };
+  // level k from its patch and the face derivatives above (`fa`) and below (`fb`) it: both results, one 16-byte store each per row
+  auto emit = [&](int64_t k, const P& x, const real (&fa)[SEG + 1][V + 1], const real (&fb)[SEG + 1][V + 1]) {
+    if (MET) hmetrics(k, false);
+    // gx on rows 0 .. SEG at columns 1 .. V + 1, its mean back to the centre at columns 1 .. V
+    real gx[SEG + 1][V + 1], gxc[SEG + 1][V];
+#pragma unroll
+    for (int r = 0; r <= SEG; ++r) {
+#pragma unroll
+      for (int k_ = 1; k_ <= V + 1; ++k_) {
+        real d = x.v[r][k_] - x.v[r][k_ - 1];
+        if (MET) {
+          if (mx.p) d = d / mxv[r][k_ - 1];
+        }
+        gx[r][k_ - 1] = d;
+      }
+      if (pad_r) gx[r][V] = (bc_x == XG_BC_FILL) ? fill_x : gx[r][V - 1];
+#pragma unroll
+      for (int k_ = 0; k_ < V; ++k_) gxc[r][k_] = (gx[r][k_] + gx[r][k_ + 1]) * half;
+    }
+    if (fill_b) {
+#pragma unroll
+      for (int k_ = 0; k_ < V; ++k_) gxc[0][k_] = fill_y;
+    }
+    // gy on rows 1 .. SEG + 1 at columns 0 .. V (row SEG + 1, above: against the segment's last row, which row SEG repeats)
+    real gy[SEG + 1][V + 1], gyc[SEG][V + 1];
+#pragma unroll
+    for (int r = 1; r <= SEG + 1; ++r)
+#pragma unroll
+      for (int k_ = 0; k_ <= V; ++k_) {
+        real d = x.v[r][k_] - x.v[r - 1][k_];
+        if (MET) {
+          if (my.p) d = d / myv[r - 1][k_];
+        }
+        gy[r - 1][k_] = d;
+      }
+#pragma unroll
+    for (int r = 1; r <= SEG; ++r)
+#pragma unroll
+      for (int k_ = 0; k_ <= V; ++k_) {
+        real up = (r < nrow) ? gy[(r < SEG) ? r : r - 1][k_] : gy[SEG][k_];
+        if (r >= nrow && pad_t) up = (bc_y == XG_BC_FILL) ? fill_y : gy[r - 1][k_];
+        real m = (gy[r - 1][k_] + up) * half;
+        if (k_ == 0 && fill_l) m = fill_x;
+        gyc[r - 1][k_] = m;
+      }
+    // db/dz back at the levels: rows 0 .. SEG, columns 0 .. V
+    real bzc[SEG + 1][V + 1];
+#pragma unroll
+    for (int r = 0; r <= SEG; ++r)
+#pragma unroll
+      for (int k_ = 0; k_ <= V; ++k_) {
+        real m = (fa[r][k_] + fb[r][k_]) * half;
+        if (k_ == 0 && fill_l) m = fill_x;
+        if (r == 0 && fill_b) m = fill_y;
+        bzc[r][k_] = m;
+      }
+    const int64_t lv = col + k * plane + i0;
+#pragma unroll
+    for (int r = 1; r <= SEG; ++r) {
+      if (r <= nrow) {
+        T ku, kv;
+#pragma unroll
+        for (int k_ = 1; k_ <= V; ++k_) {
+          const real bzu = (bzc[r][k_ - 1] + bzc[r][k_]) * half;
+          const real bzv = (bzc[r - 1][k_] + bzc[r][k_]) * half;
+          const real gyu = (gyc[r - 1][k_ - 1] + gyc[r - 1][k_]) * half;
+          const real gxv = (gxc[r - 1][k_ - 1] + gxc[r][k_ - 1]) * half;
+          const real sxu = minus * (gx[r][k_ - 1] / bzu);
+          const real syu = minus * (gyu / bzu);
+          const real sxv = minus * (gxv / bzv);
+          const real syv = minus * (gy[r - 1][k_] / bzv);
+          vec_set(ku, k_ - 1, tensor(sxu, syu, sxu));
+          vec_set(kv, k_ - 1, tensor(sxv, syv, syv));
+        }
+        stg_s<T, NTS>(out_u + lv + rj[r] * nx, ku);
+        stg_s<T, NTS>(out_v + lv + rj[r] * nx, kv);
+      }
+    }
+  };
+
+  // face 0 lies between the pad of b above level 0 and level 0; then level k is stored once the face below it is formed
+  real fa[SEG + 1][V + 1], fb[SEG + 1][V + 1];
+  P cur = fetch(0);
+  {
+    P prev;
+    if (per_z) prev = fetch(nz - 1);
+    else if (bc_z == XG_BC_FILL) prev = padded();
+    else prev = cur;
+    zface(prev, cur, 0, true, fa);
+  }
+  for (int64_t k = 0; k < nz; ++k) {
+    const bool more = k + 1 < nz;
+    P nxt = cur;  // (extend: the pad of b below level nz-1 is the level itself)
+    if (more || outer || per_z) {
+      // an interior face; `outer`: the last face, from the pad of b below level nz-1; `left` and periodic: the pad of the
+      // derivative beyond the last face is f[0], formed again from level nz-1 and level 0 over mz[0]
+      if (more || per_z) nxt = fetch(more ? k + 1 : 0);
+      else if (bc_z == XG_BC_FILL) nxt = padded();
+      zface(cur, nxt, (more || outer) ? k + 1 : 0, false, fb);
+    } else {
+      // `left`: the pad of the derivative beyond the last face -- extend: its own, fill: the fill value itself
+#pragma unroll
+      for (int r = 0; r <= SEG; ++r)
+#pragma unroll
+        for (int k_ = 0; k_ <= V; ++k_) fb[r][k_] = (bc_z == XG_BC_EXTEND) ? fa[r][k_] : fill_z;
+    }
+    emit(k, cur, fa, fb);
+    cur = nxt;
+#pragma unroll
+    for (int r = 0; r <= SEG; ++r)
+#pragma unroll
+      for (int k_ = 0; k_ <= V; ++k_) fa[r][k_] = fb[r][k_];
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side of the fused kernels
 // ------------------------------------------------------------------------------------------
 // may every lane of a V-wide kernel load its piece of a metric / area plane as ONE aligned vector in every row and at
@@ -4198,6 +4466,85 @@ int xg_bolus_velocity(int dtype, const void* kwx, const void* kwy, const void* m
                                  ndim, outer, closed, bc_x, (float)fill_x, bc_y, (float)fill_y, bc_z, (float)fill_z, stream);
   }
   return fail(XG_ERR_INVALID, "bolus velocity: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
+}
+#endif
+
+// K7u's launcher: a (lead, Z, Y, X) field of `shape`, xg_redi_tensor's three optional broadcast metrics (mx and my at the
+// field's levels, mz at the faces) and scalars (already in `real`), out_u and out_v of `shape`; one wave per column, the
+// isopycnal family's plan.  The refusals are xg_redi_tensor's.
+static int rediuv_impl(const real* b, const real* mx, const int64_t* mx_strides, const real* my, const int64_t* my_strides,
+                       const real* mz, const int64_t* mz_strides, const RediScalars& c, real* out_u, real* out_v,
+                       const int64_t* shape, int ndim, int outer, int bc_x, real fill_x, int bc_y, real fill_y, int bc_z,
+                       real fill_z, void* stream) {
+  const char* name = "redi horizontal tensor";
+  if (!b || !out_u || !out_v || !shape) return fail(XG_ERR_INVALID, "NULL array argument");
+  int rc;
+  if ((rc = fused_dims(name, ndim, 3, {bc_x, bc_y, bc_z}, XG_BC_EXTEND))) return rc;
+  if (outer != 0 && outer != 1) return fail(XG_ERR_INVALID, "%s: outer %d is neither 0 (left) nor 1", name, outer);
+  if (c.taper != 0 && c.taper != 1) return fail(XG_ERR_INVALID, "%s: taper %d is neither 0 nor 1", name, c.taper);
+  if (shape[ndim - 3] == 0) return fail(XG_ERR_INVALID, "%s: no level along Z", name);
+  int64_t n = 1;  // the two results, `shape` each, may not overlap
+  for (int d = 0; d < ndim; ++d) n *= shape[d];
+  if (n > 0 && (uintptr_t)out_u < (uintptr_t)(out_v + n) && (uintptr_t)out_v < (uintptr_t)(out_u + n))
+    return fail(XG_ERR_INVALID, "%s: the results overlap", name);
+  VolIdx mi[3];
+  const real* mp[3] = {mx, my, mz};
+  const int64_t* ms[3] = {mx_strides, my_strides, mz_strides};
+  for (int k = 0; k < 3; ++k)
+    if ((rc = vol_index(&mi[k], mp[k], ms[k], shape, ndim))) return rc;
+  FusedPlan p;
+  const bool al = aligned16(b) && aligned16(out_u) && aligned16(out_v);
+  if ((rc = fused_plan(&p, name, shape, ndim, 3, al, true, stream)) || p.empty) return rc;
+  const int vnt = vec_nt_bits(1);  // bit 0: the lane neighbours by DPP (the metrics are read element by element)
+  const bool met = mx != nullptr || my != nullptr || mz != nullptr;
+  return fused_launch(p, [&](int64_t o0, u32 nouter, u32 nblk, u32 grid) {
+#define XG_GO(V_, M_, NTS) do { hipLaunchKernelGGL((k_rediuv<V_, M_, NTS, FSEG>), dim3(grid), dim3(BLOCK), 0, p.st, b, out_u, out_v, o0, nouter, nblk, p.nz, p.ny, p.nx, p.fnt, p.fns, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, mi[0], mi[1], mi[2], vnt, c); } while (0)
+#define XG_N(V_, M_) do { if (p.nts) XG_GO(V_, M_, true); else XG_GO(V_, M_, false); } while (0)
+#define XG_V(V_) do { if (met) XG_N(V_, true); else XG_N(V_, false); } while (0)
+    if (p.V > 1) XG_V(NV);
+    else XG_V(1);
+#undef XG_V
+#undef XG_N
+#undef XG_GO
+  });
+}
+
+// One ABI entry for both element types (xg_redi_horizontal_tensor, below).
+__attribute__((visibility("hidden"))) int xg_internal_rediuv_f64(
+    const double* b, const double* mx, const int64_t* mx_strides, const double* my, const int64_t* my_strides,
+    const double* mz, const int64_t* mz_strides, double kappa, double slope_max2, int taper, double* out_u, double* out_v,
+    const int64_t* shape, int ndim, int outer, int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z,
+    void* stream);
+__attribute__((visibility("hidden"))) int xg_internal_rediuv_f32(
+    const float* b, const float* mx, const int64_t* mx_strides, const float* my, const int64_t* my_strides, const float* mz,
+    const int64_t* mz_strides, float kappa, float slope_max2, int taper, float* out_u, float* out_v, const int64_t* shape,
+    int ndim, int outer, int bc_x, float fill_x, int bc_y, float fill_y, int bc_z, float fill_z, void* stream);
+
+int XG_FN(xg_internal_rediuv)(const real* b, const real* mx, const int64_t* mx_strides, const real* my,
+                              const int64_t* my_strides, const real* mz, const int64_t* mz_strides, real kappa,
+                              real slope_max2, int taper, real* out_u, real* out_v, const int64_t* shape, int ndim, int outer,
+                              int bc_x, real fill_x, int bc_y, real fill_y, int bc_z, real fill_z, void* stream) {
+  return rediuv_impl(b, mx, mx_strides, my, my_strides, mz, mz_strides, RediScalars{kappa, slope_max2, taper}, out_u, out_v,
+                     shape, ndim, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, stream);
+}
+
+#ifdef XG_PRIMARY
+// the exported entry (defined once, in the float64 build): the element type is an argument; the fills, kappa and
+// slope_max2 are cast to it here, once
+int xg_redi_horizontal_tensor(int dtype, const void* b, const void* mx, const int64_t* mx_strides, const void* my,
+                              const int64_t* my_strides, const void* mz, const int64_t* mz_strides, double kappa,
+                              double slope_max2, int taper, void* out_u, void* out_v, const int64_t* shape, int ndim, int outer,
+                              int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream) {
+  if (dtype == XG_T_F64)
+    return xg_internal_rediuv_f64((const double*)b, (const double*)mx, mx_strides, (const double*)my, my_strides,
+                                  (const double*)mz, mz_strides, kappa, slope_max2, taper, (double*)out_u, (double*)out_v,
+                                  shape, ndim, outer, bc_x, fill_x, bc_y, fill_y, bc_z, fill_z, stream);
+  if (dtype == XG_T_F32)
+    return xg_internal_rediuv_f32((const float*)b, (const float*)mx, mx_strides, (const float*)my, my_strides,
+                                  (const float*)mz, mz_strides, (float)kappa, (float)slope_max2, taper, (float*)out_u,
+                                  (float*)out_v, shape, ndim, outer, bc_x, (float)fill_x, bc_y, (float)fill_y, bc_z,
+                                  (float)fill_z, stream);
+  return fail(XG_ERR_INVALID, "redi horizontal tensor: element type %d is neither XG_T_F64 nor XG_T_F32", dtype);
 }
 #endif
 

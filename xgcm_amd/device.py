@@ -1589,6 +1589,21 @@ def redi_tensor(b, mx, my, mz, kappa: float, slope_max2, outer: bool, bc_x: str,
     return _fused("xg_redi_tensor", locals(), lambda p: _faces(p["b"], outer, need))
 
 
+def redi_horizontal_tensor(b, mx, my, mz, kappa: float, slope_max2, outer: bool, bc_x: str, bc_y: str, bc_z: str,
+                           fill_x: float = 0.0, fill_y: float = 0.0, fill_z: float = 0.0):
+    """Fused tapered off-diagonal components of the Redi / Gent-McWilliams tensor at u's and at v's points in one pass
+    (xg_redi_horizontal_tensor, include/xgcm_hip_ext.h): the differences of `b` to the column / row before divided by `mx` /
+    `my`; the difference of `b` along Z divided by `mz` at the faces (`outer` False: nz of them, the derivative padded beyond
+    the last; True: nz + 1) and averaged back to the levels, then towards u's and v's points; the other derivative averaged
+    to the centre and towards the point; the two slopes at each point, s2 = sx * sx + sy * sy and `redi_tensor`'s
+    kt = kappa * (slope_max2 / max(s2, slope_max2)); `slope_max2` None: kt = kappa.  `mx` and `my` broadcast against `b`,
+    `mz` against its faces.  Returns (kuz, kvz), of `b`'s shape."""
+    taper = slope_max2 is not None
+    slope_max2 = slope_max2 if taper else 0.0
+    need = "redi_horizontal_tensor: the field needs (Z, Y, X) as its last three dims and a level along Z"
+    return _fused("xg_redi_horizontal_tensor", locals(), lambda p: _faces(p["b"], outer, need))
+
+
 def redi_vertical_flux_divergence(a, kwx, kwy, mx, my, mc, outer: bool, closed: bool, bc_x: str, bc_y: str, bc_z: str,
                                   fill_x: float = 0.0, fill_y: float = 0.0, fill_z: float = 0.0) -> torch.Tensor:
     """Fused divergence of the off-diagonal vertical isoneutral flux of `a` in one pass (xg_redi_vertical_flux_divergence):

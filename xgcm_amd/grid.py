@@ -2331,9 +2331,101 @@ class Grid:
         be None).  For anything else (an array-valued kappa, a numpy scalar of a wider type) the chain above itself runs,
         the same calls in the same order, raising what it raises; neither scalar is validated beyond that."""
         return self._isopycnal(b, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted, tensor=(kappa, slope_max))
-    def _isopycnal(self, b, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted, tensor=None):
+
+    def redi_horizontal_tensor(self, b, kappa=1000.0, slope_max=1e-2, x_axis: str = "X", y_axis: str = "Y", z_axis: str = "Z",
+                               to=None, padding=None, fill_value=None, metric_weighted: bool = True):
+        """The tapered off-diagonal components of the Redi / Gent-McWilliams tensor at the U and the V points, Kuz = kappa
+        taper Sx at u's points and Kvz = kappa taper Sy at v's points -- what the horizontal isoneutral flux
+        Kux da/dx + Kuz <da/dz> needs beside `redi_tensor`'s W-point column -- from b alone in ONE pass: b is read once and
+        the two results written once (24 B/cell in float64, against about 720 for the forty launches of the chain).  The
+        diagonal stays the scalar `kappa` (MITgcm's default unit diagonal); the operator that applies (kappa, Kuz, Kvz) to
+        a tracer is not part of this method.
+
+        b at (lead, Z:center, Y:center, X:center), Z third from last.  Returns (kuz, kvz): `kuz` with dims (lead, Z:center,
+        Y:center, X:left), `kvz` with (lead, Z:center, Y:left, X:center), bit-identical, dims, coords and names included, to
+        the chain
+
+            kw   = dict(padding=padding, fill_value=fill_value)
+            step = grid.derivative if metric_weighted else grid.diff
+            gx   = step(b, x_axis, **kw)                                   # u points
+            gy   = step(b, y_axis, **kw)                                   # v points
+            bzc  = grid.interp(step(b, z_axis, to=to, **kw), z_axis, to="center", **kw)   # db/dz: faces, then back to the levels
+            bzu  = grid.interp(bzc, x_axis, to="left", **kw);   bzv = grid.interp(bzc, y_axis, to="left", **kw)
+            gyu  = grid.interp(grid.interp(gy, y_axis, to="center", **kw), x_axis, to="left", **kw)   # db/dy at u points
+            gxv  = grid.interp(grid.interp(gx, x_axis, to="center", **kw), y_axis, to="left", **kw)   # db/dx at v points
+            sxu, syu = -(gx / bzu),  -(gyu / bzu)
+            sxv, syv = -(gxv / bzv), -(gy / bzv)
+            for (sa, sb, pick) in ((sxu, syu, sxu), (sxv, syv, syv)):      # redi_tensor's taper, at each point with both slopes there
+                s2 = sa * sa + sb * sb
+                if slope_max is None:
+                    kt = kappa
+                else:
+                    m2  = float(slope_max) * float(slope_max)              # as in redi_tensor
+                    ex  = s2 - m2
+                    kt  = kappa * (m2 / (m2 + (ex + abs(ex)) * 0.5))
+                result = kt * pick                                         # kuz = kt_u * sxu,  kvz = kt_v * syv
+
+        every operation in the fields' dtype, no fused multiply-add, IEEE quotients, the negation a product with -1, no
+        guard on a zero db/dz.  `to` is the face position at which db/dz is formed, "left" or "outer"; None resolves as in
+        `isopycnal_slope`.  Every stage pads its own input, as the chain does: with "left" the mean back to the levels
+        pads the derivative beyond the last face; with "outer" no pad along Z is used after b's own.  The pads of bzc, of
+        the centre mean of gy left of column 0 and of the centre mean of gx below row 0 are those stages' own (periodic:
+        the far one, extend: its own, fill: `fill_value` itself).
+
+        `kappa=1.0, slope_max=None` gives the bare slopes at the U and V points exactly, Sx at u's and Sy at v's: the
+        results are 1.0 * s, which carries the bits of s.
+
+        Under `extend` the first and the last level see half the stratification: the outermost face derivative is
+        b - b = 0, so the mean back to the level is half the inner face's and the slopes there are doubled before the
+        taper.  MITgcm's tensor has the same property; nothing is built around it.
+
+        The results are exactly 0 / 0 where the 4-point mean of db/dz cancels: for one level with "outer" under any
+        boundary, for one level with "left" unless Z is `fill`, and for two levels with periodic Z.
+
+        Bound where tapered (s2 > m2): |kuz| and |kvz| <= kappa slope_max (1 + 7 eps), see
+        `tests/test_redi_horizontal_tensor.py` for the count.  The metrics are `isopycnal_slope`'s: X at (lead, Z:center,
+        Y:center, X:left), Y at (lead, Z:center, Y:left, X:center), Z at (lead, Z face, Y:center, X:center), one broadcast
+        array each, each may be absent on its own.
+
+        Out of scope: the tracer operator on (kappa, Kuz, Kvz), a non-unit diagonal, other tapers, land masks and partial
+        cells.
+
+        The one pass serves exactly the calls that `isopycnal_slope`'s one pass serves (the list in its docstring) with
+        `kappa` and `slope_max` each a Python int or float, or a numpy floating scalar that does not promote the fields'
+        dtype (`slope_max` may be None).  For everything else the chain above itself runs, the same calls in the same
+        order, raising what it raises."""
+        return self._isopycnal(b, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted, tensor=(kappa, slope_max),
+                               horizontal=True)
+
+    def _redi_horizontal_chain(self, b, kappa, slope_max, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted):
+        """the chain of `redi_horizontal_tensor`'s docstring, call by call (`to` already resolved): every fallback of the one pass"""
+        kw = dict(padding=padding, fill_value=fill_value)
+        step = self.derivative if metric_weighted else self.diff
+        gx = step(b, x_axis, **kw)
+        gy = step(b, y_axis, **kw)
+        bzc = self.interp(step(b, z_axis, to=to, **kw), z_axis, to="center", **kw)
+        bzu = self.interp(bzc, x_axis, to="left", **kw)
+        bzv = self.interp(bzc, y_axis, to="left", **kw)
+        gyu = self.interp(self.interp(gy, y_axis, to="center", **kw), x_axis, to="left", **kw)
+        gxv = self.interp(self.interp(gx, x_axis, to="center", **kw), y_axis, to="left", **kw)
+        sxu, syu = -(gx / bzu), -(gyu / bzu)
+        sxv, syv = -(gxv / bzv), -(gy / bzv)
+        outs = []
+        for sa, sb, pick in ((sxu, syu, sxu), (sxv, syv, syv)):
+            s2 = sa * sa + sb * sb
+            if slope_max is None:
+                kt = kappa
+            else:
+                m2 = float(slope_max) * float(slope_max)
+                ex = s2 - m2
+                den = m2 + (ex + abs(ex)) * 0.5
+                kt = kappa * (m2 / den)
+            outs.append(kt * pick)
+        return tuple(outs)
+
+    def _isopycnal(self, b, x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted, tensor=None, horizontal=False):
         """`isopycnal_slope`: one launch of K7q, or its chain.  `tensor` (kappa, slope_max): `redi_tensor`, one launch of
-        K7r, or its chain"""
+        K7r, or its chain; with `horizontal`: `redi_horizontal_tensor`, one launch of K7u, or its chain"""
         arg, to_arg = b, to
         b, was_xr = self._wrap_in(b)
         zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
@@ -2374,6 +2466,8 @@ class Grid:
         if plan is not None and tensor is not None and not (_weak_scalar(tensor[0], b.data)
                                                             and (tensor[1] is None or _weak_scalar(tensor[1], b.data))):
             plan = None   # (an array, a wider numpy scalar: the chain's own promotion)
+        if plan is None and horizontal:
+            return self._redi_horizontal_chain(arg, tensor[0], tensor[1], x_axis, y_axis, z_axis, to, padding, fill_value, metric_weighted)
         if plan is None and tensor is not None:
             kappa, slope_max = tensor
             kw = dict(padding=padding, fill_value=fill_value)
@@ -2397,7 +2491,10 @@ class Grid:
         bcx, bcy, fvx, fvy, bcz, fvz = plan
         host = not _is_tensor(b.data)
         mx, my, mz = (None if m is None else _aligned_view(m, dims) for m, dims in zip(mets, m_dims))
-        if tensor is not None:
+        if horizontal:
+            m2 = None if tensor[1] is None else float(tensor[1]) * float(tensor[1])
+            outs = _dev.redi_horizontal_tensor(b.data, mx, my, mz, float(tensor[0]), m2, to == "outer", bcx, bcy, bcz, fvx, fvy, fvz)
+        elif tensor is not None:
             m2 = None if tensor[1] is None else float(tensor[1]) * float(tensor[1])
             outs = _dev.redi_tensor(b.data, mx, my, mz, float(tensor[0]), m2, to == "outer", bcx, bcy, bcz, fvx, fvy, fvz)
         else:
@@ -2409,6 +2506,21 @@ class Grid:
             return g if m is None else g._replace(name=_name_after(g.name, m))
 
         bz = named(self._labels_of_step(b, m_dims[2], zf, f_shape), mets[2])
+        if horizontal:
+            # the two derivatives, db/dz back at the levels and at the two points, the cross means, the four quotients; then
+            # the taper's steps as below
+            step, both = self._labels_of_step, self._labels_of_binary
+            gx, gy = named(step(b, m_dims[0], xl), mets[0]), named(step(b, m_dims[1], yl), mets[1])
+            bzc = step(bz, c_dims, tz, b.shape)
+            bzu, bzv = step(bzc, m_dims[0], xl), step(bzc, m_dims[1], yl)
+            gyu = step(step(gy, c_dims, yc), m_dims[0], xl)
+            gxv = step(step(gx, c_dims, xc), m_dims[1], yl)
+            res = []
+            for sa, sb, own in ((both(gx, bzu), both(gyu, bzu), 0), (both(gxv, bzv), both(gy, bzv), 1)):
+                pick = (sa, sb)[own]
+                res.append(pick if tensor[1] is None else both(both(both(sa, sa), both(sb, sb)), pick))
+            outs = tuple(r._replace(data=_dev.tohost(out) if host else out) for r, out in zip(res, outs))
+            return tuple(to_xarray(r) for r in outs) if was_xr else outs
         res = []
         for k, (dim_l, dim_c) in enumerate(((xl, xc), (yl, yc))):
             g = named(self._labels_of_step(b, m_dims[k], dim_l), mets[k])
