@@ -58,7 +58,10 @@
  *   xg_redi_tensor      kappa * taper * (sx, sy, sx^2 + sy^2) of those slopes, the taper min(1, m2 / s2): one pass (likewise)
  *   xg_redi_vertical_flux_divergence  d/dz(kwx * gx + kwy * gy) of a tracer, gx and gy its level means at the faces: one
  *                      pass (likewise)
- *   (the Gent-McWilliams eddy-induced velocity from xg_redi_tensor's results: include/xgcm_hip_gm.h)
+ *   xg_bolus_velocity   -d/dz of the Gent-McWilliams streamfunction (interp(kwx, X), interp(kwy, Y)) and its horizontal
+ *                      divergence: the eddy-induced (u*, v*, w*), one pass (likewise)
+ *   xg_redi_horizontal_tensor  kappa * taper * sx at u's points and kappa * taper * sy at v's, from b alone: one pass
+ *                      (likewise)
  *   xg_*_i64           the same bodies on integer arrays, which numpy keeps integral and wraps
  *                      (xgcm/gridops.py:23-24,123-126,172-175,227-278; xgcm/padding.py:610-615)
  *   xg_convert         numpy's dtype promotion / `astype` around them (int * float metric: xgcm/grid.py:804-808)
@@ -577,6 +580,48 @@ int xg_redi_vertical_flux_divergence(int dtype, const void* a, const void* kwx, 
                                      const int64_t* mx_strides, const void* my, const int64_t* my_strides, const void* mc,
                                      const int64_t* mc_strides, void* out, const int64_t* shape, int ndim, int outer, int closed,
                                      int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
+/* The Gent-McWilliams eddy-induced (bolus) velocity from xg_redi_tensor's kwx and kwy, one pass.  `shape` (.., nz, ny, nx) is
+ * the LEVELS' shape; kwx, kwy and out_w are contiguous at the faces of Z, nz of them (`outer` = 1: nz + 1); out_u and out_v
+ * have `shape`.
+ *   px[i] = (kwx[i-1] + kwx[i]) * 0.5    py[j] = (kwy[j-1] + kwy[j]) * 0.5      the streamfunction at u's / v's columns
+ *   closed = 1: px = py = +0.0 at face 0 and, `outer`, at face nz; kwx and kwy are never read there
+ *   out_u[k] = -1 * ((px[k+1] - px[k]) [/ mzu[k]])    out_v[k] = -1 * ((py[k+1] - py[k]) [/ mzv[k]])
+ *   tx = px [* dyG]    ty = py [* dxG]    out_w = ((tx[i+1] - tx[i]) + (ty[j+1] - ty[j])) [/ rA]
+ * no fused multiply-add, IEEE quotients.  Pads: kwx left of column 0 and kwy below row 0 (periodic: the far one, extend:
+ * itself, fill: the fill value); the TRANSPORTS tx right of the last column and ty above the last row (periodic: the one at
+ * index 0, extend: at n-1, fill: the fill value itself, not multiplied by a metric); `outer` = 0: px and py beyond face nz-1
+ * (periodic: face 0's -- closed: +0.0 --, extend: face nz-1's, fill: fill_z itself).  A closed face of out_w is formed from
+ * +0.0 through the same products, differences and quotient.  mzu and mzv broadcast against `shape`; dyG, dxG and rA against
+ * `shape` with the faces along Z; strides in elements, 0 = broadcast; NULL: absent, each on its own.  The fills are cast to
+ * the element type (-0.0 and NaN keep their bits).  XG_ERR_UNSUPPORTED: ndim < 3.  XG_ERR_INVALID: an element type other than
+ * XG_T_F64 / XG_T_F32, a NULL kwx, kwy, result or shape, a metric without strides, outer or closed not 0 or 1, an unknown
+ * boundary code, nz < 1; the results are untouched then.  An empty result is XG_OK without a launch. */
+int xg_bolus_velocity(int dtype, const void* kwx, const void* kwy, const void* mzu, const int64_t* mzu_strides, const void* mzv,
+                      const int64_t* mzv_strides, const void* dyG, const int64_t* dyG_strides, const void* dxG,
+                      const int64_t* dxG_strides, const void* rA, const int64_t* rA_strides, void* out_u, void* out_v,
+                      void* out_w, const int64_t* shape, int ndim, int outer, int closed, int bc_x, double fill_x, int bc_y,
+                      double fill_y, int bc_z, double fill_z, void* stream);
+/* The U- and V-point components of the tapered Redi / Gent-McWilliams tensor of a field b of `shape` (.., nz, ny, nx), one
+ * pass; out_u (at u's points: left of the cell along X) and out_v (at v's: below it along Y) have `shape`.
+ *   gx[i] = (b[i] - b[i-1]) [/ mx]     gy[j] = (b[j] - b[j-1]) [/ my]        f[k] = (b[k] - b[k-1]) [/ mz[k]]   (faces of Z)
+ *   bzc[k] = (f[k] + f[k+1]) * 0.5     bzu[i] = (bzc[i-1] + bzc[i]) * 0.5    bzv[j] = (bzc[j-1] + bzc[j]) * 0.5
+ *   gyc[j] = (gy[j] + gy[j+1]) * 0.5   gyu[i] = (gyc[i-1] + gyc[i]) * 0.5     gxc[i] = (gx[i] + gx[i+1]) * 0.5   gxv[j] = (gxc[j-1] + gxc[j]) * 0.5
+ *   at u's points sx = -1 * (gx / bzu), sy = -1 * (gyu / bzu);  at v's points sx = -1 * (gxv / bzv), sy = -1 * (gy / bzv)
+ *   s2 = sx * sx + sy * sy     kt = kappa * (m2 / (m2 + ((s2 - m2) + |s2 - m2|) * 0.5))     (`taper` = 0: kt = kappa)
+ *   out_u = kt * sx at u's points     out_v = kt * sy at v's points
+ * no fused multiply-add, IEEE quotients, no guard on a zero bzu or bzv.  `outer` = 0: nz faces, f[nz] is the pad of f
+ * (periodic: f[0], extend: f[nz-1], fill: fill_z itself); `outer` = 1: nz + 1 faces, b padded above level 0 and below level
+ * nz-1 and no pad of f.  Every stage pads its own input: b left of column 0, below row 0 and along Z (periodic: the far one,
+ * extend: its own, fill: the fill value); gx right of the last column and gy above the last row; bzc and gyc left of column 0,
+ * bzc and gxc below row 0 (fill: the fill value ITSELF, never formed from padded b).  mx and my broadcast against `shape`, mz
+ * against `shape` with the faces along Z; NULL: absent, each on its own.  kappa, slope_max2 (= m2) and the fills are cast to
+ * the element type once (-0.0 and NaN fills keep their bits).  XG_ERR_UNSUPPORTED: ndim < 3.  XG_ERR_INVALID: an element type
+ * other than XG_T_F64 / XG_T_F32, a NULL b, result or shape, a metric without strides, outer or taper not 0 or 1, an unknown
+ * boundary code, nz < 1, results that overlap; the results are untouched then.  An empty result is XG_OK without a launch. */
+int xg_redi_horizontal_tensor(int dtype, const void* b, const void* mx, const int64_t* mx_strides, const void* my,
+                              const int64_t* my_strides, const void* mz, const int64_t* mz_strides, double kappa,
+                              double slope_max2, int taper, void* out_u, void* out_v, const int64_t* shape, int ndim, int outer,
+                              int bc_x, double fill_x, int bc_y, double fill_y, int bc_z, double fill_z, void* stream);
 
 /* ---- the momentum side: kinetic energy and the vector-invariant advection term, one pass each ---- */
 /* Arrays of identical `shape` (.., Y, X): u at (Y:center, X:left), v at (Y:left, X:center).

@@ -862,7 +862,7 @@ def _abi_call(D, dtype, shape, kws, planes, k, off=ALIGNED):
         bufs.append((torch.full((off + n + ALIGNED,), TR.SENTINEL, dtype=TR.TORCH[dtype], device=D._MEM.device), n, s))
         args.append(bufs[-1][0][off:off + n].data_ptr())
     args += [_hip.i64(shape), len(shape), int(to == "outer"), closed, _hip.BC[px], FILL["X"], _hip.BC[py], FILL["Y"], _hip.BC[pz], FILL["Z"]]
-    D._check(_hip.entry(D._MEM.lib(), "xg_bolus_velocity")(*args, D._stream()))
+    D._check(getattr(D._MEM.lib(), "xg_bolus_velocity")(*args, D._stream()))
     outs = []
     for buf, n, s in bufs:
         whole = buf.cpu().numpy()
@@ -964,7 +964,7 @@ def abi_bad_calls():
     def call(code=TR.CODE[np.float64], kwx=kw, kwy=kw, o=outs, shape=shape, ndim=3, outer=0, closed=1, bcx=_hip.BC["periodic"],
              bcy=_hip.BC["extend"], bcz=_hip.BC["fill"], mets=(None,) * 5, strides=(None,) * 5):
         margs = [x for pair in zip(mets, strides) for x in pair]
-        return _hip.entry(lib, "xg_bolus_velocity")(code, P(kwx), P(kwy), *margs, *[P(x) for x in o], None if shape is None else _hip.i64(shape),
+        return getattr(lib, "xg_bolus_velocity")(code, P(kwx), P(kwy), *margs, *[P(x) for x in o], None if shape is None else _hip.i64(shape),
                                      ndim, outer, closed, bcx, 0.0, bcy, 0.0, bcz, 0.0, D._stream())
 
     untouched = lambda: all(bool((x == TR.SENTINEL).all()) for x in outs)  # noqa: E731
@@ -1011,52 +1011,31 @@ def test_the_device_wrapper_refuses_fields_of_different_shapes_and_no_level(host
         D.bolus_velocity(np.zeros((4, 6)), np.zeros((4, 6)), None, None, None, None, None, False, True, "periodic", "fill", "extend")
 
 
-def gm_prototypes():
-    """name -> (return type, [(type, parameter name), ...]) of every prototype of include/xgcm_hip_gm.h, read as
-    tests/test_host_logic.py reads include/xgcm_hip.h"""
-    import os
-    import re
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "include", "xgcm_hip_gm.h")).read()
-    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-    protos = {}
-    for ret, name, params in re.findall(r"^\s*((?:int|void)\s*\*?)\s*(xg_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        pairs = []
-        for q in [q.strip() for q in params.split(",") if q.strip() not in ("", "void")]:
-            ctype, pname = re.fullmatch(r"(.*?)(\w+)", q, flags=re.S).groups()
-            pairs.append((re.sub(r"\bconst\b|\bstruct\b|\s+", "", ctype), pname))
-        protos[name] = (ret.replace(" ", ""), pairs)
-    return protos
-
-
 def test_the_second_header_its_table_and_both_libraries_agree():
-    """include/xgcm_hip_gm.h declares exactly the entries of `_hip.GM_SIGNATURES`, none of them is in `_hip.SIGNATURES` (the
-    export list of include/xgcm_hip.h), each is bound parameter by parameter as the header has it, the row names its slots
-    as the header names the parameters, and both builds export it"""
+    """include/xgcm_hip.h declares xg_bolus_velocity, `_hip.SIGNATURES` binds it parameter by parameter as the header has
+    it, its row is `_hip.FUSED`'s and names its slots as the header names the parameters, and both builds export it"""
     import ctypes as C
     import os
 
     import test_fused_marshalling as TM
 
-    protos = gm_prototypes()
-    assert set(protos) == set(_hip.GM_SIGNATURES) == set(_hip.FUSED_AT_FACES) == {"xg_bolus_velocity"}
-    assert not set(protos) & set(_hip.SIGNATURES) and not set(protos) & set(_hip.FUSED)
+    protos = {"xg_bolus_velocity": TM.PROTOS["xg_bolus_velocity"]}
+    assert set(protos) <= set(_hip.SIGNATURES) and set(protos) <= set(_hip.FUSED)
     scalars = {"int": C.c_int, "double": C.c_double}
     for name, (ret, params) in protos.items():
-        res, args = _hip.GM_SIGNATURES[name]
+        res, args = _hip.SIGNATURES[name]
         assert ret == "int" and res is C.c_int and len(args) == len(params)
         for (ctype, pname), a in zip(params, args):
             if ctype.endswith("*"):
                 assert a is C.c_void_p or (ctype == "int64_t*" and a._type_ is C.c_int64), (name, pname)
             else:
                 assert a is scalars[ctype], (name, pname)
-        row = _hip.FUSED_AT_FACES[name]
+        row = _hip.FUSED[name]
         assert _hip.forms(name) == [(name, False)] and TM._slot_names(row, False) == [pname for _, pname in params]
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for lib in ("libxgcm_hip.so", "libxgcm_host.so"):
         assert hasattr(C.CDLL(os.path.join(root, "xgcm_amd", lib)), "xg_bolus_velocity")
-    assert _hip.load().xg_bolus_velocity.argtypes == _hip.GM_SIGNATURES["xg_bolus_velocity"][1]
+    assert _hip.load().xg_bolus_velocity.argtypes == _hip.SIGNATURES["xg_bolus_velocity"][1]
 
 
 def test_argument_order_through_the_recording_library(monkeypatch):
@@ -1079,7 +1058,6 @@ def test_argument_order_through_the_recording_library(monkeypatch):
     for n, m in mets.items():
         expected[n] = m.data_ptr()
         expected[n + "_strides"] = tuple(0 if s == 1 else st for s, st in zip(m.shape, m.stride()))
-    monkeypatch.setitem(TM.PROTOS, "xg_bolus_velocity", gm_prototypes()["xg_bolus_velocity"])
     TM._check_call(mem.recorder, "xg_bolus_velocity", expected)
 
 

@@ -159,4 +159,4 @@ def test_every_row_names_its_slots_as_the_header_names_the_parameters():
             for full in [entry] if row.typed else [entry + "_f64", entry + "_f32"]:
                 assert _slot_names(row, halo) == [pname for _, pname in PROTOS[full][1]], full
                 seen += 1
-    assert seen == 2 * 17 + 8  # 13 pairs and their four `_halo` forms, eight typed entries
+    assert seen == 2 * 17 + 10  # 13 pairs and their four `_halo` forms, ten typed entries

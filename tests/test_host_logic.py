@@ -243,7 +243,7 @@ def test_c_abi_signatures_match_the_header_parameter_by_parameter():
                "double": C.c_double, "float": C.c_float}
     pointees = dict(scalars, **{"void*": C.c_void_p, "xg_multi_desc": _hip.MultiDesc})
     protos = header_prototypes()
-    assert len(protos) == len(_hip.SIGNATURES) == 117
+    assert len(protos) == len(_hip.SIGNATURES) == 119
     wrong = []
     for name, (ret, params) in protos.items():
         res, args = _hip.SIGNATURES[name]

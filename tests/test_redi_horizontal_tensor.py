@@ -26,7 +26,6 @@ slope_max * slope_max cast to the dtype (sqrt(m2) is within eps / 2 of slope_max
 
 import itertools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -787,7 +786,7 @@ def _abi_call(D, dtype, shape, b, planes, k, offs=(ALIGNED, ALIGNED)):
     bufs = [torch.full((off + n + ALIGNED,), TR.SENTINEL, dtype=TR.TORCH[dtype], device=D._MEM.device) for off in offs]
     args += [buf[off:off + n].data_ptr() for buf, off in zip(bufs, offs)]
     args += [_hip.i64(shape), len(shape), int(to == "outer"), _hip.BC[px], FILL["X"], _hip.BC[py], FILL["Y"], _hip.BC[pz], FILL["Z"]]
-    D._check(_hip.entry(D._MEM.lib(), "xg_redi_horizontal_tensor")(*args, D._stream()))
+    D._check(getattr(D._MEM.lib(), "xg_redi_horizontal_tensor")(*args, D._stream()))
     res = []
     for buf, off in zip(bufs, offs):
         whole = buf.cpu().numpy()
@@ -871,7 +870,7 @@ def abi_bad_calls():
     The refusals are xg_redi_tensor's"""
     import xgcm_amd.device as D
 
-    fn = _hip.entry(D._MEM.lib(), "xg_redi_horizontal_tensor")
+    fn = getattr(D._MEM.lib(), "xg_redi_horizontal_tensor")
     shape = [2, 3, 4]
     t = torch.ones(shape, dtype=torch.float64, device=D._MEM.device)
     outs = [torch.full(shape, TR.SENTINEL, dtype=torch.float64, device=D._MEM.device) for _ in range(2)]
@@ -929,54 +928,36 @@ def test_the_device_wrapper_refuses_a_field_without_a_level(host_abi):
         D.redi_horizontal_tensor(np.zeros((0, 4, 6)), None, None, None, 1000.0, None, False, "periodic", "fill", "extend")
 
 
-def ext_prototypes():
-    """name -> (return type, [(type, parameter name), ...]) of every prototype of include/xgcm_hip_ext.h, read as
-    tests/test_host_logic.py reads include/xgcm_hip.h"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "include", "xgcm_hip_ext.h")).read()
-    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-    protos = {}
-    for ret, name, params in re.findall(r"^\s*((?:int|void)\s*\*?)\s*(xg_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        pairs = []
-        for q in [q.strip() for q in params.split(",") if q.strip() not in ("", "void")]:
-            ctype, pname = re.fullmatch(r"(.*?)(\w+)", q, flags=re.S).groups()
-            pairs.append((re.sub(r"\bconst\b|\bstruct\b|\s+", "", ctype), pname))
-        protos[name] = (ret.replace(" ", ""), pairs)
-    return protos
-
-
 def test_the_extension_header_its_table_and_both_libraries_agree():
-    """include/xgcm_hip_ext.h declares exactly the entries of `_hip.EXT_SIGNATURES`, whatever their number; none of them is in
-    `_hip.SIGNATURES` or `_hip.GM_SIGNATURES` (the export lists of the two other headers); each is bound parameter by
-    parameter as the header has it, the row names its slots as the header names the parameters, `_hip.ROWS` includes it, both
-    builds export it and `_hip.entry` types it lazily"""
+    """include/xgcm_hip.h declares xg_redi_horizontal_tensor; `_hip.SIGNATURES` binds each of its forms parameter by
+    parameter as the header has it, its row is `_hip.FUSED`'s and names its slots as the header names the parameters, both
+    builds export it, and whoever opens a build types it with the row's argtypes"""
     import ctypes as C
 
+    import host_abi_device
     import test_fused_marshalling as TM
 
-    protos = ext_prototypes()
-    assert "xg_redi_horizontal_tensor" in protos
-    assert set(protos) == set(_hip.EXT_SIGNATURES) == {e for name in _hip.FUSED_EXT for e, _ in _hip.forms(name)}
-    assert not set(protos) & (set(_hip.SIGNATURES) | set(_hip.GM_SIGNATURES) | set(_hip.FUSED) | set(_hip.FUSED_AT_FACES))
+    protos = TM.PROTOS
+    name = "xg_redi_horizontal_tensor"
+    assert name in protos and name in _hip.SIGNATURES
     scalars = {"int": C.c_int, "double": C.c_double}
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    libs = [C.CDLL(os.path.join(root, "xgcm_amd", lib)) for lib in ("libxgcm_hip.so", "libxgcm_host.so")]
-    for name, row in _hip.FUSED_EXT.items():
-        assert row.typed and _hip.ROWS[name] is row
-        for entry, halo in _hip.forms(name):
-            ret, params = protos[entry]
-            res, args = _hip.EXT_SIGNATURES[entry]
-            assert ret == "int" and res is C.c_int and len(args) == len(params)
-            for (ctype, pname), a in zip(params, args):
-                if ctype.endswith("*"):
-                    assert a is C.c_void_p or (ctype == "int64_t*" and a._type_ is C.c_int64), (entry, pname)
-                else:
-                    assert a is scalars[ctype], (entry, pname)
-            assert TM._slot_names(row, halo) == [pname for _, pname in params]
-            for lib in libs:
-                assert hasattr(lib, entry)
-                assert _hip.entry(lib, entry).argtypes == args
-    row = _hip.FUSED_EXT["xg_redi_horizontal_tensor"]
+    for lib in ("libxgcm_hip.so", "libxgcm_host.so"):
+        assert hasattr(C.CDLL(os.path.join(root, "xgcm_amd", lib)), name)
+    row = _hip.FUSED[name]
+    assert row.typed and _hip.forms(name) == [(name, False)]
+    for entry, halo in _hip.forms(name):
+        ret, params = protos[entry]
+        res, args = _hip.SIGNATURES[entry]
+        assert ret == "int" and res is C.c_int and len(args) == len(params)
+        for (ctype, pname), a in zip(params, args):
+            if ctype.endswith("*"):
+                assert a is C.c_void_p or (ctype == "int64_t*" and a._type_ is C.c_int64), (entry, pname)
+            else:
+                assert a is scalars[ctype], (entry, pname)
+        assert TM._slot_names(row, halo) == [pname for _, pname in params]
+        for lib in (_hip.load(), host_abi_device.lib()):
+            assert getattr(lib, entry).argtypes == args
     assert [s.name for s in row.slots if s.kind == "result"] == ["out_u", "out_v"] and all(s.at == "shape" for s in row.slots if s.kind == "result")
     assert [s.name for s in row.slots if s.kind == "real"] == ["kappa", "slope_max2"]
 
@@ -999,7 +980,6 @@ def test_argument_order_through_the_recording_library(monkeypatch):
     for n, m in mets.items():
         expected[n] = m.data_ptr()
         expected[n + "_strides"] = tuple(0 if s == 1 else st for s, st in zip(m.shape, m.stride()))
-    monkeypatch.setitem(TM.PROTOS, "xg_redi_horizontal_tensor", ext_prototypes()["xg_redi_horizontal_tensor"])
     TM._check_call(mem.recorder, "xg_redi_horizontal_tensor", expected)
 
 

@@ -8,7 +8,7 @@
 #include <cstring>
 #include <cstdint>
 #include <cmath>
-#include "include/xgcm_hip_ext.h"
+#include "include/xgcm_hip.h"
 
 template <typename R> static R* block(int64_t n, unsigned seed, double lo, double hi) {
   R* p = (R*)malloc((size_t)(n > 0 ? n : 1) * sizeof(R));

@@ -218,33 +218,22 @@ FUSED = {
     "xg_redi_vertical_flux_divergence": Row("redi_vertical_flux_divergence", _fields("a") + _fields("kwx", "kwy", at="faces")
                                             + _metrics(("mx", "X metric"), ("my", "Y metric"), ("mc", "Z metric at the centre"))
                                             + _results("out") + _SHAPE + _of("flag", "outer", "closed") + _bc("x", "y", "z") + _STREAM, True),
-}
-for _name in ("vorticity", "divergence"):
-    FUSED["xg_" + _name] = Row(_name, _fields("u", "v") + _HALOS + _metrics("area") + _results("out") + _XY + _STREAM)
-
-
-# The entries of include/xgcm_hip_gm.h: rows whose `shape` no field has -- every field sits at the faces of Z and `shape`, the
-# levels' shape, comes from the wrapper's check.  A table of their own, as the header is: FUSED's rows all measure their
-# results against a field at "shape", and SIGNATURES is the export list of include/xgcm_hip.h alone.
-FUSED_AT_FACES = {
+    # every field at the faces of Z: `shape`, the levels', is no field's and comes from the wrapper's check (device._Plan.base)
     "xg_bolus_velocity": Row("bolus_velocity", _fields("kwx", "kwy", at="faces")
                              + _metrics(("mzu", "Z metric at u's points"), ("mzv", "Z metric at v's points"))
                              + _metrics(("dyG", "Y metric at u's points"), ("dxG", "X metric at v's points"), ("rA", "area"), at="faces")
                              + _results("out_u", "out_v") + _results("out_w", at="faces") + _SHAPE + _of("flag", "outer", "closed")
                              + _bc("x", "y", "z") + _STREAM, True, ("kwx", "kwy")),
-}
-# The entries of include/xgcm_hip_ext.h, the open-ended home of every later fused entry point: FUSED and FUSED_AT_FACES are
-# held to fixed sets, as their two headers are, so a new row goes HERE and its prototype there.  Rows of FUSED's kind.
-FUSED_EXT = {
     "xg_redi_horizontal_tensor": Row("redi_horizontal_tensor", _SLOPE + _of("real", "kappa", "slope_max2") + _of("flag", "taper")
                                      + _results("out_u", "out_v") + _OUTER_XYZ + _STREAM, True),
 }
-ROWS = {**FUSED, **FUSED_AT_FACES, **FUSED_EXT}
+for _name in ("vorticity", "divergence"):
+    FUSED["xg_" + _name] = Row(_name, _fields("u", "v") + _HALOS + _metrics("area") + _results("out") + _XY + _STREAM)
 
 
 def forms(name: str):
     """(entry, has the halo slots) of the forms of row `name`: itself, and `_halo` where the row has halo slots"""
-    return [(name, False)] + [(name + "_halo", True)] * any(s.kind == "halo" for s in ROWS[name].slots)
+    return [(name, False)] + [(name + "_halo", True)] * any(s.kind == "halo" for s in FUSED[name].slots)
 
 
 def _argtypes(row: Row, halo: bool, real):
@@ -256,16 +245,9 @@ def _argtypes(row: Row, halo: bool, real):
     return args
 
 
-GM_SIGNATURES = {}   # name -> (restype, argtypes); the export list of include/xgcm_hip_gm.h
-EXT_SIGNATURES = {}  # ... and of include/xgcm_hip_ext.h (typed entries only)
-for _name, _row in ROWS.items():
+for _name, _row in FUSED.items():
     for _entry, _halo in forms(_name):
-        if _name in FUSED_AT_FACES:
-            GM_SIGNATURES[_entry] = (C.c_int, _argtypes(_row, _halo, C.c_double))
-        elif _name in FUSED_EXT:
-            assert _row.typed, _name
-            EXT_SIGNATURES[_entry] = (C.c_int, _argtypes(_row, _halo, C.c_double))
-        elif _row.typed:
+        if _row.typed:
             SIGNATURES[_entry] = (C.c_int, _argtypes(_row, _halo, C.c_double))
         else:
             SIGNATURES[_entry + "_f64"] = (C.c_int, _argtypes(_row, _halo, C.c_double))
@@ -312,26 +294,14 @@ def load() -> C.CDLL:
             "xgcm_amd has no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **GM_SIGNATURES}.items():
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
-    for name in EXT_SIGNATURES:  # (typed lazily, by `entry`; a build without one of them is no build of this ABI)
-        getattr(lib, name)
     if lib.xg_version() != 1:
         raise ImportError(f"libxgcm_hip.so ABI version {lib.xg_version()} != 1")
     _lib = lib
     return lib
-
-
-def entry(lib, name: str):
-    """the entry `name` of a build of the ABI, typed: whoever opened `lib` typed the entries of SIGNATURES; one of
-    GM_SIGNATURES or EXT_SIGNATURES is typed here, on its first use, on whichever build serves the call"""
-    fn = getattr(lib, name)
-    sig = GM_SIGNATURES.get(name) or EXT_SIGNATURES.get(name)
-    if sig is not None and getattr(fn, "argtypes", None) is None:
-        fn.restype, fn.argtypes = sig
-    return fn
 
 
 def set_tunable(name: str, value: int) -> None:

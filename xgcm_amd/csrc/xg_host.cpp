@@ -26,8 +26,6 @@
 #include <vector>
 
 #include "../../include/xgcm_hip.h"
-#include "../../include/xgcm_hip_gm.h"
-#include "../../include/xgcm_hip_ext.h"
 
 namespace {
 
@@ -1165,7 +1163,7 @@ int rediflux(const R* a, const R* kwx, const R* kwy, const R* const arr[3], cons
   return XG_OK;
 }
 
-// the U- and V-point components of the tapered tensor of the header (xgcm_hip_ext.h) as the stages of their chain over one
+// the U- and V-point components of the tapered tensor of the header as the stages of their chain over one
 // (Z, Y, X) volume at a time, each into a temporary: the differences along X and Y over their metrics; b's difference along Z
 // at the faces over its metric and its mean back to the levels; the means of that towards u's and v's points; the centre
 // means of the two differences and their means towards the other point; the four quotients, negated; the taper at each

@@ -4,8 +4,6 @@
 #include <initializer_list>
 
 #include "xg_common.hpp"
-#include "../../include/xgcm_hip_gm.h"
-#include "../../include/xgcm_hip_ext.h"
 
 // rows of Y per wave-task of the fused two-component kernels (see STENCIL_SEG in xg_stencil.hip): A/B on one GPU
 // (XG_HIP_LIB), 4320 x 4320 x 90: vorticity 70.0 / 71.7 / 71.3 % with 4 / 2 / 1 rows, gradient 73.9 / 75.7 / 75.6 %,
@@ -2909,7 +2907,7 @@ __global__ __launch_bounds__(BLOCK) void k_bolus(
 
 // ------------------------------------------------------------------------------------------
 // K7u: the tapered off-diagonal components of the Redi / Gent-McWilliams tensor at u's and v's points in ONE pass over
-// (lead, Z, Y, X), one field in, two out at the levels (include/xgcm_hip_ext.h):
+// (lead, Z, Y, X), one field in, two out at the levels (include/xgcm_hip.h):
 //   gx[i] = (b[i] - b[i-1]) [/ mx]    gy[j] = (b[j] - b[j-1]) [/ my]    f[k] = (b[k] - b[k-1]) [/ mz[k]]     bzc[k] = (f[k] + f[k+1]) * 0.5
 //   bzu[i] = (bzc[i-1] + bzc[i]) * 0.5          bzv[j] = (bzc[j-1] + bzc[j]) * 0.5
 //   gyu[i] = (gyc[i-1] + gyc[i]) * 0.5, gyc[j] = (gy[j] + gy[j+1]) * 0.5        gxv[j] = (gxc[j-1] + gxc[j]) * 0.5, gxc[i] = (gx[i] + gx[i+1]) * 0.5

@@ -1329,7 +1329,7 @@ def _binary_blockwise(op: str, a, b):
 
 
 class _Plan(NamedTuple):
-    """one form of a row of _hip.FUSED / _hip.FUSED_AT_FACES, resolved for `_fused` once at import"""
+    """one form of a row of _hip.FUSED, resolved for `_fused` once at import"""
 
     names: dict      # ABI suffix -> the entry's name (a typed entry has one name and takes the `dtype` code first)
     arrays: tuple    # every array slot of the ROW: the halo slabs count towards the dtype whichever form is called
@@ -1377,7 +1377,7 @@ def _plan(row, entry: str, halo: bool) -> _Plan:
         results=tuple((s.name, s.at) for s in slots if s.kind == "result"), call=tuple(call))
 
 
-_PLANS = {entry: _plan(row, entry, halo) for name, row in _hip.ROWS.items() for entry, halo in _hip.forms(name)}
+_PLANS = {entry: _plan(row, entry, halo) for name, row in _hip.FUSED.items() for entry, halo in _hip.forms(name)}
 _DTYPE_CODE = {"f64": _hip.DTYPE["float64"], "f32": _hip.DTYPE["float32"]}
 
 
@@ -1415,7 +1415,7 @@ def _fused(entry: str, v: dict, check=None):
         for n, strides, at, what in metrics:
             v[strides] = _hip.i64(_bstrides(v[n], shapes[at], what))
         v["dtype"], v["shape"], v["ndim"], v["stream"] = _DTYPE_CODE[sfx], _hip.i64(shape), len(shape), _stream()
-        _check(_hip.entry(lib, names[sfx])(*[v[n] if arg is None else arg(v[n]) for n, arg in call]))
+        _check(getattr(lib, names[sfx])(*[v[n] if arg is None else arg(v[n]) for n, arg in call]))
     return outs[0] if len(outs) == 1 else tuple(outs)
 
 
@@ -1592,7 +1592,7 @@ def redi_tensor(b, mx, my, mz, kappa: float, slope_max2, outer: bool, bc_x: str,
 def redi_horizontal_tensor(b, mx, my, mz, kappa: float, slope_max2, outer: bool, bc_x: str, bc_y: str, bc_z: str,
                            fill_x: float = 0.0, fill_y: float = 0.0, fill_z: float = 0.0):
     """Fused tapered off-diagonal components of the Redi / Gent-McWilliams tensor at u's and at v's points in one pass
-    (xg_redi_horizontal_tensor, include/xgcm_hip_ext.h): the differences of `b` to the column / row before divided by `mx` /
+    (xg_redi_horizontal_tensor, include/xgcm_hip.h): the differences of `b` to the column / row before divided by `mx` /
     `my`; the difference of `b` along Z divided by `mz` at the faces (`outer` False: nz of them, the derivative padded beyond
     the last; True: nz + 1) and averaged back to the levels, then towards u's and v's points; the other derivative averaged
     to the centre and towards the point; the two slopes at each point, s2 = sx * sx + sy * sy and `redi_tensor`'s

@@ -29,7 +29,7 @@ import operator
 import threading
 import warnings
 from collections import OrderedDict
-from typing import Any, Dict, Iterable, List, Mapping, Optional, Tuple
+from typing import Any, Dict, Iterable, List, Mapping, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -64,6 +64,23 @@ def _name_after(name, *metrics):
         if m is not None and getattr(m, "name", None) != name:
             return None
     return name
+
+
+def named(g, m):
+    """`g`, named after its quotient or product with the metric `m` (None: `g` as it is)"""
+    return g if m is None else g._replace(name=_name_after(g.name, m))
+
+
+class _ColumnPoints(NamedTuple):
+    """the dims of the column operators' points (`Grid._column_points`) and `held`, every dim the three axes hold"""
+
+    tz: str
+    zf: str
+    yc: str
+    yl: str
+    xc: str
+    xl: str
+    held: set
 
 
 class _DimsOnly:
@@ -1254,6 +1271,45 @@ class Grid:
             return None  # (the chain raises the missing-boundary error)
         return bc[x_axis], bc[y_axis], fill_of(fv[x_axis]), fill_of(fv[y_axis])
 
+    def _xyz_plan(self, fields, x_axis, y_axis, z_axis, padding, fill_value, metrics, z_modes=None):
+        """`_second_order_plan`'s four extended by (bc_z, fill_z), else None: also where Z has no boundary (the chain raises)
+        or one outside `z_modes`.  The one-axis operators of a chain hand their fill value on as it is (None: 0.0), so a
+        -0.0 or a NaN keeps its bits on all three axes"""
+        plan = self._second_order_plan(fields, x_axis, y_axis, padding, fill_value, metrics)
+        if plan is None:
+            return None
+        bcz = self._complete_user_kwargs_using_axis_defaults(padding, "padding")[z_axis]
+        if bcz is None or (z_modes is not None and bcz not in z_modes):
+            return None
+        return plan + (bcz, fill_of(self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")[z_axis]))
+
+    def _stage_metrics(self, stages, like, metric_weighted):
+        """the metrics of the `stages` (dims, axes, name) of a one-pass operator, resident where `like` is; None each when
+        not `metric_weighted`.  None, not served: a lookup raises (the chain raises it where the chain looks the metric
+        up), a metric has a dim outside its stage, or one is chunked"""
+        if not metric_weighted:
+            return [None] * len(stages)
+        try:
+            mets = [self._resident(self.get_metric(_DimsOnly(dims, name), axes, _layout=dims), like) for dims, axes, name in stages]
+        except (KeyError, ValueError):
+            return None
+        fits = all(set(m.dims) <= set(dims) and not _is_chunked(m.data) for m, (dims, _, _) in zip(mets, stages))
+        return mets if fits else None
+
+    def _column_points(self, x_axis, y_axis, z_axis, to):
+        """(`to`, the points) of an operator over (lead, Z, Y, X) columns with faces at Z:`to` (None: `outer` where the Z axis
+        has it, else `left`).  The points are None unless `to` is `left` or `outer` and a position of Z, all three axes
+        have `center`, X and Y have `left`, and Z has no face connection or fold"""
+        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
+        if to is None:
+            to = "outer" if "outer" in zax.coords else "left"
+        if not (to in ("left", "outer") and to in zax.coords and all("center" in ax.coords for ax in (zax, yax, xax))
+                and "left" in yax.coords and "left" in xax.coords and not gridops.complex_topology(self, z_axis)):
+            return to, None
+        held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
+        return to, _ColumnPoints(zax.coords["center"], zax.coords[to], yax.coords["center"], yax.coords["left"],
+                                 xax.coords["center"], xax.coords["left"], held)
+
     def flux_divergence(self, u, v, tracer, x_axis: str = "X", y_axis: str = "Y", padding=None, fill_value=None,
                         metric_weighted: bool = True):
         """Flux-form advection tendency `divergence(flux(u, v, tracer))` in ONE pass: u, v and the tracer are read once,
@@ -1411,11 +1467,7 @@ class Grid:
                     factors = (functools.reduce(operator.mul, factors[1:], factors[0]),)
                 factors = tuple(self._resident(f, t.data) for f in factors)
             if all(set(f.dims) <= set(out_dims) for f in factors) and not gridops.complex_topology(self, z_axis):
-                plan = self._second_order_plan([u, v, w, t], x_axis, y_axis, padding, fill_value, list(factors))
-            if plan is not None:
-                bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
-                fv = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
-                plan = None if bc[z_axis] is None else plan + (bc[z_axis], fill_of(fv[z_axis]))
+                plan = self._xyz_plan([u, v, w, t], x_axis, y_axis, z_axis, padding, fill_value, list(factors))
         if plan is None:
             kw = dict(padding=padding, fill_value=fill_value)
             fx, fy = self.flux(args[0], args[1], args[3], x_axis, y_axis, **kw)
@@ -1634,14 +1686,9 @@ class Grid:
                 weight = None  # (the chain raises it where the chain looks the metric up)
             if weight is not None and all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data))
                                           for m, dims in ((weight, b.dims), (mx, dims_x), (my, dims_y))):
-                plan = self._second_order_plan([b], x_axis, y_axis, padding, fill_value,
-                                               [m for m in (weight, mx, my) if m is not None])
-            if plan is not None:
-                bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
-                fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
-                # periodic: the pad is the column total; no boundary: the chain raises
-                plan = None if bc[z_axis] not in ("fill", "extend") else \
-                    plan + (bc[z_axis], 0.0 if fval[z_axis] is None else float(fval[z_axis]))  # (as cumsum: -0.0 stays)
+                # periodic Z: the pad is the column total
+                plan = self._xyz_plan([b], x_axis, y_axis, z_axis, padding, fill_value,
+                                      [m for m in (weight, mx, my) if m is not None], z_modes=("fill", "extend"))
         if plan is None:
             kw = dict(padding=padding, fill_value=fill_value)
             p = self.cumint(arg, z_axis, to="outer", **kw)
@@ -1731,15 +1778,7 @@ class Grid:
             except (KeyError, ValueError):
                 fits = False  # (the chain raises it where the chain looks the metric up)
             if fits:
-                plan = self._second_order_plan([u, v, w], x_axis, y_axis, padding, fill_value,
-                                               [m for m in (mu, mv) if m is not None])
-            if plan is not None:
-                bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
-                fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
-                # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as
-                # it is (None: 0.0), so a -0.0 keeps its sign on all three axes
-                fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
-                plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
+                plan = self._xyz_plan([u, v, w], x_axis, y_axis, z_axis, padding, fill_value, [m for m in (mu, mv) if m is not None])
         if plan is None:
             kw = dict(padding=padding, fill_value=fill_value)
             u, v, w = args
@@ -2008,19 +2047,12 @@ class Grid:
         dt = float(dt)
         if not (dt >= 0.0 and np.isfinite(dt)):
             raise ValueError(f"{what}: dt must be finite and not negative, got {dt}")
-        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
-        if to is None:
-            to = "outer" if "outer" in zax.coords else "left"
-        plan = None
-        served = (all(isinstance(f, DataArray) for f in (u, v, nu)) and u.ndim >= 3 and to in ("left", "outer") and to in zax.coords
-                  and all("center" in ax.coords for ax in (zax, yax, xax)) and "left" in yax.coords and "left" in xax.coords
-                  and not gridops.complex_topology(self, z_axis) and not _is_chunked(nu.data))
-        mets = [None] * 4
+        to, pts = self._column_points(x_axis, y_axis, z_axis, to)
+        plan = mets = None
+        served = all(isinstance(f, DataArray) for f in (u, v, nu)) and u.ndim >= 3 and pts is not None and not _is_chunked(nu.data)
         if served:
-            tz, zf = zax.coords["center"], zax.coords[to]
-            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            tz, zf, yc, yl, xc, xl, held = pts
             lead = u.dims[:-3]
-            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
             nu_dims = lead + (zf, yc, xc)   # the dims nu is read at: those of `lead` it lacks are broadcast
             f_shape = tuple(u.shape[:-3]) + (u.shape[-3] + (1 if to == "outer" else 0),) + tuple(u.shape[-2:])
             served = (u.dims == lead + (tz, yc, xl) and v.dims == lead + (tz, yl, xc) and not held & set(lead)
@@ -2029,14 +2061,8 @@ class Grid:
         if served:
             # the stages of the two solves: u's flux, u's result, v's flux, v's result
             m_dims = [lead + (zf, yc, xl), u.dims, lead + (zf, yl, xc), v.dims]
-            try:
-                if metric_weighted:
-                    for k, f in enumerate((u, u, v, v)):
-                        mets[k] = self._resident(self.get_metric(_DimsOnly(m_dims[k], f.name), (z_axis,), _layout=m_dims[k]), u.data)
-                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, m_dims))
-            except (KeyError, ValueError):
-                served = False  # (the chain raises it where the chain looks the metric up)
-        if served:
+            mets = self._stage_metrics([(dims, (z_axis,), f.name) for dims, f in zip(m_dims, (u, u, v, v))], u.data, metric_weighted)
+        if mets is not None:
             plan = self._second_order_plan([u, v], x_axis, y_axis, padding, fill_value, [nu] + [m for m in mets if m is not None])
         if plan is None:
             kw = dict(padding=padding, fill_value=fill_value)
@@ -2046,10 +2072,7 @@ class Grid:
             xu = self.implicit_vertical_diffusion(u, nu_u, dt, z_axis=z_axis, to=to_arg, metric_weighted=metric_weighted)
             xv = self.implicit_vertical_diffusion(v, nu_v, dt, z_axis=z_axis, to=to_arg, metric_weighted=metric_weighted)
             return xu, xv
-        bcx, bcy = plan[0], plan[1]
-        # the one-axis operators of the chain hand their fill value on as it is (None: 0.0): a -0.0 or a NaN keeps its bits
-        fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
-        fvx, fvy = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis))
+        bcx, bcy, fvx, fvy = plan  # (the fills as the chain's one-axis operators hand them on: a -0.0 or a NaN keeps its bits)
         host = not any(_is_tensor(f.data) for f in (u, v, nu))
         ou, ov = _dev.implicit_vertical_viscosity(u.data, v.data, _aligned_view(nu, nu_dims),
                                                   *(None if m is None else _aligned_view(m, dims) for m, dims in zip(mets, m_dims)),
@@ -2159,46 +2182,24 @@ class Grid:
         args = (b, u, v)
         (b, xr0), (u, xr1), (v, xr2) = (self._wrap_in(a) for a in args)
         was_xr = xr0 or xr1 or xr2
-        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
-        if to is None:
-            to = "outer" if "outer" in zax.coords else "left"
-        plan = None
+        to, pts = self._column_points(x_axis, y_axis, z_axis, to)
+        plan = mets = None
         fields = [f for f in (u, v, b) if f is not None]
-        served = (all(isinstance(f, DataArray) and f.ndim >= 3 for f in fields) and to in ("left", "outer") and to in zax.coords
-                  and all("center" in ax.coords for ax in (zax, yax, xax))
-                  and "left" in yax.coords and "left" in xax.coords and u.shape[-3] > 0
-                  and not gridops.complex_topology(self, z_axis))
+        served = all(isinstance(f, DataArray) and f.ndim >= 3 for f in fields) and pts is not None and u.shape[-3] > 0
         if served:
-            tz, zf = zax.coords["center"], zax.coords[to]
-            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            tz, zf, yc, yl, xc, xl, held = pts
             lead = u.dims[:-3]
-            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
             served = (u.dims == lead + (tz, yc, xl) and v.dims == lead + (tz, yl, xc) and (not ri or b.dims == lead + (tz, yc, xc))
                       and not held & set(lead))
-        mets = [None, None, None]
         if served:
             f_shape = tuple(u.shape[:-3]) + (u.shape[-3] + (1 if to == "outer" else 0),) + tuple(u.shape[-2:])
             f_dims = [lead + (zf, yc, xl), lead + (zf, yl, xc), lead + (zf, yc, xc)]   # the derivatives of u, v, b; the result
-            try:
-                if metric_weighted:
-                    for k, f in enumerate((u, v, b)):
-                        if f is not None:
-                            mets[k] = self._resident(self.get_metric(_DimsOnly(f_dims[k], f.name), (z_axis,), _layout=f_dims[k]),
-                                                     u.data)
-                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, f_dims))
-            except (KeyError, ValueError):
-                served = False  # (the chain raises it where the chain looks the metric up)
-        if served:
-            plan = self._second_order_plan(fields, x_axis, y_axis, padding, fill_value, [m for m in mets if m is not None])
+            mets = self._stage_metrics([(dims, (z_axis,), f.name) for dims, f in zip(f_dims, fields)], u.data, metric_weighted)
+        if mets is not None:
+            mets += [None] * (3 - len(mets))   # (no b: no third stage)
+            plan = self._xyz_plan(fields, x_axis, y_axis, z_axis, padding, fill_value, [m for m in mets if m is not None])
         if plan is not None and closure is not None and not all(_weak_scalar(s, u.data) for s in closure):
             plan = None   # (an array, a wider numpy scalar: the chain's own promotion)
-        if plan is not None:
-            bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
-            fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
-            # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as it is
-            # (None: 0.0), so a -0.0 or a NaN keeps its bits on all three axes
-            fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
-            plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
         if plan is None:
             kw = dict(padding=padding, fill_value=fill_value)
             b, u, v = args
@@ -2428,41 +2429,21 @@ class Grid:
         K7r, or its chain; with `horizontal`: `redi_horizontal_tensor`, one launch of K7u, or its chain"""
         arg, to_arg = b, to
         b, was_xr = self._wrap_in(b)
-        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
-        if to is None:
-            to = "outer" if "outer" in zax.coords else "left"
-        plan = None
-        served = (isinstance(b, DataArray) and b.ndim >= 3 and to in ("left", "outer") and to in zax.coords
-                  and all("center" in ax.coords for ax in (zax, yax, xax))
-                  and "left" in yax.coords and "left" in xax.coords and b.shape[-3] > 0
-                  and not gridops.complex_topology(self, z_axis))
+        to, pts = self._column_points(x_axis, y_axis, z_axis, to)
+        plan = mets = None
+        served = isinstance(b, DataArray) and b.ndim >= 3 and pts is not None and b.shape[-3] > 0
         if served:
-            tz, zf = zax.coords["center"], zax.coords[to]
-            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            tz, zf, yc, yl, xc, xl, held = pts
             lead = b.dims[:-3]
-            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
             served = b.dims == lead + (tz, yc, xc) and not held & set(lead)
-        mets = [None, None, None]
         if served:
             f_shape = tuple(b.shape[:-3]) + (b.shape[-3] + (1 if to == "outer" else 0),) + tuple(b.shape[-2:])
             c_dims = lead + (tz, yc, xc)
             m_dims = [lead + (tz, yc, xl), lead + (tz, yl, xc), lead + (zf, yc, xc)]   # the three derivatives' dims
-            try:
-                if metric_weighted:
-                    for k, ax in enumerate((x_axis, y_axis, z_axis)):
-                        mets[k] = self._resident(self.get_metric(_DimsOnly(m_dims[k], b.name), (ax,), _layout=m_dims[k]), b.data)
-                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, m_dims))
-            except (KeyError, ValueError):
-                served = False  # (the chain raises it where the chain looks the metric up)
-        if served:
-            plan = self._second_order_plan([b], x_axis, y_axis, padding, fill_value, [m for m in mets if m is not None])
-        if plan is not None:
-            bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
-            fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
-            # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as it is
-            # (None: 0.0), so a -0.0 or a NaN keeps its bits on all three axes
-            fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
-            plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
+            mets = self._stage_metrics([(dims, (ax,), b.name) for dims, ax in zip(m_dims, (x_axis, y_axis, z_axis))], b.data,
+                                       metric_weighted)
+        if mets is not None:
+            plan = self._xyz_plan([b], x_axis, y_axis, z_axis, padding, fill_value, [m for m in mets if m is not None])
         if plan is not None and tensor is not None and not (_weak_scalar(tensor[0], b.data)
                                                             and (tensor[1] is None or _weak_scalar(tensor[1], b.data))):
             plan = None   # (an array, a wider numpy scalar: the chain's own promotion)
@@ -2502,9 +2483,6 @@ class Grid:
 
         # dims, coords and names as the chain's, step by step over placeholders: each derivative (named after its quotient
         # with the metric), the mean back to the centre, the mean at the faces, the quotient (the negation changes neither)
-        def named(g, m):
-            return g if m is None else g._replace(name=_name_after(g.name, m))
-
         bz = named(self._labels_of_step(b, m_dims[2], zf, f_shape), mets[2])
         if horizontal:
             # the two derivatives, db/dz back at the levels and at the two points, the cross means, the four quotients; then
@@ -2588,45 +2566,26 @@ class Grid:
         args, to_arg = (a, kwx, kwy), to
         (a, xr1), (kwx, xr2), (kwy, xr3) = self._wrap_in(a), self._wrap_in(kwx), self._wrap_in(kwy)
         was_xr = xr1 or xr2 or xr3
-        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
-        if to is None:
-            to = "outer" if "outer" in zax.coords else "left"
-        plan = None
+        to, pts = self._column_points(x_axis, y_axis, z_axis, to)
+        plan = mets = None
         served = (isinstance(a, DataArray) and isinstance(kwx, DataArray) and isinstance(kwy, DataArray) and a.ndim >= 3
-                  and to in ("left", "outer") and to in zax.coords and all("center" in ax.coords for ax in (zax, yax, xax))
-                  and "left" in yax.coords and "left" in xax.coords and a.shape[-3] > 0
-                  and not gridops.complex_topology(self, z_axis))
+                  and pts is not None and a.shape[-3] > 0)
         if served:
-            tz, zf = zax.coords["center"], zax.coords[to]
-            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            tz, zf, yc, yl, xc, xl, held = pts
             lead = a.dims[:-3]
-            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
             served = a.dims == lead + (tz, yc, xc) and not held & set(lead)
-        mets = [None, None, None]
         if served:
             f_shape = tuple(a.shape[:-3]) + (a.shape[-3] + (1 if to == "outer" else 0),) + tuple(a.shape[-2:])
             c_dims, f_dims = lead + (tz, yc, xc), lead + (zf, yc, xc)
             m_dims = [lead + (tz, yc, xl), lead + (tz, yl, xc), c_dims]   # the two derivatives' dims and the result's
             served = all(k.dims == f_dims and tuple(k.shape) == f_shape for k in (kwx, kwy))
         if served:
-            try:
-                if metric_weighted:
-                    for k, ax in enumerate((x_axis, y_axis, z_axis)):
-                        mets[k] = self._resident(self.get_metric(_DimsOnly(m_dims[k], a.name), (ax,), _layout=m_dims[k]), a.data)
-                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, m_dims))
-            except (KeyError, ValueError):
-                served = False  # (the chain raises it where the chain looks the metric up)
-        if served and not any(_is_chunked(k.data) for k in (kwx, kwy)):
+            mets = self._stage_metrics([(dims, (ax,), a.name) for dims, ax in zip(m_dims, (x_axis, y_axis, z_axis))], a.data,
+                                       metric_weighted)
+        if mets is not None and not any(_is_chunked(k.data) for k in (kwx, kwy)):
             dtype = _dt.np_dtype(a.data)
             if all(_dt.np_dtype(k.data) == dtype for k in (kwx, kwy)):
-                plan = self._second_order_plan([a], x_axis, y_axis, padding, fill_value, [m for m in mets if m is not None])
-        if plan is not None:
-            bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
-            fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
-            # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as it is
-            # (None: 0.0), so a -0.0 or a NaN keeps its bits on all three axes
-            fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
-            plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
+                plan = self._xyz_plan([a], x_axis, y_axis, z_axis, padding, fill_value, [m for m in mets if m is not None])
         if plan is None:
             a, kwx, kwy = args
             kw = dict(padding=padding, fill_value=fill_value)
@@ -2635,7 +2594,7 @@ class Grid:
             gy = self.interp(self.interp(step(a, y_axis, **kw), y_axis, **kw), z_axis, to=to, **kw)
             f = kwx * gx + kwy * gy
             if closed:
-                f = self._closed_flux(f, zax.coords.get(to), to == "outer")
+                f = self._closed_flux(f, self.axes[z_axis].coords.get(to), to == "outer")
             return step(f, z_axis, **kw)
         bcx, bcy, fvx, fvy, bcz, fvz = plan
         host = not any(_is_tensor(x.data) for x in (a, kwx, kwy))
@@ -2646,9 +2605,6 @@ class Grid:
         # dims, coords and name as the chain's, step by step over placeholders: each derivative (named after its quotient
         # with the metric), the mean back to the centre, the mean at the faces, the product with the tensor component; the
         # sum (closing it changes neither coords nor name); the step back to the centre, named after its metric quotient
-        def named(g, m):
-            return g if m is None else g._replace(name=_name_after(g.name, m))
-
         prods = []
         for k, (dim_l, dim_c, kwk) in enumerate(((xl, xc, kwx), (yl, yc, kwy))):
             g = named(self._labels_of_step(a, m_dims[k], dim_l), mets[k])
@@ -2718,43 +2674,26 @@ class Grid:
         args = (kwx, kwy)
         (kwx, xr1), (kwy, xr2) = self._wrap_in(kwx), self._wrap_in(kwy)
         was_xr = xr1 or xr2
-        zax, yax, xax = self.axes[z_axis], self.axes[y_axis], self.axes[x_axis]
+        zax = self.axes[z_axis]
         to = next((pos for pos in ("outer", "left") if zax.coords.get(pos) in getattr(kwx, "dims", ())), None)
-        plan = None
-        served = (isinstance(kwx, DataArray) and isinstance(kwy, DataArray) and kwx.ndim >= 3 and to is not None
-                  and all("center" in ax.coords for ax in (zax, yax, xax)) and "left" in yax.coords and "left" in xax.coords
-                  and not gridops.complex_topology(self, z_axis))
+        pts = self._column_points(x_axis, y_axis, z_axis, to)[1]   # (`to` stays the input's own: None, no face dim, runs the chain)
+        plan = mets = None
+        served = isinstance(kwx, DataArray) and isinstance(kwy, DataArray) and kwx.ndim >= 3 and to is not None and pts is not None
         if served:
-            tz, zf = zax.coords["center"], zax.coords[to]
-            yc, yl, xc, xl = yax.coords["center"], yax.coords["left"], xax.coords["center"], xax.coords["left"]
+            tz, zf, yc, yl, xc, xl, held = pts
             lead = kwx.dims[:-3]
-            held = set(zax.coords.values()) | set(yax.coords.values()) | set(xax.coords.values())
             nz = kwx.shape[-3] - (1 if to == "outer" else 0)
             served = (kwx.dims == lead + (zf, yc, xc) and kwy.dims == kwx.dims and tuple(kwy.shape) == tuple(kwx.shape)
                       and not held & set(lead) and nz > 0)
-        mets = [None] * 5
         if served:
             l_shape = tuple(kwx.shape[:-3]) + (nz,) + tuple(kwx.shape[-2:])
             w_dims = kwx.dims
             # the five metrics' stages: ub's and vb's dims, px's and py's, wb's
             m_dims = [lead + (tz, yc, xl), lead + (tz, yl, xc), lead + (zf, yc, xl), lead + (zf, yl, xc), w_dims]
             m_axes = [(z_axis,), (z_axis,), (y_axis,), (x_axis,), (x_axis, y_axis)]
-            try:
-                if metric_weighted:
-                    for k in range(5):
-                        mets[k] = self._resident(self.get_metric(_DimsOnly(m_dims[k], kwx.name), m_axes[k], _layout=m_dims[k]), kwx.data)
-                served = all(m is None or (set(m.dims) <= set(dims) and not _is_chunked(m.data)) for m, dims in zip(mets, m_dims))
-            except (KeyError, ValueError):
-                served = False  # (the chain raises it where the chain looks the metric up)
-        if served:
-            plan = self._second_order_plan([kwx, kwy], x_axis, y_axis, padding, fill_value, [m for m in mets if m is not None])
-        if plan is not None:
-            bc = self._complete_user_kwargs_using_axis_defaults(padding, "padding")
-            fval = self._complete_user_kwargs_using_axis_defaults(fill_value, "fill_value")
-            # (no boundary along Z: the chain raises)  The one-axis operators of the chain hand their fill value on as it is
-            # (None: 0.0), so a -0.0 or a NaN keeps its bits on all three axes
-            fvx, fvy, fvz = (0.0 if fval[ax] is None else float(fval[ax]) for ax in (x_axis, y_axis, z_axis))
-            plan = None if bc[z_axis] is None else (plan[0], plan[1], fvx, fvy, bc[z_axis], fvz)
+            mets = self._stage_metrics([(dims, axes, kwx.name) for dims, axes in zip(m_dims, m_axes)], kwx.data, metric_weighted)
+        if mets is not None:
+            plan = self._xyz_plan([kwx, kwy], x_axis, y_axis, z_axis, padding, fill_value, [m for m in mets if m is not None])
         if plan is None:
             kwx, kwy = args
             kw = dict(padding=padding, fill_value=fill_value)
@@ -2781,9 +2720,6 @@ class Grid:
         # dims, coords and names as the chain's, step by step over placeholders: the two means (closing them changes neither
         # coords nor name), the step to the centre named after its metric quotient (the negation changes neither), the
         # transports named after their products, the divergence nameless with the coords of its two components
-        def named(g, m):
-            return g if m is None else g._replace(name=_name_after(g.name, m))
-
         px = self._labels_of_step(kwx, m_dims[2], xl)
         py = self._labels_of_step(kwy, m_dims[3], yl)
         ub = named(self._labels_of_step(px, m_dims[0], tz, l_shape), mets[0])
